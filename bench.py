@@ -249,6 +249,18 @@ def profile_kernel_groups(m, eng, cfg_scale):
     return by, gsum, family_replay_ms
 
 
+def dump_outputs(path, eng):
+    """`--dump-outputs DIR`: what the last timed step handed its caller, as DIR/<name>.npy (float32, V x 5 x S x S each, under 1 MB at
+    the benchmark's sizes): the updated latents `x` of every view, and the x0 estimate `x0` and the classifier-free-guided noise
+    prediction `eps` of the query views this process owns (every view on one GPU).  Inputs and weights are seeded, so two builds run
+    with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    own = slice(eng.q0, eng.q0 + eng.Vq)
+    for name, t in (("x", eng.x), ("x0", eng.x0[own]), ("eps", eng.eps[own])):
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def cpu_baseline(sd, V, S, D, cfg_scale, n_timed=3, threads=16):
     """The CPU oracle (port of the reference path, pinned to it by tests/golden) on this host's cores."""
     from mvdfusion_amd import synthetic as syn
@@ -406,7 +418,13 @@ def main():
     ap.add_argument("--shard-emulate", default=None, metavar="r/N",
                     help="single GPU: also time the work of rank r of an N-way view-parallel job (Vq = V/N query views); "
                          "several ranks: '0/8,7/8'")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the latents / x0 estimate / noise prediction of the last timed step as DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and (a.train_step or a.dry_run):
+        ap.error("--dump-outputs writes the denoising step's outputs: not with --train-step or --dry-run")
     if a.train_step:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_train
@@ -482,6 +500,8 @@ def main():
         return time.perf_counter() - t0, ev0.elapsed_ms(ev1) / a.steps
 
     dt, gpu_ms = timed_run(eng, ex)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng)
     if a.tune_cache and not os.path.exists(a.tune_cache) and rank == 0:
         hip.save_tuned(a.tune_cache)
     if world > 1:

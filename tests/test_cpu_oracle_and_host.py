@@ -289,13 +289,15 @@ def test_factory_resolves_reference_targets():
     assert isinstance(s, DDPMScheduler)
 
 
-def test_zero_edit_drop_in_aliases_and_reference_yaml_configs():
+def test_zero_edit_drop_in_aliases_and_reference_yaml_configs(tmp_path):
     """north_star: "demo.py and train.py drop in unchanged".  mvdfusion_amd.install_aliases() registers the mirrors under the reference's
     dotted module names, so `from utils.load_model import instantiate_from_config` (demo.py:21, train.py:24) and the yaml `target:`
-    strings (utils/load_model.py:10-25) resolve to this package.  In a clean interpreter: (1) the aliases alone (no reference on the
-    path -- the GPU box); (2) container-only, with /root/reference/configs present: EVERY `target:` of the model block of EVERY shipped
-    yaml resolves, and `instantiate_from_config(cfg.model)` builds the full ViewFusion (weight paths cleared: no checkpoints offline;
-    parameter initialisers skipped for speed) with the yaml's own n_pts_per_ray / finetune_unet."""
+    strings (utils/load_model.py:10-25) resolve to this package.  In a clean interpreter, with no reference on the path: (1) the aliases
+    alone; (2) the yaml-shaped model block of the two shipped configuration families -- sampling (n_pts_per_ray 1, frozen UNet, 15 views,
+    configs/mvd_gso.yaml) and training (n_pts_per_ray 3, finetuned UNet, 7 views, configs/mvd_train.yaml), built by
+    mvdfusion_amd.configs.model_config with the VAE block of the yaml: EVERY `target:` resolves, and `instantiate_from_config(model)` builds
+    the full ViewFusion (weight paths cleared: no checkpoints offline; parameter initialisers skipped for speed) with that n_pts_per_ray /
+    finetune_unet."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -317,42 +319,41 @@ from external.sd1.ldm.models.autoencoder import AutoencoderKL
 from external.sd1.ldm.modules.encoders.modules import FrozenCLIPImageEmbedder
 assert ViewFusion.__module__.startswith("mvdfusion_amd.") and AutoencoderKL.__module__.startswith("mvdfusion_amd.")
 out = {"aliases": len(names), "configs": {}}
-cfgdir = "/root/reference/configs"
-if os.path.isdir(cfgdir):
-    import yaml
-    for name in sorted(os.listdir(cfgdir)):
-        cfg = yaml.safe_load(open(os.path.join(cfgdir, name)))
-        targets = []
-        def walk(n):
-            if isinstance(n, dict):
-                if "target" in n: targets.append(n["target"].strip())
-                for v in n.values(): walk(v)
-        walk(cfg["model"])
-        for t in targets:
-            cls = get_obj_from_str(t)
-            assert t.startswith("torch.") or cls.__module__.startswith("mvdfusion_amd."), (t, cls)
-        mc = cfg["model"]
-        for k in ("vae_path", "clip_path", "unet_path", "unet_cc_path"):
-            mc["params"][k] = None
-        m = instantiate_from_config(mc)
-        assert type(m).__module__ == "mvdfusion_amd.viewfusion_zero_depth_rgb"
-        assert m.view_attn.n_pts_per_ray == mc["params"]["view_attn_config"]["params"]["n_pts_per_ray"]
-        assert m.finetune_unet == mc["params"]["finetune_unet"]
-        assert all(p.requires_grad == m.finetune_unet for n, p in m.unet_model.named_parameters() if ".aligned_attn_" not in n)
-        V = cfg["inference"]["train_batch_size"]
-        assert m.view_attn.fused_supported(V, V * V * 1024 * m.view_attn.n_pts_per_ray), (name, V)      # the shipped view counts take the fused kernel
-        out["configs"][name] = dict(targets=len(targets), views=V, params=sum(p.numel() for p in m.parameters()))
+from mvdfusion_amd.configs import model_config
+vae = {"target": "external.sd1.ldm.models.autoencoder.AutoencoderKL",
+       "params": {"embed_dim": 4, "monitor": "val/rec_loss", "lossconfig": {"target": "torch.nn.Identity"},
+                  "ddconfig": {"double_z": True, "z_channels": 4, "resolution": 256, "in_channels": 3, "out_ch": 3, "ch": 128,
+                               "ch_mult": [1, 2, 4, 4], "num_res_blocks": 2, "attn_resolutions": [], "dropout": 0.0}}}
+for name, D, finetune, V in (("sampling", 1, False, 15), ("training", 3, True, 7)):
+    params = model_config(320, D=D, finetune_unet=finetune, vae_config=vae, clip_path=None, unet_cc_path=None)
+    del params["precision"]                                   # (not a yaml key: the package default applies)
+    mc = {"target": "mvdfusion.viewfusion_zero_depth_rgb.ViewFusion", "params": params}
+    targets = []
+    def walk(n):
+        if isinstance(n, dict):
+            if "target" in n: targets.append(n["target"].strip())
+            for v in n.values(): walk(v)
+    walk(mc)
+    for t in targets:
+        cls = get_obj_from_str(t)
+        assert t.startswith("torch.") or cls.__module__.startswith("mvdfusion_amd."), (t, cls)
+    m = instantiate_from_config(mc)
+    assert type(m).__module__ == "mvdfusion_amd.viewfusion_zero_depth_rgb"
+    assert m.view_attn.n_pts_per_ray == D
+    assert m.finetune_unet == finetune
+    assert all(p.requires_grad == m.finetune_unet for n, p in m.unet_model.named_parameters() if ".aligned_attn_" not in n)
+    assert m.view_attn.fused_supported(V, V * V * 1024 * m.view_attn.n_pts_per_ray), (name, V)      # the shipped view counts take the fused kernel
+    out["configs"][name] = dict(targets=len(targets), views=V, params=sum(p.numel() for p in m.parameters()))
 print("ALIASJSON " + json.dumps(out))
 """ % root
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
+    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=600, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-3000:]
     import json
     rec = json.loads(r.stdout[r.stdout.index("ALIASJSON ") + 10:].splitlines()[0])
     assert rec["aliases"] >= 9
-    if os.path.isdir("/root/reference/configs"):
-        assert set(rec["configs"]) == {"mvd_colab.yaml", "mvd_gso.yaml", "mvd_train.yaml", "mvd_wild.yaml"}, rec
-        assert all(c["targets"] == 6 and c["params"] > 1.0e9 for c in rec["configs"].values()), rec
+    assert set(rec["configs"]) == {"sampling", "training"}, rec
+    assert all(c["targets"] == 6 and c["params"] > 1.0e9 for c in rec["configs"].values()), rec
 
 
 def test_precision_policy_parsing():
