@@ -309,6 +309,11 @@ int mvd_pixel_cross_attn(const float* q, const float* k, const float* v, void* o
  * With cfg == 0 only the first V rows are produced. */
 int mvd_unet_input(const float* x, const float* input_latents, void* out_sp, int V, int S, int cpad, int cfg,
                    mvd_stream_t stream);
+/* mvd_unet_input for nscene scenes of V views each (nscene >= 1; mvd_unet_input is nscene = 1): x (nscene*V,5,S,S) scene-major
+ * (global view g = scene*V + v), input_latents (nscene,5,S,S) -> out (2*nscene*V*S*S, cpad): conditional row g = [x[g], il[g / V]],
+ * null rows [nscene*V, 2*nscene*V) = [x, 0]. */
+int mvd_unet_input_scenes(const float* x, const float* input_latents, void* out_sp, int nscene, int V, int S, int cpad, int cfg,
+                          mvd_stream_t stream);
 /* out[r, 0:Ca] = a[r], out[r, Ca:Ca+Cb] = b[r]  (torch.cat([h, hs.pop()], dim=1), unet.py:550) */
 int mvd_concat_channels(const float* a, int Ca, const float* b, int Cb, float* out, void* out_sp, int rows, long long* gn_stats,
                         int gn_hw, int gn_groups, mvd_stream_t stream);
@@ -361,6 +366,14 @@ int mvd_gridattn_tokens(const float* x, const float* depth_noise, const float* s
                         const float* feat, const float* in_feat, const float* cams, const float* in_cam,
                         void* tokens_sp, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
                         mvd_stream_t stream);
+/* mvd_gridattn_tokens for nscene independent scenes of V views each in one launch (nscene >= 1; mvd_gridattn_tokens is nscene = 1).
+ * Global view g = scene*V + v: x (nscene*V,5,S,S), feat (nscene*V,S,S,256), cams (nscene*V, MVD_CAM_RECORD), depth_noise
+ * (nsteps, nscene*V, D, S, S); per scene: in_feat (nscene,S,S,256), in_cam (nscene, MVD_CAM_RECORD).  Rows are scene-major:
+ * scene*(Vq*S*S*D*V) + the single-scene row; every scene takes the query views [q0, q0+Vq) of its own rig. */
+int mvd_gridattn_tokens_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                               const float* feat, const float* in_feat, const float* cams, const float* in_cam, void* tokens_sp,
+                               int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
+                               mvd_stream_t stream);
 /* Fused G1-G4 (:269-397): tokens are generated in registers and pushed through pre_layer_b, the 3 DiTBlocks over the V views,
  * and the weight_layer softmax pooling in ONE launch; output = the pooled (Vq*S*S*D, 256) rows as split planes (the final
  * Linear 256->768 is a plain mvd_gemm).  1 <= V <= 16: a wavefront owns 16 token rows = 16 / Vp points, Vp = the next power of
@@ -381,6 +394,14 @@ int mvd_gridattn_fused(const float* x, const float* depth_noise, const float* st
                        const float* vecs, void* pooled_sp, int V, int q0, int Vq, int S, int D, float depth_scale,
                        float depth_shift, int prec /* MVD_PREC_X3 | MVD_PREC_X4: partial products per MAC, as mvd_gemm_desc.prec */,
                        mvd_stream_t stream);
+/* mvd_gridattn_fused for nscene independent scenes of V views each in one launch (nscene >= 1; mvd_gridattn_fused is nscene = 1),
+ * same per-view / per-scene layouts as mvd_gridattn_tokens_scenes; pooled rows scene-major (scene*Vq*S*S*D + the single-scene row).
+ * Vq*S*S*D*Vp (one scene's padded token rows) must be a multiple of 64: a workgroup never straddles two scenes.  The weight stream
+ * and vecs are shared by all scenes (one timestep). */
+int mvd_gridattn_fused_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                              const float* feat, const float* in_feat, const float* cams, const float* in_cam, const void* wstream,
+                              const float* vecs, void* pooled_sp, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale,
+                              float depth_shift, int prec, mvd_stream_t stream);
 /* timm Attention core over the V reference views (:52): qkv (Nseq*V, 3*heads*dhead) -> out (Nseq*V, heads*dhead) */
 int mvd_view_mha(const float* qkv, void* out_sp, int Nseq, int V, int heads, int dhead,
                  mvd_stream_t stream); /* output: split planes */

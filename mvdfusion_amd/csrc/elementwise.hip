@@ -60,8 +60,9 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ W, 
   }
 }
 
+// V = views of all scenes (conditional rows [0, V), null rows [V, 2V)); Vs = views per scene: conditional row b takes input latent b / Vs
 __global__ __launch_bounds__(256) void unet_input_kernel(const float* __restrict__ x, const float* __restrict__ il,
-                                                         u16* __restrict__ out_sp, int V, int S, int cpad, int nb) {
+                                                         u16* __restrict__ out_sp, int V, int Vs, int S, int cpad, int nb) {
   const int SS = S * S;
   const size_t total = (size_t)nb * SS * cpad;
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
@@ -73,7 +74,7 @@ __global__ __launch_bounds__(256) void unet_input_kernel(const float* __restrict
     if (c < 5) {
       o = x[((size_t)v * 5 + c) * SS + pix];
     } else if (c < 10 && b < V) {
-      const float t = il[(size_t)(c - 5) * SS + pix];
+      const float t = il[((size_t)(b / Vs) * 5 + (c - 5)) * SS + pix];
       o = (c < 9) ? t / 0.18215f : t;
     }
     store_sp1(out_sp, e / cpad, cpad, c, o);
@@ -383,15 +384,22 @@ extern "C" int mvd_gemv(const float* W, const float* bias, const float* x, float
   return 0;
 }
 
-extern "C" int mvd_unet_input(const float* x, const float* input_latents, void* out_sp, int V, int S, int cpad, int cfg,
-                              mvd_stream_t stream) {
+extern "C" int mvd_unet_input_scenes(const float* x, const float* input_latents, void* out_sp, int nscene, int V, int S, int cpad, int cfg,
+                                     mvd_stream_t stream) {
   MVD_CHECK_ARG(x && input_latents && out_sp && cpad % 32 == 0 && V > 0 && S > 0 && cpad >= 10, "mvd_unet_input: bad arguments");
-  const int nb = cfg ? 2 * V : V;
+  MVD_CHECK_ARG(nscene >= 1 && (long long)nscene * V <= 0x3fffffff, "mvd_unet_input_scenes: nscene=%d (>= 1)", nscene);
+  const int NV = nscene * V;
+  const int nb = cfg ? 2 * NV : NV;
   const size_t total = (size_t)nb * S * S * cpad;
-  hipLaunchKernelGGL(unet_input_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, input_latents, (u16*)out_sp, V,
+  hipLaunchKernelGGL(unet_input_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, x, input_latents, (u16*)out_sp, NV, V,
                      S, cpad, nb);
   MVD_CHECK_LAUNCH("mvd_unet_input");
   return 0;
+}
+
+extern "C" int mvd_unet_input(const float* x, const float* input_latents, void* out_sp, int V, int S, int cpad, int cfg,
+                              mvd_stream_t stream) {
+  return mvd_unet_input_scenes(x, input_latents, out_sp, 1, V, S, cpad, cfg, stream);
 }
 
 extern "C" int mvd_concat_channels(const float* a, int Ca, const float* b, int Cb, float* out, void* out_sp, int rows,

@@ -2,7 +2,7 @@
 // depth-sample -> unproject -> reproject -> bilinear gather -> Plucker/harmonic embedding kernel that writes the token
 // matrix consumed by the aggregation transformer's first GEMM.
 //
-// One wavefront per 3-D query point (query view b, pixel, depth sample d); it loops over the V reference views and
+// One wavefront per 3-D query point ([scene,] query view b, pixel, depth sample d); it loops over the V reference views and
 // writes one coalesced 736-float row per view: lanes own 4 feature channels each (float4 gathers from the
 // channels-last feature maps, which stay L2/MALL resident: (V+1) x S x S x 256 fp32 = 1 MB per view), and the 210
 // sin/cos embedding values are spread over the lanes.
@@ -14,24 +14,29 @@ __global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ x
                                                      const float* __restrict__ steps, const int* __restrict__ iter,
                                                      const float* __restrict__ grid_lin, const float* __restrict__ feat,
                                                      const float* __restrict__ in_feat, const float* __restrict__ cams,
-                                                     const float* __restrict__ in_cam, u16* __restrict__ tok, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift) {
+                                                     const float* __restrict__ in_cam, u16* __restrict__ tok, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift) {
   const int lane = threadIdx.x & 63;
   const int SS = S * S;
-  const size_t npts = (size_t)Vq * SS * D;
+  const size_t npts = (size_t)nscene * Vq * SS * D;
   const size_t pt = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pt >= npts) return;
   const int d = (int)(pt % D);
   const int pix = (int)((pt / D) % SS);
-  const int b = q0 + (int)(pt / ((size_t)D * SS));  // global index of the query view
+  const int qv = (int)(pt / ((size_t)D * SS));      // scene * Vq + query view (scene-major, like the rows)
+  const int scene = __builtin_amdgcn_readfirstlane(qv / Vq);      // (pt is wave-uniform: one wavefront per point)
+  const int gv0 = scene * V;                         // global index of the scene's view 0
+  const int b = q0 + (qv - scene * Vq);              // index of the query view inside its scene
+  in_feat += (size_t)scene * SS * 256;
+  in_cam += (size_t)scene * MVD_CAM_RECORD;
   const int it = iter[0];
   const float sqrt_ac = steps[(size_t)it * MVD_STEP_STRIDE + 1];
   const float dstd = steps[(size_t)it * MVD_STEP_STRIDE + 2];
 
   // ---- G1: depth sample and world point  (:419-432, ray_utils.py:175-202,367-369)
-  const float dch = x[((size_t)b * 5 + 4) * SS + pix] / sqrt_ac;
-  const float smp = dch + dstd * depth_noise[(((size_t)it * V + b) * D + d) * SS + pix];
+  const float dch = x[((size_t)(gv0 + b) * 5 + 4) * SS + pix] / sqrt_ac;
+  const float smp = dch + dstd * depth_noise[(((size_t)it * nscene * V + gv0 + b) * D + d) * SS + pix];
   const float depth = fminf(fmaxf((smp + 1.0f) / 2.0f, 0.f), 1.f) * depth_scale + depth_shift;
-  const Cam cb = load_cam(cams + (size_t)b * MVD_CAM_RECORD);
+  const Cam cb = load_cam(cams + (size_t)(gv0 + b) * MVD_CAM_RECORD);
   const float ndx = grid_lin[pix % S], ndy = grid_lin[pix / S];
   float p1[3], p2[3], dir[3], org[3], X[3];
   unproject(cb, ndx, ndy, 1.f, p1);
@@ -69,10 +74,10 @@ __global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ x
   }
   // ---- per reference view
   for (int vr = 0; vr < V; ++vr) {
-    const Cam cv = load_cam(cams + (size_t)vr * MVD_CAM_RECORD);
+    const Cam cv = load_cam(cams + (size_t)(gv0 + vr) * MVD_CAM_RECORD);
     float u, v;
     project(cv, X, u, v);
-    const float4 fr = bilinear4(feat + (size_t)vr * SS * 256, S, lane * 4, -u, -v);
+    const float4 fr = bilinear4(feat + (size_t)(gv0 + vr) * SS * 256, S, lane * 4, -u, -v);
     float rd[3] = {X[0] - cv.C[0], X[1] - cv.C[1], X[2] - cv.C[2]};
     const float nr = sqrtf(rd[0] * rd[0] + rd[1] * rd[1] + rd[2] * rd[2]);
     float rdep[1] = {nr};
@@ -227,19 +232,29 @@ extern "C" int mvd_zembed(const float* lat, const float* w, const float* b, floa
   return 0;
 }
 
+extern "C" int mvd_gridattn_tokens_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                          const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                          const float* in_cam, void* tokens_sp, int nscene, int V, int q0, int Vq, int S, int D,
+                                          float depth_scale, float depth_shift, mvd_stream_t stream) {
+  MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && tokens_sp,
+                "mvd_gridattn_tokens: null pointer");
+  MVD_CHECK_ARG(nscene >= 1, "mvd_gridattn_tokens_scenes: nscene=%d (>= 1)", nscene);
+  MVD_CHECK_ARG(V > 0 && V <= 16 && S > 1 && D > 0, "mvd_gridattn_tokens: bad shape (V <= 16)");
+  MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V, "mvd_gridattn_tokens: bad query-view range [%d, %d) of %d", q0, q0 + Vq, V);
+  const size_t npts = (size_t)nscene * Vq * S * S * D;      // one wavefront per point: a point never straddles two scenes
+  MVD_CHECK_ARG((size_t)nscene * V <= 0x7fffffff && (npts + 3) / 4 <= 0x7fffffff, "mvd_gridattn_tokens: grid too large");
+  hipLaunchKernelGGL(tokens_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, x, depth_noise, steps, iter,
+                     grid_lin, feat, in_feat, cams, in_cam, (u16*)tokens_sp, nscene, V, q0, Vq, S, D, depth_scale, depth_shift);
+  MVD_CHECK_LAUNCH("mvd_gridattn_tokens");
+  return 0;
+}
+
 extern "C" int mvd_gridattn_tokens(const float* x, const float* depth_noise, const float* steps, const int* iter,
                                    const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
                                    const float* in_cam, void* tokens_sp, int V, int q0, int Vq, int S, int D, float depth_scale,
                                    float depth_shift, mvd_stream_t stream) {
-  MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && tokens_sp,
-                "mvd_gridattn_tokens: null pointer");
-  MVD_CHECK_ARG(V > 0 && V <= 16 && S > 1 && D > 0, "mvd_gridattn_tokens: bad shape (V <= 16)");
-  MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V, "mvd_gridattn_tokens: bad query-view range [%d, %d) of %d", q0, q0 + Vq, V);
-  const size_t npts = (size_t)Vq * S * S * D;
-  hipLaunchKernelGGL(tokens_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, x, depth_noise, steps, iter,
-                     grid_lin, feat, in_feat, cams, in_cam, (u16*)tokens_sp, V, q0, Vq, S, D, depth_scale, depth_shift);
-  MVD_CHECK_LAUNCH("mvd_gridattn_tokens");
-  return 0;
+  return mvd_gridattn_tokens_scenes(x, depth_noise, steps, iter, grid_lin, feat, in_feat, cams, in_cam, tokens_sp, 1, V, q0, Vq, S, D,
+                                    depth_scale, depth_shift, stream);
 }
 
 extern "C" int mvd_gridattn_tokens_backward(const float* x, const float* depth_noise, const float* steps, const int* iter,

@@ -5,11 +5,14 @@
 //          MLP 256->512->256, gated residuals), weight_layer softmax over V, weighted sum
 // and writes the pooled (Nseq, 256) rows as split planes for the last Linear 256->768 (a plain mvd_gemm).
 //
-// Mapping.  Token rows are ordered ((query view, pixel, depth sample), reference view slot): Vp consecutive rows = one 3-D point =
+// Mapping.  Token rows are ordered (scene, (query view, pixel, depth sample), reference view slot): Vp consecutive rows = one 3-D point =
 // one attention sequence, Vp = the next power of two >= V (so a sequence never straddles a wavefront's 16 rows).  Slots vr >= V are
 // PADDING: they run the arithmetic on a copy of the last reference view (finite values), are masked out as attention KEYS and in the
 // softmax-over-V pooling, and are never stored -- the reference's view counts 15 / 7 / 5 / 3 (configs/mvd_gso.yaml:97, mvd_train.yaml:90,97)
 // take this kernel at 16 / 8 / 8 / 4 slots.  A wavefront owns 16 consecutive rows for the whole kernel; a workgroup is 4 wavefronts (64 rows).
+// Scenes (mvd_gridattn_fused_scenes): N independent rigs in one launch, each with its own cameras, input view and latents, addressed by the
+// global view index scene * V + view; a scene's rows are a whole number of workgroups (checked at launch), so the scene is workgroup-uniform
+// and no point, wavefront or workgroup straddles two scenes.  The weight stream is shared: every scene's rows read the same slots.
 // Activations never touch LDS or HBM: every GEMM is computed as  out^T = W x^T  (MFMA A operand = 16 weight rows, B operand =
 // the wave's 16 activation rows), so a lane holds, for row (lane & 15), four consecutive output channels 16j + 4(lane>>4) + r
 // of each 16-channel tile j -- exactly the register image of the NEXT GEMM's B fragment once the weight k-order inside
@@ -62,6 +65,7 @@ struct G4Params {
   const float* vecs;              // G4_VEC_GRANULES * 256 floats
   u16* pooled_sp;                 // (Nseq, 256) split planes
   int V, Vp, lv, q0, Vq, S, D, nslots;      // Vp = 2^lv >= V: rows per 3-D point (reference views padded to a power of two)
+  int nscene, wg_per_scene;                 // scenes in the launch; workgroups per scene (Vq*S*S*D*Vp / 64)
   float depth_scale, depth_shift;
 };
 
@@ -340,7 +344,9 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   const int vr = pad_row ? V - 1 : vslot;
   const int d = (int)(pt % D);
   const int pix = (int)((pt / D) % SS);
-  const int b = p.q0 + (int)(pt / ((size_t)D * SS));
+  const int scene = (int)(blockIdx.x / (unsigned)p.wg_per_scene);        // workgroup-uniform (scalar)
+  const int b = p.q0 + (int)(pt / ((size_t)D * SS)) - scene * p.Vq;      // query view inside the scene
+  const int gv0 = scene * V;                                             // global index of the scene's view 0
   // geometry of this lane's row: world point, Plucker coordinates, bilinear taps in the reference view and the input view
   Vec6 qpl, rpl;
   float rdep, depth;
@@ -349,10 +355,10 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
     const int it = p.iter[0];
     const float sqrt_ac = p.steps[(size_t)it * MVD_STEP_STRIDE + 1];
     const float dstd = p.steps[(size_t)it * MVD_STEP_STRIDE + 2];
-    const float dch = p.x[((size_t)b * 5 + 4) * SS + pix] / sqrt_ac;
-    const float smp = dch + dstd * p.depth_noise[(((size_t)it * V + b) * D + d) * SS + pix];
+    const float dch = p.x[((size_t)(gv0 + b) * 5 + 4) * SS + pix] / sqrt_ac;
+    const float smp = dch + dstd * p.depth_noise[(((size_t)it * p.nscene * V + gv0 + b) * D + d) * SS + pix];
     depth = fminf(fmaxf((smp + 1.0f) / 2.0f, 0.f), 1.f) * p.depth_scale + p.depth_shift;
-    const Cam cb = load_cam(p.cams + (size_t)b * MVD_CAM_RECORD);
+    const Cam cb = load_cam(p.cams + (size_t)(gv0 + b) * MVD_CAM_RECORD);
     const float ndx = p.grid_lin[pix % S], ndy = p.grid_lin[pix / S];
     float p1[3], p2[3], dir[3], org[3], X[3];
     unproject(cb, ndx, ndy, 1.f, p1);
@@ -372,7 +378,7 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
       qpl.e = cb.C[2] * qpl.a - cb.C[0] * qpl.c;
       qpl.f = cb.C[0] * qpl.b - cb.C[1] * qpl.a;
     }
-    const Cam cv = load_cam(p.cams + (size_t)vr * MVD_CAM_RECORD);
+    const Cam cv = load_cam(p.cams + (size_t)(gv0 + vr) * MVD_CAM_RECORD);
     {
       const float rd[3] = {X[0] - cv.C[0], X[1] - cv.C[1], X[2] - cv.C[2]};
       const float nr = sqrtf(rd[0] * rd[0] + rd[1] * rd[1] + rd[2] * rd[2]);
@@ -389,12 +395,13 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
       float u, v;
       project(cv, X, u, v);
       tr = make_taps(S, -u, -v);
-      const Cam ci = load_cam(p.in_cam);
+      const Cam ci = load_cam(p.in_cam + (size_t)scene * MVD_CAM_RECORD);
       project(ci, X, u, v);
       ti = make_taps(S, -u, -v);
     }
   }
-  const float* fref = p.feat + (size_t)vr * SS * 256;
+  const float* fref = p.feat + (size_t)(gv0 + vr) * SS * 256;
+  const float* const fin = p.in_feat + (size_t)scene * SS * 256;
   // ------------------------------------------------------------------ pre_layer: Linear(723 -> 256) + GELU
   f32x4 h[16];          // residual stream: tile j = channels 16j + 4g + r of row r16
   f32x4 acc[16];
@@ -424,7 +431,7 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int ks = (c4 & 1) * 4 + q;
-      const float* fm = c4 < 2 ? fref : p.in_feat;
+      const float* fm = c4 < 2 ? fref : fin;
       const Taps& tp = c4 < 2 ? tr : ti;
       tk[q] = make_frag(gather4(fm, tp, 32 * ks + 4 * g), gather4(fm, tp, 32 * ks + 16 + 4 * g));
     }
@@ -698,12 +705,13 @@ extern "C" int mvd_gridattn_fused_slots(void) { return 23 + 3 * 64; }
 extern "C" size_t mvd_gridattn_fused_stream_bytes(void) { return (size_t)(23 + 3 * 64) * G4_SLOT_BYTES; }
 extern "C" size_t mvd_gridattn_fused_vec_floats(void) { return (size_t)G4_VEC_GRANULES * 256; }
 
-extern "C" int mvd_gridattn_fused(const float* x, const float* depth_noise, const float* steps, const int* iter,
-                                  const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
-                                  const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int V, int q0,
-                                  int Vq, int S, int D, float depth_scale, float depth_shift, int prec, mvd_stream_t stream) {
+extern "C" int mvd_gridattn_fused_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                         const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                         const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int nscene, int V,
+                                         int q0, int Vq, int S, int D, float depth_scale, float depth_shift, int prec, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && wstream && vecs && pooled_sp,
                 "mvd_gridattn_fused: null pointer");
+  MVD_CHECK_ARG(nscene >= 1, "mvd_gridattn_fused_scenes: nscene=%d (>= 1)", nscene);
   MVD_CHECK_ARG(V >= 1 && V <= 16, "mvd_gridattn_fused: V=%d outside [1, 16] (use the unfused path)", V);
   int lv = 0;
   while ((1 << lv) < V) ++lv;
@@ -712,16 +720,28 @@ extern "C" int mvd_gridattn_fused(const float* x, const float* depth_noise, cons
   MVD_CHECK_ARG(prec == MVD_PREC_X3 || prec == MVD_PREC_X4, "mvd_gridattn_fused: prec %d (MVD_PREC_X3 or MVD_PREC_X4)", prec);
   MVD_CHECK_ARG(((uintptr_t)wstream & 15) == 0 && ((uintptr_t)vecs & 15) == 0 && ((uintptr_t)pooled_sp & 127) == 0,
                 "mvd_gridattn_fused: wstream / vecs must be 16-byte, pooled_sp 128-byte aligned");
-  const size_t T = (size_t)Vq * S * S * D * Vp;           // token rows incl. the padding slots
-  MVD_CHECK_ARG(T % 64 == 0, "mvd_gridattn_fused: padded token count %zu must be a multiple of 64", T);
+  const size_t Ts = (size_t)Vq * S * S * D * Vp;          // token rows of one scene incl. the padding slots
+  // a scene = whole workgroups: the kernel takes the scene from blockIdx.x, and no point / wavefront / workgroup straddles two scenes
+  MVD_CHECK_ARG(Ts % 64 == 0, "mvd_gridattn_fused: padded token count %zu per scene must be a multiple of 64", Ts);
+  MVD_CHECK_ARG(Ts / 64 <= 0x7fffffff && (Ts / 64) * (size_t)nscene <= 0x7fffffff, "mvd_gridattn_fused: grid too large");
   G4Params p;
   p.dbg = g_g4_dbg;
   p.x = x; p.depth_noise = depth_noise; p.steps = steps; p.iter = iter; p.grid_lin = grid_lin; p.feat = feat;
   p.in_feat = in_feat; p.cams = cams; p.in_cam = in_cam; p.wstream = (const unsigned char*)wstream; p.vecs = vecs;
   p.pooled_sp = (u16*)pooled_sp; p.V = V; p.Vp = Vp; p.lv = lv; p.q0 = q0; p.Vq = Vq; p.S = S; p.D = D; p.nslots = 23 + 3 * 64;
+  p.nscene = nscene; p.wg_per_scene = (int)(Ts / 64);
   p.depth_scale = depth_scale; p.depth_shift = depth_shift;
-  if (prec == MVD_PREC_X3) hipLaunchKernelGGL(g4_fused_kernel<3>, dim3((unsigned)(T / 64)), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(g4_fused_kernel<4>, dim3((unsigned)(T / 64)), dim3(256), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)(Ts / 64 * nscene));
+  if (prec == MVD_PREC_X3) hipLaunchKernelGGL(g4_fused_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(g4_fused_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
   MVD_CHECK_LAUNCH("mvd_gridattn_fused");
   return 0;
+}
+
+extern "C" int mvd_gridattn_fused(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                  const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                  const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int V, int q0,
+                                  int Vq, int S, int D, float depth_scale, float depth_shift, int prec, mvd_stream_t stream) {
+  return mvd_gridattn_fused_scenes(x, depth_noise, steps, iter, grid_lin, feat, in_feat, cams, in_cam, wstream, vecs, pooled_sp, 1, V, q0,
+                                   Vq, S, D, depth_scale, depth_shift, prec, stream);
 }

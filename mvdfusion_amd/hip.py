@@ -100,6 +100,7 @@ SIGNATURES = {
     "mvd_attention": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _i, _i, _vp]),
     "mvd_pixel_cross_attn": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvd_unet_input": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvd_unet_input_scenes": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvd_concat_channels": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "mvd_concat_groupnorm_fits": (_i, [_i, _i, _i, _i]),
     "mvd_concat_groupnorm": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
@@ -127,10 +128,12 @@ SIGNATURES = {
     "mvd_advance_iter": (_i, [_vp, _vp]),
     "mvd_zembed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mvd_gridattn_tokens": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _f, _f, _vp]),
+    "mvd_gridattn_tokens_scenes": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "mvd_gridattn_fused_slots": (_i, []),
     "mvd_gridattn_fused_stream_bytes": (_sz, []),
     "mvd_gridattn_fused_vec_floats": (_sz, []),
     "mvd_gridattn_fused": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "mvd_gridattn_fused_scenes": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "mvd_view_mha": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mvd_view_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvd_cfg_ddim_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _f, _i, _vp]),

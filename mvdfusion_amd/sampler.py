@@ -111,3 +111,55 @@ class DDIMSampler:
         from . import hip
         out = hip.check_finite(eng.x.clone(), "DDIMSampler.sample")
         return (out, inter) if return_intermediates else out
+
+    @torch.no_grad()
+    def sample_scenes(self, conds, unconditional_scale, depth=True, return_intermediates=False, verbose=True, x_T=None,
+                      num_steps=None, use_graph=True):
+        """``sample`` for N scenes in one batched step: ``conds`` is a list of (batch_cameras, input_latents, input_cameras,
+        clip_embed), one per scene, all with the same V and S.  Every step runs GridAttn, the CFG-batched UNet (2 N V images: the
+        N V conditional rows scene-major, then the N V null rows) and the update once for all scenes.  Returns x_0 (N, V, 5, S, S)
+        [and the per-step {'t','xt','x0'} list with (N, V, 5, S, S) tensors].  ``x_T``: (N, V, 5, S, S) initial noise.
+        ``noise_source`` is called once per scene, in scene order, exactly as ``sample`` calls it for that scene alone."""
+        assert depth, "MVD-Fusion samples RGB-D latents (depth=True at every call site: demo.py:85-90)"
+        m = self.model
+        N = len(conds)
+        if N < 1:
+            raise ValueError("sample_scenes: no scenes")
+        V, S, D = int(conds[0][3].shape[0]), self.latent_size, m.view_attn.n_pts_per_ray
+        for i, (bc, il, ic, ce) in enumerate(conds):
+            if int(ce.shape[0]) != V or len(bc) != V:
+                raise ValueError(f"sample_scenes: scene {i} has {int(ce.shape[0])} views, scene 0 has {V} (every scene of a call "
+                                 "shares V)")
+            if tuple(il.shape[-2:]) != (S, S):
+                raise ValueError(f"sample_scenes: scene {i} has {tuple(il.shape[-2:])} latents, the sampler's latent size is {S}")
+        if x_T is not None and tuple(x_T.shape) != (N, V, self.z_dim + 1, S, S):
+            raise ValueError(f"sample_scenes: x_T {tuple(x_T.shape)}, expected {(N, V, self.z_dim + 1, S, S)}")
+        dev = m._device.device
+        total = self.ddim_timesteps.shape[0]
+        n_run = total if num_steps is None else int(num_steps)
+        cfg = unconditional_scale != 1.0
+        eng = m.engine(V, S, D, cfg, scenes=N)
+        eng.set_conditioning_scenes([(bc, il.to(dev), ic, ce.to(dev)) for bc, il, ic, ce in conds])
+        st, dd = self.tables()
+        table = ddim_step_table(st, dd, [total - i - 1 for i in range(total)])
+        x_T = torch.randn([N * V, self.z_dim + 1, S, S], device=dev) if x_T is None else x_T.reshape(N * V, self.z_dim + 1, S, S)
+        if self.noise_source is not None:
+            per = [self.noise_source(V, S, D, total) for _ in range(N)]
+            dn = torch.stack([torch.as_tensor(p[0]).reshape(total, V, D, S, S) for p in per], 1).reshape(total, N * V, D, S, S)
+            sn = torch.stack([torch.as_tensor(p[1]).reshape(total, V, 5, S, S) for p in per], 1).reshape(total, N * V, 5, S, S)
+        else:
+            dn = torch.randn(total, N * V, D, S, S, device=dev)
+            sn = torch.randn(total, N * V, 5, S, S, device=dev)
+        eng.set_schedule(table, dn, sn)
+        eng.x.copy_(x_T)
+        inter = []
+        for i in range(n_run):
+            eng.depth_mode = 1 if (self.feed_prev_depth and i > 0) else 0
+            eng.step(unconditional_scale, do_update=True, use_graph=use_graph)
+            if return_intermediates:
+                inter.append({"t": int(self.ddim_timesteps[total - i - 1]), "xt": eng.x.clone().view(N, V, 5, S, S),
+                              "x0": eng.x0.clone().view(N, V, 5, S, S)})
+        eng.depth_mode = 0
+        from . import hip
+        out = hip.check_finite(eng.x.clone(), "DDIMSampler.sample_scenes").view(N, V, 5, S, S)
+        return (out, inter) if return_intermediates else out

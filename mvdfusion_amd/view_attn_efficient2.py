@@ -239,7 +239,7 @@ class GridAttn(nn.Module):
                 all(b.num_heads == 8 and b.mlp.fc1.out_features == 512 for b in blocks))
 
     def run(self, ctx, x, depth_noise, steps, it, cams_rec, in_cam_rec, input_latents, c, vol_out, V, S, D, q0=0, Vq=None,
-            vol_planes=None, vol_planes_col=0, fused=None, depth_src=None, depth_steps=None):
+            vol_planes=None, vol_planes_col=0, fused=None, depth_src=None, depth_steps=None, scenes=1):
         """x (V,5,S,S) noisy latents; c (1,256) time conditioning (t_embed[:1]); vol_out: (>=V*S*S*D, 768) buffer
         whose first Vq*S*S*D rows receive the feature frustum (row = ((v*S + y)*S + x)*D + d) of the query views
         [q0, q0+Vq) (all V views by default; a view-parallel rank passes the range it owns).  vol_planes: optional planes
@@ -248,18 +248,23 @@ class GridAttn(nn.Module):
         of token kernel + GEMMs; True / False force one of them.
         depth_src / depth_steps (overwrite_attn_depth, view_attn_efficient2.py:418-426): a (V,5,S,S) buffer whose channel 4 is the depth
         map to sample around INSTEAD of the x0-style estimate x[:,4] / sqrt(alpha_bar), with a step table whose sqrt(alpha_bar) column
-        is 1 (x / 1 is exact) and whose depth-std column is unchanged -- the kernels themselves are the same."""
+        is 1 (x / 1 is exact) and whose depth-std column is unchanged -- the kernels themselves are the same.
+        scenes: N independent rigs of V views each in one launch (scene-major: x / cams_rec / depth_noise hold N*V views, global view
+        scene*V + v; input_latents / in_cam_rec hold N); vol_out's first N*Vq*S*S*D rows receive the frustums scene after scene."""
         Vq = V if Vq is None else Vq
+        N = int(scenes)
         L = hip.lib()
         assert x.shape[1] == 5, "depth wise efficient attention requires 4+1 channels"
+        assert N == 1 or (N > 1 and x.shape[0] == N * V and input_latents.shape[0] == N and q0 == 0 and Vq == V), \
+            (N, V, q0, Vq, tuple(x.shape), tuple(input_latents.shape))
         w_pre, w_fin = self.packed()
         z = self.z_embedder[0]
-        feat = ctx.ws.get("ga.feat", (V, S, S, 256))
-        in_feat = ctx.ws.get("ga.infeat", (1, S, S, 256))
-        hip.check(L.mvd_zembed(hip.ptr(x), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(feat), V, S, hip.stream()))
-        hip.check(L.mvd_zembed(hip.ptr(input_latents), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(in_feat), 1, S,
+        feat = ctx.ws.get("ga.feat", (N * V, S, S, 256))
+        in_feat = ctx.ws.get("ga.infeat", (N, S, S, 256))
+        hip.check(L.mvd_zembed(hip.ptr(x), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(feat), N * V, S, hip.stream()))
+        hip.check(L.mvd_zembed(hip.ptr(input_latents), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(in_feat), N, S,
                                hip.stream()))
-        nseq = Vq * S * S * D
+        nseq = N * Vq * S * S * D
         T = nseq * V
         dsrc = x if depth_src is None else depth_src
         dsteps = steps if depth_steps is None else depth_steps
@@ -270,25 +275,25 @@ class GridAttn(nn.Module):
             grid_lin = torch.linspace(1.0 - half, -1.0 + half, S, dtype=torch.float32).to(ctx.device)
             ctx.ws.bufs[("ga.lin", S)] = grid_lin
         if fused is None:
-            fused = self.fused_supported(V, T)
+            fused = self.fused_supported(V, T // N)
         if fused:
-            assert self.fused_supported(V, T), (V, T)
+            assert self.fused_supported(V, T // N), (V, T // N)
             stream, vecs = self.packed_fused(ctx.device)
             for bi, blk in enumerate(self.aggregation_transformer.layer_list):      # adaLN modulation of this step -> vecs
                 lin = blk.adaLN_modulation[1]
                 hip.gemv(lin.weight, lin.bias, c, vecs[bi * _G4_VEC_BLOCK:bi * _G4_VEC_BLOCK + 1536].view(1, 1536), act_in=hip.ACT_SILU)
             pool = ctx.ws.planes("ga.pool", nseq, self.hidden_size)
-            hip.check(L.mvd_gridattn_fused(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
-                                           hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec), hip.ptr(stream),
-                                           hip.ptr(vecs), hip.ptr(pool), V, q0, Vq, S, D, float(self.depth_scale),
-                                           float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, hip.stream()))
+            hip.check(L.mvd_gridattn_fused_scenes(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
+                                                  hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec), hip.ptr(stream),
+                                                  hip.ptr(vecs), hip.ptr(pool), N, V, q0, Vq, S, D, float(self.depth_scale),
+                                                  float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, hip.stream()))
             ctx.gemm(pool, w_fin, vol_out, M=nseq, out_planes=vol_planes, out_planes_col=vol_planes_col, kind="ga")
             return vol_out
         tokens = ctx.ws.planes("ga.tokens", T, hip.TOKEN_LD)
-        hip.check(L.mvd_gridattn_tokens(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
-                                        hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec),
-                                        hip.ptr(tokens), V, q0, Vq, S, D, float(self.depth_scale), float(self.depth_shift),
-                                        hip.stream()))
+        hip.check(L.mvd_gridattn_tokens_scenes(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
+                                               hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec),
+                                               hip.ptr(tokens), N, V, q0, Vq, S, D, float(self.depth_scale), float(self.depth_shift),
+                                               hip.stream()))
         h = ctx.ws.get("ga.h", (T, self.hidden_size))
         h_alt = ctx.ws.get("ga.h_alt", (T, self.hidden_size))
         ctx.gemm(tokens, w_pre, h, act=hip.ACT_GELU, kind="ga")

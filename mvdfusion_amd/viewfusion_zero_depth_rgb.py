@@ -40,24 +40,32 @@ def _sinusoid_freqs(dim, max_period=10000):
 
 
 class StepEngine:
-    """One denoising iteration (GridAttn -> CFG-batched UNet -> CFG combine [+ DDIM update]) on static buffers."""
+    """One denoising iteration (GridAttn -> CFG-batched UNet -> CFG combine [+ DDIM update]) on static buffers.
 
-    def __init__(self, model, V, S, D, cfg, device, prec, q0=0, Vq=None, policy=None):
+    scenes = N independent objects denoised together (same V, S, D, cfg, schedule and weights; own cameras, input view, CLIP embedding
+    and noise): every per-view buffer holds N*V views scene-major (global view scene*V + v), the per-scene ones (input latents, input
+    camera) N, and the UNet's CFG batch is [N*V conditional rows | N*V null rows].  View-parallel sharding (q0 / Vq) is single-scene only."""
+
+    def __init__(self, model, V, S, D, cfg, device, prec, q0=0, Vq=None, policy=None, scenes=1):
         self.m, self.V, self.S, self.D, self.cfg = model, V, S, D, bool(cfg)
         self.q0, self.Vq = q0, (V if Vq is None else Vq)   # query views owned by this rank (view-parallel sharding)
+        self.N = N = int(scenes)
+        if N < 1 or (N > 1 and (self.q0 != 0 or self.Vq != V)):
+            raise ValueError(f"StepEngine(scenes={scenes}, q0={q0}, Vq={Vq}, V={V}): view-parallel sharding is single-scene only")
+        NV = N * V
         self.ctx = Ctx(device, prec, policy)
         dev = self.ctx.device
-        B = 2 * self.Vq if cfg else self.Vq
+        B = 2 * N * self.Vq if cfg else N * self.Vq
         self.B = B
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
-        self.x = z(V, 5, S, S)                 # current latents (NCHW like the reference), updated in place
-        self.x0 = z(V, 5, S, S)
-        self.eps = z(V, 5, S, S)
-        self.input_latents = z(1, 5, S, S)
-        self.clip_v_embed = z(V, 796)
-        self.cams = z(V, hip.CAM_RECORD)
-        self.in_cam = z(1, hip.CAM_RECORD)
-        self.context = z(B, 768)               # rows [V,2V) stay zero: the null branch (unet.py:173)
+        self.x = z(NV, 5, S, S)                # current latents (NCHW like the reference), updated in place
+        self.x0 = z(NV, 5, S, S)
+        self.eps = z(NV, 5, S, S)
+        self.input_latents = z(N, 5, S, S)
+        self.clip_v_embed = z(NV, 796)
+        self.cams = z(NV, hip.CAM_RECORD)
+        self.in_cam = z(N, hip.CAM_RECORD)
+        self.context = z(B, 768)               # rows [NV,2NV) stay zero: the null branch (unet.py:173)
         self.vol = z(B * S * S * D, 768)       # rows of the null branch stay zero (unet.py:190)
         # the same as split planes, inside the level-0 operand buffer of the UNet's view-aligned transformers (zero-initialised)
         self.vol_planes, self.vol_col = model.unet_model.level0_operand(self.ctx, B, S, D)
@@ -65,12 +73,12 @@ class StepEngine:
         self.iter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.steps = z(1, hip.STEP_STRIDE)
         self.steps_nodiv = z(1, hip.STEP_STRIDE)   # the same table with sqrt(alpha_bar) = 1: GridAttn's depth source is used as is
-        self.prev = z(V, 5, S, S)              # channel 4: an explicit overwrite_attn_depth (apply_model(prev_depth=...))
+        self.prev = z(NV, 5, S, S)             # channel 4: an explicit overwrite_attn_depth (apply_model(prev_depth=...))
         self.depth_mode = 0                    # GridAttn samples depth around 0: x[:,4] / sqrt(alpha_bar) (the x0-style estimate);
                                                # 1: the previous step's x0 estimate self.x0[:,4] (DDIMSampler feed_prev_depth);
                                                # 2: self.prev[:,4] (view_attn_efficient2.py:418-426)
-        self.depth_noise = z(1, V, D, S, S)
-        self.ddim_noise = z(1, V, 5, S, S)
+        self.depth_noise = z(1, NV, D, S, S)
+        self.ddim_noise = z(1, NV, 5, S, S)
         self.f256 = _sinusoid_freqs(256).to(dev)
         self.funet = _sinusoid_freqs(model.unet_model.unet_model.model_channels).to(dev)
         self.graphs = {}
@@ -81,10 +89,23 @@ class StepEngine:
 
     # -- host-side inputs ----------------------------------------------------------------------------
     def set_conditioning(self, batch_cameras, input_latents, input_cameras, clip_v_embed):
+        if self.N != 1:
+            raise ValueError(f"set_conditioning on a {self.N}-scene engine: use set_conditioning_scenes")
         self.cams.copy_(pack_cameras(batch_cameras).to(self.cams.device))
         self.in_cam.copy_(pack_cameras(input_cameras).to(self.cams.device))
         self.input_latents.copy_(input_latents.reshape(1, 5, self.S, self.S))
         self.clip_v_embed.copy_(clip_v_embed.reshape(self.V, 796))
+
+    def set_conditioning_scenes(self, conds):
+        """conds: one (batch_cameras, input_latents, input_cameras, clip_v_embed) per scene, in scene order."""
+        if len(conds) != self.N:
+            raise ValueError(f"set_conditioning_scenes: {len(conds)} scenes for a {self.N}-scene engine")
+        V, S = self.V, self.S
+        for n, (bc, il, ic, ce) in enumerate(conds):
+            self.cams[n * V:(n + 1) * V].copy_(pack_cameras(bc).to(self.cams.device))
+            self.in_cam[n:n + 1].copy_(pack_cameras(ic).to(self.cams.device))
+            self.input_latents[n:n + 1].copy_(il.reshape(1, 5, S, S))
+            self.clip_v_embed[n * V:(n + 1) * V].copy_(ce.reshape(V, 796))
 
     def set_schedule(self, steps_table, depth_noise, ddim_noise):
         dev = self.ctx.device
@@ -111,7 +132,7 @@ class StepEngine:
         self.done = it
 
     def depth_geo(self):
-        """(depth source (V,5,S,S), step table) GridAttn's kernels read the depth channel and its std from (see depth_mode)."""
+        """(depth source (N*V,5,S,S), step table) GridAttn's kernels read the depth channel and its std from (see depth_mode)."""
         if self.depth_mode == 0:
             return self.x, self.steps
         return (self.x0 if self.depth_mode == 1 else self.prev), self.steps_nodiv
@@ -119,7 +140,8 @@ class StepEngine:
     # -- one iteration -------------------------------------------------------------------------------
     def enqueue(self, cfg_scale, do_update, prefetcher=None):
         m, ctx, L = self.m, self.ctx, hip.lib()
-        V, S, D, B, q0, Vq = self.V, self.S, self.D, self.B, self.q0, self.Vq
+        V, S, D, B, q0, Vq, N = self.V, self.S, self.D, self.B, self.q0, self.Vq, self.N
+        NVq = N * Vq                   # conditional rows of the UNet batch (q0 = 0, Vq = V when N > 1)
         ctx.B, ctx.D = B, D
         ctx.begin_step()           # eager warm-up and graph capture walk the same rotating buffers
         st = hip.stream
@@ -135,14 +157,14 @@ class StepEngine:
         m.view_attn.run(ctx, self.x, self.depth_noise, self.steps, self.iter, self.cams, self.in_cam,
                         self.input_latents, c, self.vol, V, S, D, q0=q0, Vq=Vq, vol_planes=self.vol_planes,
                         vol_planes_col=self.vol_col, depth_src=None if self.depth_mode == 0 else dsrc,
-                        depth_steps=None if self.depth_mode == 0 else dsteps)
+                        depth_steps=None if self.depth_mode == 0 else dsteps, scenes=N)
         # cc_projection (:322)
         p = m.cc_projection
-        c1 = ctx.ws.get("vf.cc1", (Vq, 768))
-        c2 = ctx.ws.get("vf.cc2", (Vq, 768))
-        ctx.gemv_rows(p[0].weight, p[0].bias, self.clip_v_embed[q0:q0 + Vq], c1, act_out=hip.ACT_SILU)
+        c1 = ctx.ws.get("vf.cc1", (NVq, 768))
+        c2 = ctx.ws.get("vf.cc2", (NVq, 768))
+        ctx.gemv_rows(p[0].weight, p[0].bias, self.clip_v_embed[q0:q0 + NVq], c1, act_out=hip.ACT_SILU)
         ctx.gemv_rows(p[2].weight, p[2].bias, c1, c2, act_out=hip.ACT_SILU)
-        ctx.gemv_rows(p[4].weight, p[4].bias, c2, self.context[:Vq])
+        ctx.gemv_rows(p[4].weight, p[4].bias, c2, self.context[:NVq])
         if self.drop_masks is not None:        # UNetWrapper.forward(is_train=True) condition dropout (eager only, never captured)
             clip_m, vol_m, cat_m = self.drop_masks
             self.context[:Vq] *= clip_m[:, None]
@@ -151,9 +173,9 @@ class StepEngine:
             vp[:Vq, :, 2 * self.vol_col:] *= vol_m.to(torch.int16)[:, None, None]        # x * {0, 1} keeps / zeroes the planes
         ctx.context = self.context
         # UNet on the CFG batch (unet.py:167-196)
-        xq, x0q, epsq = self.x[q0:q0 + Vq], self.x0[q0:q0 + Vq], self.eps[q0:q0 + Vq]
-        hip.check(L.mvd_unet_input(hip.ptr(xq), hip.ptr(self.input_latents), hip.ptr(self.x_in), Vq, S, 32,
-                                   int(self.cfg), st()))
+        xq, x0q, epsq = self.x[q0:q0 + NVq], self.x0[q0:q0 + NVq], self.eps[q0:q0 + NVq]
+        hip.check(L.mvd_unet_input_scenes(hip.ptr(xq), hip.ptr(self.input_latents), hip.ptr(self.x_in), N, Vq, S, 32,
+                                          int(self.cfg), st()))
         if self.drop_masks is not None:        # x_concat channels 5..9 of the (rows, [32 hi | 32 lo]) input planes
             xin = self.x_in.view(B, S * S, 64)
             cm = self.drop_masks[2].to(torch.int16)[:, None, None]
@@ -166,8 +188,8 @@ class StepEngine:
                                            unet.model_channels, st()))
         y = unet.run(ctx, self.x_in, tsu, S)
         hip.check(L.mvd_cfg_ddim_update(hip.ptr(y), 8, hip.ptr(xq), hip.ptr(x0q), hip.ptr(epsq),
-                                        hip.ptr(self.ddim_noise[:, q0:q0 + Vq]), V * 5 * S * S, hip.ptr(self.steps),
-                                        hip.ptr(self.iter), Vq, S, int(self.cfg), float(cfg_scale), int(do_update), st()))
+                                        hip.ptr(self.ddim_noise[:, q0:q0 + NVq]), N * V * 5 * S * S, hip.ptr(self.steps),
+                                        hip.ptr(self.iter), NVq, S, int(self.cfg), float(cfg_scale), int(do_update), st()))
         if do_update:
             hip.check(L.mvd_advance_iter(hip.ptr(self.iter), st()))
 
@@ -370,7 +392,14 @@ class ViewFusion(nn.Module):
             self._packed_sig = None
         return r
 
-    def engine(self, V, S, D, cfg, q0=0, Vq=None):
+    def engine(self, V, S, D, cfg, q0=0, Vq=None, scenes=1):
+        """The StepEngine of one (V, S, D, cfg, view range, scenes) signature (created on first use, then reused).  scenes = N objects
+        denoised together in every step (scene-major buffers, see StepEngine); view-parallel sharding (q0 / Vq) is single-scene only.
+        Engines are kept until invalidate_packed(): each distinct N holds its own workspace, graphs and tuned GEMM shapes."""
+        if int(scenes) < 1:
+            raise ValueError(f"engine(scenes={scenes}): at least one scene")
+        if int(scenes) > 1 and (q0 != 0 or (Vq is not None and Vq != V)):
+            raise ValueError(f"engine(V={V}, q0={q0}, Vq={Vq}, scenes={scenes}): view-parallel sharding is single-scene only")
         sig = hip.params_signature(self)
         if sig != self._packed_sig:      # an in-place update (optimizer step, fill_) since the weights were packed; load_state_dict /
             if self._packed_sig is not None:      # .cuda() invalidate fully themselves (the device may have changed)
@@ -381,14 +410,14 @@ class ViewFusion(nn.Module):
             hip.register_param_maxima(self.parameters())      # one reduction + one host read instead of one per packed weight
         if Vq is not None and Vq <= 0:
             raise ValueError(f"engine(V={V}, q0={q0}, Vq={Vq}): a rank must own at least one query view")
-        key = (V, S, D, bool(cfg), q0, Vq)
+        key = (V, S, D, bool(cfg), q0, Vq) if int(scenes) == 1 else (V, S, D, bool(cfg), q0, Vq, int(scenes))
         e = self._engines.get(key)
         if e is None:
             dev = self._device.device
             if dev.type != "cuda":
                 raise RuntimeError("mvdfusion_amd.ViewFusion runs on the GPU only (model.cuda() first); "
                                    "there is no CPU path in the product")
-            e = StepEngine(self, V, S, D, cfg, dev, self.precision, q0=q0, Vq=Vq, policy=self.precision_policy)
+            e = StepEngine(self, V, S, D, cfg, dev, self.precision, q0=q0, Vq=Vq, policy=self.precision_policy, scenes=int(scenes))
             self._engines[key] = e
         return e
 
@@ -508,6 +537,22 @@ class ViewFusion(nn.Module):
             x_sample, intermediates = res
             return x_sample, batch_latents, input_latents, batch_cameras, intermediates
         return res
+
+    def sample_scenes(self, batches, trainer_config, cfg_scale, return_input=False, depth=False, verbose=True):
+        """``sample`` for several objects at once: every DDIM step denoises all of them in one batched step (DDIMSampler.sample_scenes;
+        the scenes share V, S, cfg_scale and the schedule).  Returns a list with what ``sample`` returns for each batch, in order."""
+        prepared = [self.prepare_batch(b, trainer_config) for b in batches]
+        conds = [(bc, il, ic, ce) for _, bc, il, ic, ce in prepared]
+        res = self.ddim.sample_scenes(conds, unconditional_scale=cfg_scale, depth=depth, return_intermediates=return_input,
+                                      verbose=verbose)
+        if not return_input:
+            return [res[n] for n in range(len(batches))]
+        x, inter = res
+        out = []
+        for n, (batch_latents, batch_cameras, input_latents, _, _) in enumerate(prepared):
+            its = [{"t": it["t"], "xt": it["xt"][n], "x0": it["x0"][n]} for it in inter]
+            out.append((x[n], batch_latents, input_latents, batch_cameras, its))
+        return out
 
     @torch.no_grad()
     def p_losses(self, batch, trainer_config, noise_source=None, _aux=None):
