@@ -280,6 +280,11 @@ int mvd_softmax_rows(const float* x, void* y_sp, int rows, int cols, int ldx, fl
  * (adaLN "modulate", view_attn_efficient2.py:15-16,51,53,65-66); attention.py:211-213, mvdfusion/attention.py:35-37. */
 int mvd_layernorm(const float* x, void* y_sp, float* y_f32, const float* w, const float* b, int rows, int C, float eps,
                   int w_plus_one, mvd_stream_t stream); /* y_sp: split planes (rows, C), C % 32 == 0, and / or y_f32: fp32 (rows, C) */
+/* mvd_layernorm with one modulation per row group (a scene of a multi-scene training step): rows [g*rows_per_group, (g+1)*rows_per_group)
+ * use w + g*ldw / b + g*ldw (w_plus_one as above).  rows_per_group must divide rows; ldw >= 0, a multiple of 4 (0: all groups share
+ * w / b).  mvd_layernorm is rows_per_group = rows. */
+int mvd_layernorm_groups(const float* x, void* y_sp, float* y_f32, const float* w, const float* b, int ldw, int rows, int rows_per_group,
+                         int C, float eps, int w_plus_one, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Self-attention over the tokens of one view (CrossAttention with context=None, attention.py:170-193).
@@ -346,6 +351,10 @@ int mvd_fill_zero(float* p, size_t n, mvd_stream_t stream);
  * freqs (dim/2) = exp(-ln(1e4) * i / (dim/2)) is computed once on the host exactly as the reference does. */
 int mvd_timestep_embedding(const float* steps, const int* iter, const float* freqs, float* out, int dim,
                            mvd_stream_t stream);
+/* nscene sinusoid rows: out row n (dim floats) from step row *iter + n*steps_scene_stride (each scene of a training step has its own
+ * timestep).  steps must hold that many rows; steps_scene_stride is 0 when nscene = 1 (then = mvd_timestep_embedding). */
+int mvd_timestep_embedding_scenes(const float* steps, const int* iter, const float* freqs, float* out, int dim, int nscene,
+                                  int steps_scene_stride, mvd_stream_t stream);
 int mvd_advance_iter(int* iter, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -374,6 +383,13 @@ int mvd_gridattn_tokens_scenes(const float* x, const float* depth_noise, const f
                                const float* feat, const float* in_feat, const float* cams, const float* in_cam, void* tokens_sp,
                                int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
                                mvd_stream_t stream);
+/* mvd_gridattn_tokens_scenes with a timestep per scene: scene n reads step row *iter + n*steps_scene_stride (its x0-depth divisor and
+ * depth std); the depth noise stays indexed by *iter.  The step table must hold those rows.  steps_scene_stride = 0 is
+ * mvd_gridattn_tokens_scenes (bit-identical); nscene = 1 requires 0. */
+int mvd_gridattn_tokens_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                                 const float* feat, const float* in_feat, const float* cams, const float* in_cam, void* tokens_sp,
+                                 int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
+                                 int steps_scene_stride, mvd_stream_t stream);
 /* Fused G1-G4 (:269-397): tokens are generated in registers and pushed through pre_layer_b, the 3 DiTBlocks over the V views,
  * and the weight_layer softmax pooling in ONE launch; output = the pooled (Vq*S*S*D, 256) rows as split planes (the final
  * Linear 256->768 is a plain mvd_gemm).  1 <= V <= 16: a wavefront owns 16 token rows = 16 / Vp points, Vp = the next power of
@@ -397,11 +413,19 @@ int mvd_gridattn_fused(const float* x, const float* depth_noise, const float* st
 /* mvd_gridattn_fused for nscene independent scenes of V views each in one launch (nscene >= 1; mvd_gridattn_fused is nscene = 1),
  * same per-view / per-scene layouts as mvd_gridattn_tokens_scenes; pooled rows scene-major (scene*Vq*S*S*D + the single-scene row).
  * Vq*S*S*D*Vp (one scene's padded token rows) must be a multiple of 64: a workgroup never straddles two scenes.  The weight stream
- * and vecs are shared by all scenes (one timestep). */
+ * and vecs are shared by all scenes (one timestep; mvd_gridattn_fused_scenes_t: one per scene). */
 int mvd_gridattn_fused_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
                               const float* feat, const float* in_feat, const float* cams, const float* in_cam, const void* wstream,
                               const float* vecs, void* pooled_sp, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale,
                               float depth_shift, int prec, mvd_stream_t stream);
+/* mvd_gridattn_fused_scenes with a timestep per scene: scene n reads step row *iter + n*steps_scene_stride and the whole vector table at
+ * vecs + n*vecs_scene_stride floats (its adaLN modulation; the biases / scales are repeated per scene), e.g. vecs_scene_stride =
+ * mvd_gridattn_fused_vec_floats() for an (nscene, vec_floats) table.  The depth noise stays indexed by *iter.  Both strides 0 is
+ * mvd_gridattn_fused_scenes (bit-identical); nscene = 1 requires both 0; vecs_scene_stride % 4 == 0 (16-byte alignment). */
+int mvd_gridattn_fused_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                                const float* feat, const float* in_feat, const float* cams, const float* in_cam, const void* wstream,
+                                const float* vecs, void* pooled_sp, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale,
+                                float depth_shift, int prec, int steps_scene_stride, int vecs_scene_stride, mvd_stream_t stream);
 /* timm Attention core over the V reference views (:52): qkv (Nseq*V, 3*heads*dhead) -> out (Nseq*V, heads*dhead) */
 int mvd_view_mha(const float* qkv, void* out_sp, int Nseq, int V, int heads, int dhead,
                  mvd_stream_t stream); /* output: split planes */
@@ -470,6 +494,16 @@ int mvd_groupnorm_backward(const float* x, const float* dy, const float* gamma, 
  * dw = mvd_col_sum(dyxhat), db = mvd_col_sum(dy).  dyxhat may be null. */
 int mvd_layernorm_backward(const float* x, const float* dy, const float* w, int rows, int C, float eps, float* dx, float* dyxhat,
                            mvd_stream_t stream);
+/* Column sums per row group: out[g][c] = sum over rows [g*rows_per_group, (g+1)*rows_per_group) of x[r][c] (ngroups x cols), same
+ * fixed-order fp64 reduction as mvd_col_sum per group.  ws: mvd_col_sum_groups_workspace_doubles(ngroups, rows_per_group, cols). */
+size_t mvd_col_sum_groups_workspace_doubles(int ngroups, int rows_per_group, int cols);
+int mvd_col_sum_groups(const float* x, int ngroups, int rows_per_group, int cols, int ldx, float* out, double* ws, size_t ws_doubles,
+                       mvd_stream_t stream);
+/* mvd_layernorm_backward with one weight per row group (the backward of mvd_layernorm_groups): rows of group g use w + g*ldw.  Writes dx,
+ * dyxhat (rows, C; required when dw is given) and, when non-null, dw / db (ngroups, C) = the column sums of dyxhat / dy per group (the
+ * per-scene dscale / dshift of adaLN).  ws: mvd_col_sum_groups_workspace_doubles(rows / rows_per_group, rows_per_group, C) doubles. */
+int mvd_layernorm_backward_groups(const float* x, const float* dy, const float* w, int ldw, int rows, int rows_per_group, int C, float eps,
+                                  float* dx, float* dyxhat, float* dw, float* db, double* ws, size_t ws_doubles, mvd_stream_t stream);
 /* Activations of the training step (viewfusion_zero_depth_rgb.py:362-397 -> view_attn_efficient2.py:42-67 DiTBlock / Mlp, pre_layer_b):
  * mvd_act_planes: y = act(x), act = MVD_ACT_GELU (exact erf) or MVD_ACT_SILU, of the fp32 matrix x (rows, cols; leading dim ldx) as split
  * planes (sp, ldp % 32 == 0, padded columns zero; NULL = none) and / or fp32 (y, leading dim ldy; NULL = none) in one pass.
@@ -495,6 +529,13 @@ int mvd_gridattn_tokens_backward(const float* x, const float* depth_noise, const
                                  const float* cams, const float* in_cam, const float* dtok, int ldt, long long* dfeat_acc,
                                  long long* din_feat_acc, float scale, int V, int q0, int Vq, int S, int D, float depth_scale,
                                  float depth_shift, mvd_stream_t stream);
+/* mvd_gridattn_tokens_backward for nscene scenes (the layouts of mvd_gridattn_tokens_scenes_t, per-scene step rows included):
+ * dtok rows scene-major, dfeat_acc (nscene*V,S,S,256), din_feat_acc (nscene,S,S,256).  Same 64-bit fixed-point scatter: bit-identical to
+ * one mvd_gridattn_tokens_backward per scene at that scene's step row.  nscene = 1, steps_scene_stride = 0 is mvd_gridattn_tokens_backward. */
+int mvd_gridattn_tokens_backward_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                                        const float* cams, const float* in_cam, const float* dtok, int ldt, long long* dfeat_acc,
+                                        long long* din_feat_acc, float scale, int nscene, int V, int q0, int Vq, int S, int D,
+                                        float depth_scale, float depth_shift, int steps_scene_stride, mvd_stream_t stream);
 
 #ifdef __cplusplus
 }

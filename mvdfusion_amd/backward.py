@@ -61,6 +61,20 @@ def col_sum(x, rows, cols):
     return out
 
 
+def col_sum_groups(x, ngroups, cols=None):
+    """Column sums of each of ngroups equal consecutive row blocks of x (rows, cols): (ngroups, cols) (mvd_col_sum_groups)."""
+    x = x if x.is_contiguous() else x.contiguous()
+    cols = x.shape[-1] if cols is None else cols
+    rows = x.numel() // x.shape[-1]
+    assert rows % ngroups == 0, (rows, ngroups)
+    out = torch.empty(ngroups, cols, dtype=torch.float32, device=x.device)
+    L = hip.lib()
+    n = L.mvd_col_sum_groups_workspace_doubles(ngroups, rows // ngroups, cols)
+    ws = torch.empty(n, dtype=torch.float64, device=x.device)
+    hip.check(L.mvd_col_sum_groups(hip.ptr(x), ngroups, rows // ngroups, cols, x.shape[-1], hip.ptr(out), hip.ptr(ws), n, hip.stream()))
+    return out
+
+
 def act_planes(x, act, planes=True, f32=False):
     """act(x) of the fp32 matrix x (rows, cols) in one pass: (split planes (rows, 2 * ceil32(cols)) | None, fp32 (rows, cols) | None)
     (mvd_act_planes; act = hip.ACT_GELU / hip.ACT_SILU)."""
@@ -231,6 +245,23 @@ def layernorm_backward(x, dy, weight, eps):
     return dx, col_sum(t, rows, C), col_sum(dy, rows, C)
 
 
+def layernorm_backward_groups(x, dy, weight, eps, ngroups):
+    """layernorm_backward with one weight row per group of rows (weight (ngroups, C) with row stride ldw): (dx, dweight (ngroups, C),
+    dbias (ngroups, C)) -- the per-scene dscale / dshift of adaLN (mvd_layernorm_backward_groups)."""
+    rows, C = x.shape
+    assert rows % ngroups == 0 and weight.shape == (ngroups, C) and weight.stride(-1) == 1, (rows, ngroups, tuple(weight.shape))
+    dx, t = torch.empty_like(x), torch.empty_like(x)
+    dy = dy.contiguous()
+    dw = torch.empty(ngroups, C, dtype=torch.float32, device=x.device)
+    db = torch.empty_like(dw)
+    L = hip.lib()
+    n = L.mvd_col_sum_groups_workspace_doubles(ngroups, rows // ngroups, C)
+    ws = torch.empty(n, dtype=torch.float64, device=x.device)
+    hip.check(L.mvd_layernorm_backward_groups(hip.ptr(x), hip.ptr(dy), hip.ptr(weight), weight.stride(0), rows, rows // ngroups, C,
+                                              float(eps), hip.ptr(dx), hip.ptr(t), hip.ptr(dw), hip.ptr(db), hip.ptr(ws), n, hip.stream()))
+    return dx, dw, db
+
+
 def geglu_backward(h, dy):
     """Backward of GEGLU y = a * gelu(g), [a | g] = h (rows, 2*half): dh (rows, 2*half)."""
     rows, half = dy.shape
@@ -244,10 +275,17 @@ def attention_backward(q, k, v, dout, B, heads, L, dhead):
     """Backward of softmax(Q K^T / sqrt(d)) V per (batch, head); all tensors token-major fp32 (B*L, heads*dhead).
     Returns (dq, dk, dv)."""
     dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-    n = B * heads * L * 3
+    dout = dout.contiguous()
+    # the kernels take at most 65535 sequences per launch (grid limit): more -- GridAttn's attention over V of a multi-scene step has
+    # N*V*S*S*D sequences -- run as consecutive chunks of independent sequences (the same per-sequence arithmetic)
+    chunk = 65535 if B > 65535 else B
+    n = chunk * heads * L * 3
     stats = torch.empty(n, dtype=torch.float32, device=q.device)
-    hip.check(hip.lib().mvd_attention_backward(hip.ptr(q), hip.ptr(k), hip.ptr(v), hip.ptr(dout.contiguous()), B, heads, L, dhead,
-                                               hip.ptr(dq), hip.ptr(dk), hip.ptr(dv), hip.ptr(stats), n, hip.stream()))
+    for b0 in range(0, B, chunk):
+        b = min(chunk, B - b0)
+        r = slice(b0 * L, (b0 + b) * L)
+        hip.check(hip.lib().mvd_attention_backward(hip.ptr(q[r]), hip.ptr(k[r]), hip.ptr(v[r]), hip.ptr(dout[r]), b, heads, L, dhead,
+                                                   hip.ptr(dq[r]), hip.ptr(dk[r]), hip.ptr(dv[r]), hip.ptr(stats), n, hip.stream()))
     return dq, dk, dv
 
 

@@ -96,7 +96,7 @@ def _c(t):
 
 def resblock_backward(tape, rb, x, emb, dout, B, H, W):
     """ResBlock (openaimodel.py:255-275; no scale-shift norm, dropout 0).  x (M, Cin) fp32 block input, emb (1, ted) the shared
-    time embedding, dout (M, Cout).  Returns (dx, {name: grad}, demb (1, ted))."""
+    time embedding -- or (R, ted): one per scene, each for M / R scene-major rows --, dout (M, Cout).  Returns (dx, {name: grad}, demb (R, ted))."""
     gn1, conv1 = rb.in_layers[0], rb.in_layers[2]
     gn2, conv2 = rb.out_layers[0], rb.out_layers[3]
     lin_e = rb.emb_layers[1]
@@ -105,8 +105,13 @@ def resblock_backward(tape, rb, x, emb, dout, B, H, W):
     # ---- forward (unfused)
     a1 = tape.groupnorm(x, gn1, B, HW, True)
     se = torch.nn.functional.silu(emb)                                     # (1, ted)   host glue
-    e = se @ lin_e.weight.t() + lin_e.bias                                 # (1, Co)
-    h1 = tape.conv3x3(a1, conv1.weight, conv1.bias + e[0], B, H, W)
+    e = se @ lin_e.weight.t() + lin_e.bias                                 # (R, Co)
+    R = emb.shape[0]
+    if R == 1:
+        h1 = tape.conv3x3(a1, conv1.weight, conv1.bias + e[0], B, H, W)
+    else:                                                                   # a time-embedding row per scene: added to its rows
+        h1 = tape.conv3x3(a1, conv1.weight, conv1.bias, B, H, W)
+        h1 = (h1.reshape(R, -1, Co) + e[:, None, :]).reshape(-1, Co)
     a2 = tape.groupnorm(h1, gn2, B, HW, True)
     has_skip = not isinstance(rb.skip_connection, torch.nn.Identity)
     xp = tape.planes(x) if has_skip else None
@@ -118,10 +123,16 @@ def resblock_backward(tape, rb, x, emb, dout, B, H, W):
     if db1 is None:                                                         # conv1 frozen: the column sum is still the gradient of the
         db1 = bw.col_sum(_c(dh1), B * HW, Co)                               # time-embedding vector (always needed)
     g["in_layers.2.bias"] = db1
-    # the time-embedding vector is added per channel to every row: its gradient is the same column sum
-    g["emb_layers.1.bias"] = db1.clone()
-    g["emb_layers.1.weight"] = torch.outer(db1, se[0])
-    demb = (db1[None, :] @ lin_e.weight) * (torch.sigmoid(emb) * (1 + emb * (1 - torch.sigmoid(emb))))
+    # the time-embedding vector is added per channel to every row: its gradient is the same column sum (per scene: over the scene's rows)
+    if R == 1:
+        g["emb_layers.1.bias"] = db1.clone()
+        g["emb_layers.1.weight"] = torch.outer(db1, se[0])
+        demb = (db1[None, :] @ lin_e.weight) * (torch.sigmoid(emb) * (1 + emb * (1 - torch.sigmoid(emb))))
+    else:
+        dbs = bw.col_sum_groups(_c(dh1), R)                                 # (R, Co)
+        g["emb_layers.1.bias"] = dbs.sum(0)
+        g["emb_layers.1.weight"] = dbs.t() @ se
+        demb = (dbs @ lin_e.weight) * (torch.sigmoid(emb) * (1 + emb * (1 - torch.sigmoid(emb))))
     dx, g["in_layers.0.weight"], g["in_layers.0.bias"] = bw.groupnorm_backward(_c(x), _c(da1), gn1.weight, gn1.bias, B, HW, Ci, gn1.eps, True)
     if has_skip:
         sk = rb.skip_connection

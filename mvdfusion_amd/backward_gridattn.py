@@ -31,72 +31,121 @@ def _silu_grad(z):
     return s * (1 + z * (1 - s))
 
 
-def _dit_block_backward(tape, blk, h, c, dh2, T, V):
-    """One DiTBlock (view_attn_efficient2.py:42-67).  h (T, C) block input, c (1, C) conditioning, dh2 gradient at the block output.
-    Returns (dh, {name: grad}, dc (1, C))."""
-    C, H = blk.hidden_size, blk.num_heads
-    dh_ = C // H
+def _modulation(blk, c):
+    """(SiLU(c), the six adaLN vectors): (C,) each for one conditioning row, (R, C) views of the (R, 6C) modulation for one row per scene."""
+    C = blk.hidden_size
     lin = blk.adaLN_modulation[1]
     sc_ = F.silu(c)
-    mod = sc_ @ lin.weight.t() + lin.bias                                    # (1, 6C)   host glue
-    sh1, s1, g1, sh2, s2, g2 = (mod[0, i * C:(i + 1) * C].contiguous() for i in range(6))
+    mod = sc_ @ lin.weight.t() + lin.bias                                    # (R, 6C)   host glue
+    if c.shape[0] == 1:
+        return sc_, [mod[0, i * C:(i + 1) * C].contiguous() for i in range(6)]
+    return sc_, [mod[:, i * C:(i + 1) * C] for i in range(6)]
+
+
+def _ln_modulate(h, out, scale, shift, T, C):
+    """LayerNorm(h) * (1 + scale) + shift; scale / shift (R, C) apply to R equal scene-major row groups (mvd_layernorm_groups)."""
+    if scale.dim() == 1:
+        return hip.layernorm(h, out, scale, shift, T, C, eps=1e-6, w_plus_one=True)
+    return hip.layernorm_groups(h, out, scale, shift, T, C, T // scale.shape[0], eps=1e-6, w_plus_one=True)
+
+
+def _gate(g, x):
+    """g * x with the gate g (C,) shared by every row, or (R, C): one row per scene over R equal scene-major row groups of x (rows, C)."""
+    if g.dim() == 1:
+        return g * x
+    R, C = g.shape
+    return (x.reshape(R, -1, C) * g[:, None, :]).reshape(x.shape)
+
+
+def _col_sums(x, R, T, C):
+    """Column sums of x (T, C): (C,) for one conditioning row, (R, C) per scene row group."""
+    if R == 1:
+        return bw.col_sum(x.contiguous(), T, C)
+    return bw.col_sum_groups(x.contiguous(), R)
+
+
+def _dit_block_backward(tape, blk, h, c, dh2, T, V):
+    """One DiTBlock (view_attn_efficient2.py:42-67).  h (T, C) block input, c (1, C) conditioning -- or (R, C): one row per scene, each
+    conditioning T / R scene-major rows --, dh2 gradient at the block output.  Returns (dh, {name: grad}, dc (R, C))."""
+    C, H = blk.hidden_size, blk.num_heads
+    R = c.shape[0]
+    dh_ = C // H
+    lin = blk.adaLN_modulation[1]
+    sc_, (sh1, s1, g1, sh2, s2, g2) = _modulation(blk, c)
     dev = h.device
     # ---- forward (unfused)
     m1 = hip.planes_like(T, C, dev)
-    hip.layernorm(h, m1, s1, sh1, T, C, eps=1e-6, w_plus_one=True)
+    _ln_modulate(h, m1, s1, sh1, T, C)
     qkv = tape.linear(m1, blk.attn.qkv.weight, blk.attn.qkv.bias)           # (T, 3C): [q | k | v], each [heads][dhead]
     att = hip.planes_like(T, C, dev)
     hip.check(hip.lib().mvd_view_mha(hip.ptr(qkv), hip.ptr(att), T // V, V, H, dh_, hip.stream()))
     a_out = tape.linear(att, blk.attn.proj.weight, blk.attn.proj.bias)
-    h1 = h + g1 * a_out
+    h1 = h + _gate(g1, a_out)
     m2 = hip.planes_like(T, C, dev)
-    hip.layernorm(h1, m2, s2, sh2, T, C, eps=1e-6, w_plus_one=True)
+    _ln_modulate(h1, m2, s2, sh2, T, C)
     f1 = tape.linear(m2, blk.mlp.fc1.weight, blk.mlp.fc1.bias)              # pre-activation (T, hidden)
     gel, _ = bw.act_planes(f1, hip.ACT_GELU)                               # GELU + operand split in one pass (mvd_act_planes)
     f2 = tape.linear(gel, blk.mlp.fc2.weight, blk.mlp.fc2.bias)
     # ---- backward
     g = {}
-    dg2 = bw.col_sum((dh2 * f2).contiguous(), T, C)
-    dgel, g["mlp.fc2.weight"], g["mlp.fc2.bias"] = tape.linear_bwd(gel, blk.mlp.fc2.weight, dh2 * g2)
+    dg2 = _col_sums(dh2 * f2, R, T, C)
+    dgel, g["mlp.fc2.weight"], g["mlp.fc2.bias"] = tape.linear_bwd(gel, blk.mlp.fc2.weight, _gate(g2, dh2))
     dm2, g["mlp.fc1.weight"], g["mlp.fc1.bias"] = tape.linear_bwd(m2, blk.mlp.fc1.weight, bw.act_backward(dgel, f1, hip.ACT_GELU))
-    dx, ds2, dsh2 = bw.layernorm_backward(h1.contiguous(), dm2.contiguous(), (1.0 + s2).contiguous(), 1e-6)
+    if R == 1:
+        dx, ds2, dsh2 = bw.layernorm_backward(h1.contiguous(), dm2.contiguous(), (1.0 + s2).contiguous(), 1e-6)
+    else:
+        dx, ds2, dsh2 = bw.layernorm_backward_groups(h1.contiguous(), dm2.contiguous(), (1.0 + s2).contiguous(), 1e-6, R)
     dh1 = dh2 + dx
-    dg1 = bw.col_sum((dh1 * a_out).contiguous(), T, C)
-    datt, g["attn.proj.weight"], g["attn.proj.bias"] = tape.linear_bwd(att, blk.attn.proj.weight, dh1 * g1)
+    dg1 = _col_sums(dh1 * a_out, R, T, C)
+    datt, g["attn.proj.weight"], g["attn.proj.bias"] = tape.linear_bwd(att, blk.attn.proj.weight, _gate(g1, dh1))
     q, k, v = (qkv[:, i * C:(i + 1) * C].contiguous() for i in range(3))
     dq, dk, dv = bw.attention_backward(q, k, v, datt.contiguous(), T // V, H, V, dh_)
     dm1, g["attn.qkv.weight"], g["attn.qkv.bias"] = tape.linear_bwd(m1, blk.attn.qkv.weight, torch.cat([dq, dk, dv], dim=1))
-    dx, ds1, dsh1 = bw.layernorm_backward(h.contiguous(), dm1.contiguous(), (1.0 + s1).contiguous(), 1e-6)
+    if R == 1:
+        dx, ds1, dsh1 = bw.layernorm_backward(h.contiguous(), dm1.contiguous(), (1.0 + s1).contiguous(), 1e-6)
+    else:
+        dx, ds1, dsh1 = bw.layernorm_backward_groups(h.contiguous(), dm1.contiguous(), (1.0 + s1).contiguous(), 1e-6, R)
     dh = dh1 + dx
-    dmod = torch.cat([dsh1, ds1, dg1, dsh2, ds2, dg2])[None, :]               # (1, 6C)
+    if R == 1:
+        dmod = torch.cat([dsh1, ds1, dg1, dsh2, ds2, dg2])[None, :]           # (1, 6C)
+        g["adaLN_modulation.1.bias"] = dmod[0].clone()
+    else:
+        dmod = torch.cat([dsh1, ds1, dg1, dsh2, ds2, dg2], dim=1)            # (R, 6C): one row per scene
+        g["adaLN_modulation.1.bias"] = dmod.sum(0)
     g["adaLN_modulation.1.weight"] = dmod.t() @ sc_
-    g["adaLN_modulation.1.bias"] = dmod[0].clone()
     dc = (dmod @ lin.weight) * _silu_grad(c)
     return dh, g, dc
 
 
 def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     """ga: GridAttn; eng: the StepEngine whose buffers hold this step's inputs (x, depth noise, step table, cameras, input latents);
-    c (1, 256) conditioning; dvol (V*S*S*D, 768) gradient of the frustum.  Returns ({view_attn-relative name: grad}, dc (1, 256))."""
+    c (1, 256) conditioning; dvol (V*S*S*D, 768) gradient of the frustum.  Returns ({view_attn-relative name: grad}, dc (1, 256)).
+    An engine of N scenes: its N*V views scene-major, dvol (N*V*S*S*D, 768); with per-scene timesteps (eng.steps_scene_stride) c and dc
+    are (N, 256), one row per scene."""
     L = hip.lib()
     dev = dvol.device
     C = ga.hidden_size
-    nseq = V * S * S * D
+    N, sst = eng.N, eng.steps_scene_stride
+    nseq = N * V * S * S * D
     T = nseq * V
     agg = ga.aggregation_transformer
     # ---- forward (unfused chain, view_attn_efficient2.py GridAttn.run)
     z = ga.z_embedder[0]
-    feat = torch.empty(V, S, S, 256, dtype=torch.float32, device=dev)
-    in_feat = torch.empty(1, S, S, 256, dtype=torch.float32, device=dev)
-    hip.check(L.mvd_zembed(hip.ptr(eng.x), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(feat), V, S, hip.stream()))
-    hip.check(L.mvd_zembed(hip.ptr(eng.input_latents), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(in_feat), 1, S, hip.stream()))
+    feat = torch.empty(N * V, S, S, 256, dtype=torch.float32, device=dev)
+    in_feat = torch.empty(N, S, S, 256, dtype=torch.float32, device=dev)
+    hip.check(L.mvd_zembed(hip.ptr(eng.x), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(feat), N * V, S, hip.stream()))
+    hip.check(L.mvd_zembed(hip.ptr(eng.input_latents), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(in_feat), N, S, hip.stream()))
     half = 1.0 / float(S)
     grid_lin = torch.linspace(1.0 - half, -1.0 + half, S, dtype=torch.float32).to(dev)
     tokens = hip.planes_like(T, hip.TOKEN_LD, dev)
     dsrc, dsteps = eng.depth_geo()          # (the depth source the forward used: x itself, or an overwrite_attn_depth map)
     geo = (hip.ptr(dsrc), hip.ptr(eng.depth_noise), hip.ptr(dsteps), hip.ptr(eng.iter), hip.ptr(grid_lin))
-    hip.check(L.mvd_gridattn_tokens(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens), V, 0, V,
-                                    S, D, float(ga.depth_scale), float(ga.depth_shift), hip.stream()))
+    if N == 1:
+        hip.check(L.mvd_gridattn_tokens(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens), V, 0,
+                                        V, S, D, float(ga.depth_scale), float(ga.depth_shift), hip.stream()))
+    else:
+        hip.check(L.mvd_gridattn_tokens_scenes_t(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens),
+                                                 N, V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift), sst, hip.stream()))
     pre = ga.pre_layer_b[0]
     z0 = tape.linear(tokens, pre.weight, pre.bias)                             # (T, 256) pre-activation
     hs = [bw.act_planes(z0, hip.ACT_GELU, planes=False, f32=True)[1]]
@@ -131,14 +180,19 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     ldt = base.stride(0)
     mx = float(dtok[:, :512].abs().max())
     scale = 2.0 ** (40 - math.floor(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 1.0
-    dfeat_acc = torch.zeros(V, S, S, 256, dtype=torch.int64, device=dev)
-    din_acc = torch.zeros(1, S, S, 256, dtype=torch.int64, device=dev)
-    hip.check(L.mvd_gridattn_tokens_backward(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
-                                             hip.ptr(din_acc), float(scale), V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift),
-                                             hip.stream()))
+    dfeat_acc = torch.zeros(N * V, S, S, 256, dtype=torch.int64, device=dev)
+    din_acc = torch.zeros(N, S, S, 256, dtype=torch.int64, device=dev)
+    if N == 1:
+        hip.check(L.mvd_gridattn_tokens_backward(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
+                                                 hip.ptr(din_acc), float(scale), V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift),
+                                                 hip.stream()))
+    else:
+        hip.check(L.mvd_gridattn_tokens_backward_scenes(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
+                                                        hip.ptr(din_acc), float(scale), N, V, 0, V, S, D, float(ga.depth_scale),
+                                                        float(ga.depth_shift), sst, hip.stream()))
     dW = torch.zeros_like(z.weight)
     db = torch.zeros_like(z.bias)
-    for lat, acc, n in ((eng.x, dfeat_acc, V), (eng.input_latents, din_acc, 1)):
+    for lat, acc, n in ((eng.x, dfeat_acc, N * V), (eng.input_latents, din_acc, N)):
         xp = lat.reshape(n, 5, S * S).permute(0, 2, 1).reshape(n * S * S, 5)
         zz = xp @ z.weight.t() + z.bias
         dz = (acc.double() / scale).float().reshape(n * S * S, 256) * _gelu_grad(zz)
@@ -149,22 +203,26 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
 
 
 def _dit_forward(tape, blk, h, c, T, V):
-    """Unfused DiTBlock forward returning the block output (same algebra as _dit_block_backward's forward half)."""
+    """Unfused DiTBlock forward returning the block output (same algebra as _dit_block_backward's forward half); c (1, C) or (R, C) per
+    scene."""
     C, H = blk.hidden_size, blk.num_heads
-    lin = blk.adaLN_modulation[1]
-    mod = F.silu(c) @ lin.weight.t() + lin.bias
-    sh1, s1, g1, sh2, s2, g2 = (mod[0, i * C:(i + 1) * C].contiguous() for i in range(6))
+    _, (sh1, s1, g1, sh2, s2, g2) = _modulation(blk, c)
     dev = h.device
     m1 = hip.planes_like(T, C, dev)
-    hip.layernorm(h, m1, s1, sh1, T, C, eps=1e-6, w_plus_one=True)
+    _ln_modulate(h, m1, s1, sh1, T, C)
     qkv = tape.linear(m1, blk.attn.qkv.weight, blk.attn.qkv.bias)
     att = hip.planes_like(T, C, dev)
     hip.check(hip.lib().mvd_view_mha(hip.ptr(qkv), hip.ptr(att), T // V, V, H, C // H, hip.stream()))
-    h1 = tape.linear(att, blk.attn.proj.weight, blk.attn.proj.bias, res=h, colscale=g1)        # h + g1 * proj(att): the GEMM's own epilogue
+    if c.shape[0] == 1:
+        h1 = tape.linear(att, blk.attn.proj.weight, blk.attn.proj.bias, res=h, colscale=g1)    # h + g1 * proj(att): the GEMM's own epilogue
+    else:                                                                                       # (the epilogue's gate is one row: per scene
+        h1 = h + _gate(g1, tape.linear(att, blk.attn.proj.weight, blk.attn.proj.bias))           #  it is elementwise glue)
     m2 = hip.planes_like(T, C, dev)
-    hip.layernorm(h1, m2, s2, sh2, T, C, eps=1e-6, w_plus_one=True)
+    _ln_modulate(h1, m2, s2, sh2, T, C)
     f1 = tape.linear(m2, blk.mlp.fc1.weight, blk.mlp.fc1.bias)
-    return tape.linear(bw.act_planes(f1, hip.ACT_GELU)[0], blk.mlp.fc2.weight, blk.mlp.fc2.bias, res=h1, colscale=g2)
+    if c.shape[0] == 1:
+        return tape.linear(bw.act_planes(f1, hip.ACT_GELU)[0], blk.mlp.fc2.weight, blk.mlp.fc2.bias, res=h1, colscale=g2)
+    return h1 + _gate(g2, tape.linear(bw.act_planes(f1, hip.ACT_GELU)[0], blk.mlp.fc2.weight, blk.mlp.fc2.bias))
 
 
 def time_embed_backward(time_embed, t_sin, dc):
@@ -173,7 +231,8 @@ def time_embed_backward(time_embed, t_sin, dc):
     l1, l2 = time_embed[0], time_embed[2]
     z1 = t_sin @ l1.weight.t() + l1.bias
     e1 = F.silu(z1)
-    g = {"2.weight": dc.t() @ e1, "2.bias": dc[0].clone()}
+    row_sum = (lambda t: t[0].clone()) if dc.shape[0] == 1 else (lambda t: t.sum(0))      # (one row per scene: summed over the scenes)
+    g = {"2.weight": dc.t() @ e1, "2.bias": row_sum(dc)}
     dz1 = (dc @ l2.weight) * _silu_grad(z1)
-    g["0.weight"], g["0.bias"] = dz1.t() @ t_sin, dz1[0].clone()
+    g["0.weight"], g["0.bias"] = dz1.t() @ t_sin, row_sum(dz1)
     return g

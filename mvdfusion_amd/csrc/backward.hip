@@ -89,10 +89,13 @@ __global__ __launch_bounds__(256) void im2col_t_kernel(const u16* __restrict__ x
 // amax != null (round 6, mvd_col_sum_pow2): the same pass also forms max|x| -- block maxima meet in an atomicMax on the bit pattern (non-negative
 // floats order like their bits) -- and the FINAL kernel turns it into the power-of-two gradient scale {s, 1/s} of mvd_pow2_scale and re-zeroes
 // the word: the bias gradient and the operand scale of a layer's dY cost one pass over dY instead of two.
+// Row groups (mvd_col_sum_groups): blockIdx.z = group g sums rows [g*rows, (g+1)*rows) into part + g*gridDim.y*cols (one group: z = 0).
 __global__ __launch_bounds__(256) void col_sum_partial_kernel(const float* __restrict__ x, int rows, int cols, int ldx,
                                                               double* __restrict__ part, unsigned* __restrict__ amax) {
   __shared__ double s[8][32];
   __shared__ unsigned s_m[4];
+  x += (size_t)blockIdx.z * rows * ldx;
+  part += (size_t)blockIdx.z * gridDim.y * cols;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + tx;
   const int per = (rows + gridDim.y - 1) / gridDim.y;
@@ -123,6 +126,8 @@ __global__ __launch_bounds__(256) void col_sum_partial_kernel(const float* __res
 __global__ __launch_bounds__(256) void col_sum_final_kernel(const double* __restrict__ part, int splits, int cols, float* __restrict__ out,
                                                             unsigned* __restrict__ amax, float* __restrict__ out2) {
   const int c = blockIdx.x * 256 + threadIdx.x;
+  part += (size_t)blockIdx.y * splits * cols;      // row group (mvd_col_sum_groups; y = 0 otherwise): out row blockIdx.y
+  out += (size_t)blockIdx.y * cols;
   if (amax != nullptr && c == 0) {          // (every partial block has finished: this is a later launch of the same stream)
     const unsigned bits = __hip_atomic_load(amax, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     float sc = 1.f;
@@ -261,11 +266,14 @@ __global__ __launch_bounds__(256) void gn_bwd_param_kernel(const float* __restri
 // y = xhat * w + b over the last dimension (eps inside the sqrt), one wave per row (C <= 1280):
 //   dx = rstd * (dz - mean(dz) - xhat * mean(dz * xhat)), dz = dy * w;  t = dy * xhat is written out so that dw = column sums of t and
 //   db = column sums of dy come from mvd_col_sum (fixed order).
+// Row groups (mvd_layernorm_backward_groups): row r uses w + (r / rows_per_group) * ldw.
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ w,
-                                                     int rows, int C, float eps, float* __restrict__ dx, float* __restrict__ t) {
+                                                     int rows, int C, float eps, float* __restrict__ dx, float* __restrict__ t, int rows_per_group,
+                                                     int ldw) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
+  if (w) w += (size_t)(row / rows_per_group) * ldw;
   const float* xr = x + (size_t)row * C;
   const float* dr = dy + (size_t)row * C;
   float s = 0.f;
@@ -1013,8 +1021,53 @@ extern "C" int mvd_groupnorm_backward(const float* x, const float* dy, const flo
 extern "C" int mvd_layernorm_backward(const float* x, const float* dy, const float* w, int rows, int C, float eps, float* dx, float* dyxhat,
                                       mvd_stream_t stream) {
   MVD_CHECK_ARG(x && dy && dx && rows > 0 && C > 0, "mvd_layernorm_backward: bad arguments");
-  hipLaunchKernelGGL(ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, dy, w, rows, C, eps, dx, dyxhat);
+  hipLaunchKernelGGL(ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, dy, w, rows, C, eps, dx, dyxhat, rows, 0);
   MVD_CHECK_LAUNCH("mvd_layernorm_backward");
+  return 0;
+}
+
+extern "C" size_t mvd_col_sum_groups_workspace_doubles(int ngroups, int rows_per_group, int cols) {
+  return (size_t)ngroups * mvd_col_sum_workspace_doubles(rows_per_group, cols);
+}
+
+static int col_sum_groups_launch(const float* x, int ngroups, int rows_per_group, int cols, int ldx, float* out, double* ws, size_t ws_doubles,
+                                 hipStream_t stream) {
+  int splits = rows_per_group / 256;
+  if (splits < 1) splits = 1;
+  if (splits > 64) splits = 64;
+  MVD_CHECK_ARG(ws_doubles >= (size_t)ngroups * splits * cols, "mvd_col_sum_groups: workspace too small (%zu < %zu doubles)", ws_doubles,
+                (size_t)ngroups * splits * cols);
+  MVD_CHECK_ARG(ngroups <= 65535, "mvd_col_sum_groups: ngroups=%d (<= 65535)", ngroups);
+  hipLaunchKernelGGL(col_sum_partial_kernel, dim3((cols + 31) / 32, splits, ngroups), dim3(256), 0, stream, x, rows_per_group, cols, ldx, ws,
+                     (unsigned*)nullptr);
+  hipLaunchKernelGGL(col_sum_final_kernel, dim3((cols + 255) / 256, ngroups), dim3(256), 0, stream, ws, splits, cols, out, (unsigned*)nullptr,
+                     (float*)nullptr);
+  MVD_CHECK_LAUNCH("mvd_col_sum_groups");
+  return 0;
+}
+
+extern "C" int mvd_col_sum_groups(const float* x, int ngroups, int rows_per_group, int cols, int ldx, float* out, double* ws,
+                                  size_t ws_doubles, mvd_stream_t stream) {
+  MVD_CHECK_ARG(x && out && ws && ngroups > 0 && rows_per_group > 0 && cols > 0 && ldx >= cols, "mvd_col_sum_groups: bad arguments");
+  return col_sum_groups_launch(x, ngroups, rows_per_group, cols, ldx, out, ws, ws_doubles, (hipStream_t)stream);
+}
+
+extern "C" int mvd_layernorm_backward_groups(const float* x, const float* dy, const float* w, int ldw, int rows, int rows_per_group, int C,
+                                             float eps, float* dx, float* dyxhat, float* dw, float* db, double* ws, size_t ws_doubles,
+                                             mvd_stream_t stream) {
+  MVD_CHECK_ARG(x && dy && dx && rows > 0 && C > 0, "mvd_layernorm_backward: bad arguments");
+  MVD_CHECK_ARG(rows_per_group > 0 && rows % rows_per_group == 0 && ldw >= 0,
+                "mvd_layernorm_backward_groups: rows=%d, rows_per_group=%d (must divide rows), ldw=%d (>= 0)", rows, rows_per_group, ldw);
+  MVD_CHECK_ARG((!dw || dyxhat) && ((!dw && !db) || ws), "mvd_layernorm_backward_groups: dw needs dyxhat, dw / db need ws");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(ln_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, dy, w, rows, C, eps, dx, dyxhat, rows_per_group, ldw);
+  MVD_CHECK_LAUNCH("mvd_layernorm_backward");
+  const int ng = rows / rows_per_group;
+  if (dw) {
+    const int r = col_sum_groups_launch(dyxhat, ng, rows_per_group, C, C, dw, ws, ws_doubles, s);
+    if (r) return r;
+  }
+  if (db) return col_sum_groups_launch(dy, ng, rows_per_group, C, C, db, ws, ws_doubles, s);
   return 0;
 }
 

@@ -312,9 +312,11 @@ __global__ __launch_bounds__(256) void fill_zero_kernel(float* p, size_t n) {
   for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) p[e] = 0.f;
 }
 
+// one workgroup per scene: row n of out from step row *iter + n * steps_scene_stride (one scene: the grid is 1)
 __global__ void timestep_embedding_kernel(const float* __restrict__ steps, const int* __restrict__ iter,
-                                          const float* __restrict__ freqs, float* __restrict__ out, int dim) {
-  const float t = steps[(size_t)iter[0] * MVD_STEP_STRIDE + 0];
+                                          const float* __restrict__ freqs, float* __restrict__ out, int dim, int steps_scene_stride) {
+  const float t = steps[((size_t)iter[0] + (size_t)blockIdx.x * steps_scene_stride) * MVD_STEP_STRIDE + 0];
+  out += (size_t)blockIdx.x * dim;
   const int half = dim / 2;
   for (int i = threadIdx.x; i < half; i += blockDim.x) {
     const float a = t * freqs[i];
@@ -475,8 +477,20 @@ extern "C" int mvd_fill_zero(float* p, size_t n, mvd_stream_t stream) {
 extern "C" int mvd_timestep_embedding(const float* steps, const int* iter, const float* freqs, float* out, int dim,
                                       mvd_stream_t stream) {
   MVD_CHECK_ARG(steps && iter && freqs && out && dim > 0 && dim % 2 == 0, "mvd_timestep_embedding: bad arguments");
-  hipLaunchKernelGGL(timestep_embedding_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, steps, iter, freqs, out, dim);
+  hipLaunchKernelGGL(timestep_embedding_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, steps, iter, freqs, out, dim, 0);
   MVD_CHECK_LAUNCH("mvd_timestep_embedding");
+  return 0;
+}
+
+extern "C" int mvd_timestep_embedding_scenes(const float* steps, const int* iter, const float* freqs, float* out, int dim, int nscene,
+                                             int steps_scene_stride, mvd_stream_t stream) {
+  MVD_CHECK_ARG(steps && iter && freqs && out && dim > 0 && dim % 2 == 0, "mvd_timestep_embedding: bad arguments");
+  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535 && steps_scene_stride >= 0 && (nscene > 1 || steps_scene_stride == 0),
+                "mvd_timestep_embedding_scenes: nscene=%d (1 ... 65535), steps_scene_stride=%d (>= 0; 0 when nscene = 1)", nscene,
+                steps_scene_stride);
+  hipLaunchKernelGGL(timestep_embedding_kernel, dim3(nscene), dim3(256), 0, (hipStream_t)stream, steps, iter, freqs, out, dim,
+                     steps_scene_stride);
+  MVD_CHECK_LAUNCH("mvd_timestep_embedding_scenes");
   return 0;
 }
 

@@ -14,7 +14,8 @@ __global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ x
                                                      const float* __restrict__ steps, const int* __restrict__ iter,
                                                      const float* __restrict__ grid_lin, const float* __restrict__ feat,
                                                      const float* __restrict__ in_feat, const float* __restrict__ cams,
-                                                     const float* __restrict__ in_cam, u16* __restrict__ tok, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift) {
+                                                     const float* __restrict__ in_cam, u16* __restrict__ tok, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
+                                                     int steps_scene_stride) {
   const int lane = threadIdx.x & 63;
   const int SS = S * S;
   const size_t npts = (size_t)nscene * Vq * SS * D;
@@ -29,8 +30,9 @@ __global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ x
   in_feat += (size_t)scene * SS * 256;
   in_cam += (size_t)scene * MVD_CAM_RECORD;
   const int it = iter[0];
-  const float sqrt_ac = steps[(size_t)it * MVD_STEP_STRIDE + 1];
-  const float dstd = steps[(size_t)it * MVD_STEP_STRIDE + 2];
+  const size_t srow = (size_t)it + (size_t)scene * steps_scene_stride;      // the scene's step row (its own timestep); noise stays at it
+  const float sqrt_ac = steps[srow * MVD_STEP_STRIDE + 1];
+  const float dstd = steps[srow * MVD_STEP_STRIDE + 2];
 
   // ---- G1: depth sample and world point  (:419-432, ray_utils.py:175-202,367-369)
   const float dch = x[((size_t)(gv0 + b) * 5 + 4) * SS + pix] / sqrt_ac;
@@ -175,24 +177,32 @@ __global__ __launch_bounds__(256) void tokens_bwd_kernel(const float* __restrict
                                                          const float* __restrict__ steps, const int* __restrict__ iter,
                                                          const float* __restrict__ grid_lin, const float* __restrict__ cams,
                                                          const float* __restrict__ in_cam, const float* __restrict__ dtok, int ldt,
-                                                         long long* __restrict__ dfeat, long long* __restrict__ din_feat, float scale, int V,
-                                                         int q0, int Vq, int S, int D, float depth_scale, float depth_shift) {
+                                                         long long* __restrict__ dfeat, long long* __restrict__ din_feat, float scale, int nscene,
+                                                         int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
+                                                         int steps_scene_stride) {
   const int lane = threadIdx.x & 63;
   const int SS = S * S;
-  const size_t npts = (size_t)Vq * SS * D;
+  const size_t npts = (size_t)nscene * Vq * SS * D;
   const size_t pt = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pt >= npts) return;
   const int d = (int)(pt % D);
   const int pix = (int)((pt / D) % SS);
-  const int b = q0 + (int)(pt / ((size_t)D * SS));
+  const int qv = (int)(pt / ((size_t)D * SS));      // scene * Vq + query view, as in tokens_kernel
+  const int scene = __builtin_amdgcn_readfirstlane(qv / Vq);
+  const int gv0 = scene * V;
+  const int b = q0 + (qv - scene * Vq);
+  in_cam += (size_t)scene * MVD_CAM_RECORD;
+  din_feat += (size_t)scene * SS * 256;
+  dfeat += (size_t)gv0 * SS * 256;
   const int it = iter[0];
-  const float sqrt_ac = steps[(size_t)it * MVD_STEP_STRIDE + 1];
-  const float dstd = steps[(size_t)it * MVD_STEP_STRIDE + 2];
+  const size_t srow = (size_t)it + (size_t)scene * steps_scene_stride;
+  const float sqrt_ac = steps[srow * MVD_STEP_STRIDE + 1];
+  const float dstd = steps[srow * MVD_STEP_STRIDE + 2];
   // the forward's G1 geometry, verbatim (tokens_kernel)
-  const float dch = x[((size_t)b * 5 + 4) * SS + pix] / sqrt_ac;
-  const float smp = dch + dstd * depth_noise[(((size_t)it * V + b) * D + d) * SS + pix];
+  const float dch = x[((size_t)(gv0 + b) * 5 + 4) * SS + pix] / sqrt_ac;
+  const float smp = dch + dstd * depth_noise[(((size_t)it * nscene * V + gv0 + b) * D + d) * SS + pix];
   const float depth = fminf(fmaxf((smp + 1.0f) / 2.0f, 0.f), 1.f) * depth_scale + depth_shift;
-  const Cam cb = load_cam(cams + (size_t)b * MVD_CAM_RECORD);
+  const Cam cb = load_cam(cams + (size_t)(gv0 + b) * MVD_CAM_RECORD);
   const float ndx = grid_lin[pix % S], ndy = grid_lin[pix / S];
   float p1[3], p2[3], X[3];
   unproject(cb, ndx, ndy, 1.f, p1);
@@ -204,7 +214,7 @@ __global__ __launch_bounds__(256) void tokens_bwd_kernel(const float* __restrict
   }
   float4 gin = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int vr = 0; vr < V; ++vr) {
-    const Cam cv = load_cam(cams + (size_t)vr * MVD_CAM_RECORD);
+    const Cam cv = load_cam(cams + (size_t)(gv0 + vr) * MVD_CAM_RECORD);
     float u, v;
     project(cv, X, u, v);
     const Taps4 t = bilinear_taps(S, -u, -v);
@@ -232,21 +242,32 @@ extern "C" int mvd_zembed(const float* lat, const float* w, const float* b, floa
   return 0;
 }
 
-extern "C" int mvd_gridattn_tokens_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
-                                          const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
-                                          const float* in_cam, void* tokens_sp, int nscene, int V, int q0, int Vq, int S, int D,
-                                          float depth_scale, float depth_shift, mvd_stream_t stream) {
+extern "C" int mvd_gridattn_tokens_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                            const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                            const float* in_cam, void* tokens_sp, int nscene, int V, int q0, int Vq, int S, int D,
+                                            float depth_scale, float depth_shift, int steps_scene_stride, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && tokens_sp,
                 "mvd_gridattn_tokens: null pointer");
   MVD_CHECK_ARG(nscene >= 1, "mvd_gridattn_tokens_scenes: nscene=%d (>= 1)", nscene);
+  MVD_CHECK_ARG(steps_scene_stride >= 0 && (nscene > 1 || steps_scene_stride == 0),
+                "mvd_gridattn_tokens_scenes_t: steps_scene_stride=%d (>= 0; 0 when nscene = 1)", steps_scene_stride);
   MVD_CHECK_ARG(V > 0 && V <= 16 && S > 1 && D > 0, "mvd_gridattn_tokens: bad shape (V <= 16)");
   MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V, "mvd_gridattn_tokens: bad query-view range [%d, %d) of %d", q0, q0 + Vq, V);
   const size_t npts = (size_t)nscene * Vq * S * S * D;      // one wavefront per point: a point never straddles two scenes
   MVD_CHECK_ARG((size_t)nscene * V <= 0x7fffffff && (npts + 3) / 4 <= 0x7fffffff, "mvd_gridattn_tokens: grid too large");
   hipLaunchKernelGGL(tokens_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, x, depth_noise, steps, iter,
-                     grid_lin, feat, in_feat, cams, in_cam, (u16*)tokens_sp, nscene, V, q0, Vq, S, D, depth_scale, depth_shift);
+                     grid_lin, feat, in_feat, cams, in_cam, (u16*)tokens_sp, nscene, V, q0, Vq, S, D, depth_scale, depth_shift,
+                     steps_scene_stride);
   MVD_CHECK_LAUNCH("mvd_gridattn_tokens");
   return 0;
+}
+
+extern "C" int mvd_gridattn_tokens_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                          const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                          const float* in_cam, void* tokens_sp, int nscene, int V, int q0, int Vq, int S, int D,
+                                          float depth_scale, float depth_shift, mvd_stream_t stream) {
+  return mvd_gridattn_tokens_scenes_t(x, depth_noise, steps, iter, grid_lin, feat, in_feat, cams, in_cam, tokens_sp, nscene, V, q0, Vq, S,
+                                      D, depth_scale, depth_shift, 0, stream);
 }
 
 extern "C" int mvd_gridattn_tokens(const float* x, const float* depth_noise, const float* steps, const int* iter,
@@ -257,18 +278,31 @@ extern "C" int mvd_gridattn_tokens(const float* x, const float* depth_noise, con
                                     depth_scale, depth_shift, stream);
 }
 
+extern "C" int mvd_gridattn_tokens_backward_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                                   const float* grid_lin, const float* cams, const float* in_cam, const float* dtok, int ldt,
+                                                   long long* dfeat_acc, long long* din_feat_acc, float scale, int nscene, int V, int q0,
+                                                   int Vq, int S, int D, float depth_scale, float depth_shift, int steps_scene_stride,
+                                                   mvd_stream_t stream) {
+  MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && cams && in_cam && dtok && dfeat_acc && din_feat_acc,
+                "mvd_gridattn_tokens_backward: null pointer");
+  MVD_CHECK_ARG(nscene >= 1 && steps_scene_stride >= 0 && (nscene > 1 || steps_scene_stride == 0),
+                "mvd_gridattn_tokens_backward_scenes: nscene=%d (>= 1), steps_scene_stride=%d (>= 0; 0 when nscene = 1)", nscene,
+                steps_scene_stride);
+  MVD_CHECK_ARG(V > 0 && V <= 16 && S > 1 && D > 0 && ldt >= 512 && ldt % 4 == 0 && ((uintptr_t)dtok & 15) == 0 && scale > 0.f,
+                "mvd_gridattn_tokens_backward: bad shape (ldt >= 512, 16-byte aligned dtok)");
+  MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V, "mvd_gridattn_tokens_backward: bad query-view range");
+  const size_t npts = (size_t)nscene * Vq * S * S * D;
+  MVD_CHECK_ARG((size_t)nscene * V <= 0x7fffffff && (npts + 3) / 4 <= 0x7fffffff, "mvd_gridattn_tokens_backward: grid too large");
+  hipLaunchKernelGGL(tokens_bwd_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, x, depth_noise, steps, iter, grid_lin, cams,
+                     in_cam, dtok, ldt, dfeat_acc, din_feat_acc, scale, nscene, V, q0, Vq, S, D, depth_scale, depth_shift, steps_scene_stride);
+  MVD_CHECK_LAUNCH("mvd_gridattn_tokens_backward");
+  return 0;
+}
+
 extern "C" int mvd_gridattn_tokens_backward(const float* x, const float* depth_noise, const float* steps, const int* iter,
                                             const float* grid_lin, const float* cams, const float* in_cam, const float* dtok, int ldt,
                                             long long* dfeat_acc, long long* din_feat_acc, float scale, int V, int q0, int Vq, int S, int D,
                                             float depth_scale, float depth_shift, mvd_stream_t stream) {
-  MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && cams && in_cam && dtok && dfeat_acc && din_feat_acc,
-                "mvd_gridattn_tokens_backward: null pointer");
-  MVD_CHECK_ARG(V > 0 && V <= 16 && S > 1 && D > 0 && ldt >= 512 && ldt % 4 == 0 && ((uintptr_t)dtok & 15) == 0 && scale > 0.f,
-                "mvd_gridattn_tokens_backward: bad shape (ldt >= 512, 16-byte aligned dtok)");
-  MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V, "mvd_gridattn_tokens_backward: bad query-view range");
-  const size_t npts = (size_t)Vq * S * S * D;
-  hipLaunchKernelGGL(tokens_bwd_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, x, depth_noise, steps, iter, grid_lin, cams,
-                     in_cam, dtok, ldt, dfeat_acc, din_feat_acc, scale, V, q0, Vq, S, D, depth_scale, depth_shift);
-  MVD_CHECK_LAUNCH("mvd_gridattn_tokens_backward");
-  return 0;
+  return mvd_gridattn_tokens_backward_scenes(x, depth_noise, steps, iter, grid_lin, cams, in_cam, dtok, ldt, dfeat_acc, din_feat_acc, scale,
+                                             1, V, q0, Vq, S, D, depth_scale, depth_shift, 0, stream);
 }

@@ -66,6 +66,7 @@ struct G4Params {
   u16* pooled_sp;                 // (Nseq, 256) split planes
   int V, Vp, lv, q0, Vq, S, D, nslots;      // Vp = 2^lv >= V: rows per 3-D point (reference views padded to a power of two)
   int nscene, wg_per_scene;                 // scenes in the launch; workgroups per scene (Vq*S*S*D*Vp / 64)
+  int steps_scene_stride, vecs_scene_stride;  // scene n: step row *iter + n * steps_scene_stride, vector table vecs + n * vecs_scene_stride
   float depth_scale, depth_shift;
 };
 
@@ -204,6 +205,10 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   const int r16 = lane & 15, g = lane >> 4;
   const float* const smisc = (const float*)(smem + G4_OFF_MISC);        // index = global index - G4_VEC_MISC
   const int V = p.V, Vp = p.Vp, lv = p.lv, S = p.S, D = p.D, SS = S * S;
+  const int scene = (int)(blockIdx.x / (unsigned)p.wg_per_scene);        // workgroup-uniform (scalar)
+  // the scene's own timestep: its vector table (adaLN modulation) and step row; both strides are 0 for a shared timestep
+  const float* const vecs = p.vecs + (size_t)scene * p.vecs_scene_stride;
+  const float* const steps = p.steps + (size_t)scene * p.steps_scene_stride * MVD_STEP_STRIDE;
 
   // ------------------------------------------------------------------ LDS-DMA engine
   // This wave copies granules [8 wave, 8 wave + 8) of every slot.  The copy is linear (source stride = destination stride = 1 KiB), so
@@ -255,9 +260,9 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   // the 13 granules of DiT block `blk`'s vectors -> LDS buffer blk & 1: wave 0 takes granules 0-3, waves 1-3 three each
   auto stage_block_vecs = [&](int blk) {
     const int g0 = wave == 0 ? 0 : 1 + 3 * wave, cnt = wave == 0 ? 4 : 3;
-    dma_run((const unsigned char*)p.vecs + (size_t)blk * G4_BLK_BYTES + g0 * 1024, lds_ring + G4_OFF_BLK + (blk & 1) * G4_BLK_BYTES + g0 * 1024, cnt);
+    dma_run((const unsigned char*)vecs + (size_t)blk * G4_BLK_BYTES + g0 * 1024, lds_ring + G4_OFF_BLK + (blk & 1) * G4_BLK_BYTES + g0 * 1024, cnt);
   };
-  dma_run((const unsigned char*)p.vecs + (size_t)G4_VEC_MISC * 4 + wave * 1024, lds_ring + G4_OFF_MISC + wave * 1024, 1);      // misc: 4 granules
+  dma_run((const unsigned char*)vecs + (size_t)G4_VEC_MISC * 4 + wave * 1024, lds_ring + G4_OFF_MISC + wave * 1024, 1);      // misc: 4 granules
   stage_block_vecs(0);
   stage_block_vecs(1);
   bool stage_blk2 = false;         // set at the top of block 1: block 2's vectors replace block 0's behind the next barrier
@@ -344,7 +349,6 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   const int vr = pad_row ? V - 1 : vslot;
   const int d = (int)(pt % D);
   const int pix = (int)((pt / D) % SS);
-  const int scene = (int)(blockIdx.x / (unsigned)p.wg_per_scene);        // workgroup-uniform (scalar)
   const int b = p.q0 + (int)(pt / ((size_t)D * SS)) - scene * p.Vq;      // query view inside the scene
   const int gv0 = scene * V;                                             // global index of the scene's view 0
   // geometry of this lane's row: world point, Plucker coordinates, bilinear taps in the reference view and the input view
@@ -353,8 +357,8 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   Taps tr, ti;
   {
     const int it = p.iter[0];
-    const float sqrt_ac = p.steps[(size_t)it * MVD_STEP_STRIDE + 1];
-    const float dstd = p.steps[(size_t)it * MVD_STEP_STRIDE + 2];
+    const float sqrt_ac = steps[(size_t)it * MVD_STEP_STRIDE + 1];
+    const float dstd = steps[(size_t)it * MVD_STEP_STRIDE + 2];
     const float dch = p.x[((size_t)(gv0 + b) * 5 + 4) * SS + pix] / sqrt_ac;
     const float smp = dch + dstd * p.depth_noise[(((size_t)it * p.nscene * V + gv0 + b) * D + d) * SS + pix];
     depth = fminf(fmaxf((smp + 1.0f) / 2.0f, 0.f), 1.f) * p.depth_scale + p.depth_shift;
@@ -705,13 +709,18 @@ extern "C" int mvd_gridattn_fused_slots(void) { return 23 + 3 * 64; }
 extern "C" size_t mvd_gridattn_fused_stream_bytes(void) { return (size_t)(23 + 3 * 64) * G4_SLOT_BYTES; }
 extern "C" size_t mvd_gridattn_fused_vec_floats(void) { return (size_t)G4_VEC_GRANULES * 256; }
 
-extern "C" int mvd_gridattn_fused_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
-                                         const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+extern "C" int mvd_gridattn_fused_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                           const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
                                          const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int nscene, int V,
-                                         int q0, int Vq, int S, int D, float depth_scale, float depth_shift, int prec, mvd_stream_t stream) {
+                                         int q0, int Vq, int S, int D, float depth_scale, float depth_shift, int prec, int steps_scene_stride,
+                                         int vecs_scene_stride, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && wstream && vecs && pooled_sp,
                 "mvd_gridattn_fused: null pointer");
   MVD_CHECK_ARG(nscene >= 1, "mvd_gridattn_fused_scenes: nscene=%d (>= 1)", nscene);
+  MVD_CHECK_ARG(steps_scene_stride >= 0 && vecs_scene_stride >= 0 && vecs_scene_stride % 4 == 0 &&
+                    (nscene > 1 || (steps_scene_stride == 0 && vecs_scene_stride == 0)),
+                "mvd_gridattn_fused_scenes_t: steps_scene_stride=%d, vecs_scene_stride=%d (>= 0, vecs stride a multiple of 4; both 0 when "
+                "nscene = 1)", steps_scene_stride, vecs_scene_stride);
   MVD_CHECK_ARG(V >= 1 && V <= 16, "mvd_gridattn_fused: V=%d outside [1, 16] (use the unfused path)", V);
   int lv = 0;
   while ((1 << lv) < V) ++lv;
@@ -730,12 +739,21 @@ extern "C" int mvd_gridattn_fused_scenes(const float* x, const float* depth_nois
   p.in_feat = in_feat; p.cams = cams; p.in_cam = in_cam; p.wstream = (const unsigned char*)wstream; p.vecs = vecs;
   p.pooled_sp = (u16*)pooled_sp; p.V = V; p.Vp = Vp; p.lv = lv; p.q0 = q0; p.Vq = Vq; p.S = S; p.D = D; p.nslots = 23 + 3 * 64;
   p.nscene = nscene; p.wg_per_scene = (int)(Ts / 64);
+  p.steps_scene_stride = steps_scene_stride; p.vecs_scene_stride = vecs_scene_stride;
   p.depth_scale = depth_scale; p.depth_shift = depth_shift;
   const dim3 grid((unsigned)(Ts / 64 * nscene));
   if (prec == MVD_PREC_X3) hipLaunchKernelGGL(g4_fused_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(g4_fused_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
   MVD_CHECK_LAUNCH("mvd_gridattn_fused");
   return 0;
+}
+
+extern "C" int mvd_gridattn_fused_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                         const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                         const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int nscene, int V,
+                                         int q0, int Vq, int S, int D, float depth_scale, float depth_shift, int prec, mvd_stream_t stream) {
+  return mvd_gridattn_fused_scenes_t(x, depth_noise, steps, iter, grid_lin, feat, in_feat, cams, in_cam, wstream, vecs, pooled_sp, nscene, V,
+                                     q0, Vq, S, D, depth_scale, depth_shift, prec, 0, 0, stream);
 }
 
 extern "C" int mvd_gridattn_fused(const float* x, const float* depth_noise, const float* steps, const int* iter,

@@ -326,10 +326,13 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 template <int MAXV>
 __global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, u16* __restrict__ y_sp, float* __restrict__ y_f32,
                                                  const float* __restrict__ w, const float* __restrict__ bia, int rows, int C, float eps,
-                                                 int w_plus_one) {
+                                                 int w_plus_one, int rows_per_group, int ldw) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
+  const size_t goff = (size_t)(row / rows_per_group) * ldw;      // the row group's (scene's) modulation: w / b + group * ldw
+  if (w) w += goff;
+  if (bia) bia += goff;
   const int n4 = C >> 2;
   const float4* xr = (const float4*)(x + (size_t)row * C);
   float4 v[MAXV];
@@ -447,20 +450,27 @@ extern "C" int mvd_softmax_rows(const float* x, void* y_sp, int rows, int cols, 
   return 0;
 }
 
-extern "C" int mvd_layernorm(const float* x, void* y_sp, float* y_f32, const float* w, const float* b, int rows, int C, float eps,
-                             int w_plus_one, mvd_stream_t stream) {
+extern "C" int mvd_layernorm_groups(const float* x, void* y_sp, float* y_f32, const float* w, const float* b, int ldw, int rows,
+                                    int rows_per_group, int C, float eps, int w_plus_one, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && (y_sp || y_f32) && rows > 0, "mvd_layernorm: bad arguments");
   MVD_CHECK_ARG(C % 32 == 0, "mvd_layernorm: split-planes output needs C %% 32 == 0 (C=%d)", C);
   u16* yh = (u16*)y_sp;
   MVD_CHECK_ARG(C % 4 == 0 && C >= 4 && C <= 1280, "mvd_layernorm: C=%d must be a multiple of 4 and <= 1280", C);
+  MVD_CHECK_ARG(rows_per_group > 0 && rows % rows_per_group == 0 && ldw >= 0 && ldw % 4 == 0,
+                "mvd_layernorm_groups: rows=%d, rows_per_group=%d (must divide rows), ldw=%d (>= 0, a multiple of 4)", rows, rows_per_group, ldw);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(cdiv(rows, 4));
   if (C <= 256)
-    hipLaunchKernelGGL(ln_kernel<1>, grid, dim3(256), 0, s, x, yh, y_f32, w, b, rows, C, eps, w_plus_one);
+    hipLaunchKernelGGL(ln_kernel<1>, grid, dim3(256), 0, s, x, yh, y_f32, w, b, rows, C, eps, w_plus_one, rows_per_group, ldw);
   else if (C <= 512)
-    hipLaunchKernelGGL(ln_kernel<2>, grid, dim3(256), 0, s, x, yh, y_f32, w, b, rows, C, eps, w_plus_one);
+    hipLaunchKernelGGL(ln_kernel<2>, grid, dim3(256), 0, s, x, yh, y_f32, w, b, rows, C, eps, w_plus_one, rows_per_group, ldw);
   else
-    hipLaunchKernelGGL(ln_kernel<5>, grid, dim3(256), 0, s, x, yh, y_f32, w, b, rows, C, eps, w_plus_one);
+    hipLaunchKernelGGL(ln_kernel<5>, grid, dim3(256), 0, s, x, yh, y_f32, w, b, rows, C, eps, w_plus_one, rows_per_group, ldw);
   MVD_CHECK_LAUNCH("mvd_layernorm");
   return 0;
+}
+
+extern "C" int mvd_layernorm(const float* x, void* y_sp, float* y_f32, const float* w, const float* b, int rows, int C, float eps,
+                             int w_plus_one, mvd_stream_t stream) {
+  return mvd_layernorm_groups(x, y_sp, y_f32, w, b, 0, rows, rows, C, eps, w_plus_one, stream);
 }

@@ -93,6 +93,7 @@ SIGNATURES = {
     "mvd_groupnorm_chunks": (_i, [_i]),
     "mvd_groupnorm_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
     "mvd_layernorm": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp]),
+    "mvd_layernorm_groups": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp]),
     "mvd_softmax_rows": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp]),
     "mvd_attn_qk_plane_elems": (_sz, [_i, _i, _i, _i]),
     "mvd_attn_vt_plane_elems": (_sz, [_i, _i, _i, _i]),
@@ -108,9 +109,14 @@ SIGNATURES = {
     "mvd_im2col3x3_t_planes": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
     "mvd_col_sum_workspace_doubles": (_sz, [_i, _i]),
     "mvd_col_sum": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mvd_col_sum_groups_workspace_doubles": (_sz, [_i, _i, _i]),
+    "mvd_col_sum_groups": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mvd_col_sum_pow2": (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp]),
     "mvd_gridattn_tokens_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    "mvd_gridattn_tokens_backward_scenes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _f, _f, _i,
+                                                 _vp]),
     "mvd_layernorm_backward": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "mvd_layernorm_backward_groups": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvd_geglu_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "mvd_act_planes": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "mvd_act_backward": (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
@@ -125,15 +131,18 @@ SIGNATURES = {
     "mvd_transpose_planes_scaled": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     "mvd_adamw_multi": (_i, [_vp, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _vp]),
     "mvd_timestep_embedding": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "mvd_timestep_embedding_scenes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvd_advance_iter": (_i, [_vp, _vp]),
     "mvd_zembed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mvd_gridattn_tokens": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _f, _f, _vp]),
     "mvd_gridattn_tokens_scenes": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _f, _f, _vp]),
+    "mvd_gridattn_tokens_scenes_t": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "mvd_gridattn_fused_slots": (_i, []),
     "mvd_gridattn_fused_stream_bytes": (_sz, []),
     "mvd_gridattn_fused_vec_floats": (_sz, []),
     "mvd_gridattn_fused": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "mvd_gridattn_fused_scenes": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
+    "mvd_gridattn_fused_scenes_t": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _vp]),
     "mvd_view_mha": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mvd_view_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvd_cfg_ddim_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
@@ -961,6 +970,15 @@ def groupnorm_from_stats(x, y, gamma, beta, stats, B, HW, Cc, eps, silu, groups=
 def layernorm(x, y, w, b, rows, Cc, eps=1e-5, w_plus_one=False, y_f32=None):
     """y: split planes (rows, 2*C) (or None); y_f32: optional fp32 (rows, C) copy of the result."""
     check(lib().mvd_layernorm(ptr(x), ptr(y), ptr(y_f32), ptr(w), ptr(b), rows, Cc, eps, int(w_plus_one), stream()))
+    return y
+
+
+def layernorm_groups(x, y, w, b, rows, Cc, rows_per_group, eps=1e-5, w_plus_one=False, y_f32=None):
+    """layernorm with one (w, b) row per group of rows_per_group consecutive rows (mvd_layernorm_groups): w, b (ngroups, C) views sharing
+    one row stride (e.g. column slices of an (N, 6C) adaLN modulation)."""
+    assert w.stride(0) == b.stride(0) and w.stride(-1) == 1 and b.stride(-1) == 1, (w.stride(), b.stride())
+    check(lib().mvd_layernorm_groups(ptr(x), ptr(y), ptr(y_f32), ptr(w), ptr(b), w.stride(0), rows, int(rows_per_group), Cc, eps,
+                                     int(w_plus_one), stream()))
     return y
 
 

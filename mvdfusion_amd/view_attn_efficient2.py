@@ -239,7 +239,7 @@ class GridAttn(nn.Module):
                 all(b.num_heads == 8 and b.mlp.fc1.out_features == 512 for b in blocks))
 
     def run(self, ctx, x, depth_noise, steps, it, cams_rec, in_cam_rec, input_latents, c, vol_out, V, S, D, q0=0, Vq=None,
-            vol_planes=None, vol_planes_col=0, fused=None, depth_src=None, depth_steps=None, scenes=1):
+            vol_planes=None, vol_planes_col=0, fused=None, depth_src=None, depth_steps=None, scenes=1, steps_scene_stride=0):
         """x (V,5,S,S) noisy latents; c (1,256) time conditioning (t_embed[:1]); vol_out: (>=V*S*S*D, 768) buffer
         whose first Vq*S*S*D rows receive the feature frustum (row = ((v*S + y)*S + x)*D + d) of the query views
         [q0, q0+Vq) (all V views by default; a view-parallel rank passes the range it owns).  vol_planes: optional planes
@@ -250,7 +250,9 @@ class GridAttn(nn.Module):
         map to sample around INSTEAD of the x0-style estimate x[:,4] / sqrt(alpha_bar), with a step table whose sqrt(alpha_bar) column
         is 1 (x / 1 is exact) and whose depth-std column is unchanged -- the kernels themselves are the same.
         scenes: N independent rigs of V views each in one launch (scene-major: x / cams_rec / depth_noise hold N*V views, global view
-        scene*V + v; input_latents / in_cam_rec hold N); vol_out's first N*Vq*S*S*D rows receive the frustums scene after scene."""
+        scene*V + v; input_latents / in_cam_rec hold N); vol_out's first N*Vq*S*S*D rows receive the frustums scene after scene.
+        steps_scene_stride (training, one timestep per scene): scene n reads step row it + n * steps_scene_stride and c row n (c is (N, 256));
+        the fused kernel then gets one vector table per scene."""
         Vq = V if Vq is None else Vq
         N = int(scenes)
         L = hip.lib()
@@ -276,6 +278,28 @@ class GridAttn(nn.Module):
             ctx.ws.bufs[("ga.lin", S)] = grid_lin
         if fused is None:
             fused = self.fused_supported(V, T // N)
+        sst = int(steps_scene_stride)
+        if sst:
+            assert N > 1 and c.shape[0] == N, (N, tuple(c.shape))
+            if fused is False or not self.fused_supported(V, T // N):
+                raise NotImplementedError(f"GridAttn.run: per-scene timesteps need the fused aggregation kernel (V={V}, T={T // N} per scene); "
+                                          "the unfused chain shares one adaLN modulation")
+            fused = True
+        if fused and sst:
+            stream, vecs1 = self.packed_fused(ctx.device)
+            nv = vecs1.numel()
+            vecs = ctx.ws.get("ga.vecs_scenes", (N, nv))
+            vecs.copy_(vecs1.view(1, nv).expand(N, nv))          # biases / scales per scene, then each scene's adaLN modulation
+            for bi, blk in enumerate(self.aggregation_transformer.layer_list):
+                lin = blk.adaLN_modulation[1]
+                ctx.gemv_rows(lin.weight, lin.bias, c, vecs[:, bi * _G4_VEC_BLOCK:bi * _G4_VEC_BLOCK + 1536], act_in=hip.ACT_SILU)
+            pool = ctx.ws.planes("ga.pool", nseq, self.hidden_size)
+            hip.check(L.mvd_gridattn_fused_scenes_t(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
+                                                    hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec), hip.ptr(stream),
+                                                    hip.ptr(vecs), hip.ptr(pool), N, V, q0, Vq, S, D, float(self.depth_scale),
+                                                    float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, sst, nv, hip.stream()))
+            ctx.gemm(pool, w_fin, vol_out, M=nseq, out_planes=vol_planes, out_planes_col=vol_planes_col, kind="ga")
+            return vol_out
         if fused:
             assert self.fused_supported(V, T // N), (V, T // N)
             stream, vecs = self.packed_fused(ctx.device)

@@ -85,6 +85,7 @@ class StepEngine:
         self.prefetchers = {}      # per captured graph: its hip.WeightPrefetcher (None when PREFETCH_WEIGHTS is off)
         self.drop_masks = None     # training forward: (clip_mask, volume_mask, concat_mask), each (Vq,) in {0, 1} (unet.py:140-151)
         self.n_rows = 1            # rows of the device step table; the kernels index steps[iter], noise[iter] unchecked
+        self.steps_scene_stride = 0      # 0: one timestep for every scene; 1 (set_schedule_scenes, cfg=False): scene n reads step row iter + n
         self.done = 0              # host mirror of the device iteration counter
 
     # -- host-side inputs ----------------------------------------------------------------------------
@@ -108,6 +109,28 @@ class StepEngine:
             self.clip_v_embed[n * V:(n + 1) * V].copy_(ce.reshape(V, 796))
 
     def set_schedule(self, steps_table, depth_noise, ddim_noise):
+        self.steps_scene_stride = 0
+        self._set_tables(steps_table, depth_noise, ddim_noise)
+        self.n_rows = int(steps_table.shape[0])
+        self.rewind()
+
+    def set_schedule_scenes(self, steps_table, depth_noise, ddim_noise=None):
+        """One training step with a timestep PER SCENE: steps_table (N, STEP_STRIDE) holds scene n's row n, depth_noise (1, N*V, D, S, S).
+        Only on cfg=False engines (the training forward; a guided sampling step shares one schedule) and without a DDIM update."""
+        if self.cfg:
+            raise ValueError("StepEngine.set_schedule_scenes: per-scene timesteps need a cfg=False engine (the training step); "
+                             "guided sampling steps share one timestep")
+        if tuple(steps_table.shape) != (self.N, hip.STEP_STRIDE):
+            raise ValueError(f"StepEngine.set_schedule_scenes: step table {tuple(steps_table.shape)} for {self.N} scenes "
+                             f"(expected ({self.N}, {hip.STEP_STRIDE}))")
+        if ddim_noise is None:
+            ddim_noise = torch.zeros(1, self.N * self.V, 5, self.S, self.S)
+        self._set_tables(steps_table, depth_noise, ddim_noise)
+        self.steps_scene_stride = 1 if self.N > 1 else 0
+        self.n_rows = 1
+        self.rewind()
+
+    def _set_tables(self, steps_table, depth_noise, ddim_noise):
         dev = self.ctx.device
         if self.steps.shape != steps_table.shape:
             self.graphs.clear()                # table buffers are re-allocated: captured pointers go stale
@@ -122,8 +145,6 @@ class StepEngine:
             self.ddim_noise.copy_(ddim_noise)
         self.steps_nodiv.copy_(self.steps)
         self.steps_nodiv[:, 1] = 1.0
-        self.n_rows = int(steps_table.shape[0])
-        self.rewind()
 
     def rewind(self, it=0):
         """Reset the device iteration counter (and its host mirror) to row `it` of the step table."""
@@ -145,19 +166,29 @@ class StepEngine:
         ctx.B, ctx.D = B, D
         ctx.begin_step()           # eager warm-up and graph capture walk the same rotating buffers
         st = hip.stream
-        # embed_time (:276-279): sinusoid(256) -> Linear -> SiLU -> Linear; only row 0 is used downstream (t[:1])
-        ts = ctx.ws.get("vf.tsin", (1, 256))
-        hip.check(L.mvd_timestep_embedding(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, st()))
-        te1 = ctx.ws.get("vf.te1", (1, 256))
-        hip.gemv(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
-        c = ctx.ws.get("vf.c", (1, 256))
-        hip.gemv(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
+        sst, R = self.steps_scene_stride, self.t_rows
+        if sst and do_update:
+            raise ValueError("StepEngine: per-scene timesteps (set_schedule_scenes) are a training step: no DDIM update")
+        # embed_time (:276-279): sinusoid(256) -> Linear -> SiLU -> Linear; only row 0 is used downstream (t[:1]) -- one row per scene
+        # when every scene has its own timestep
+        ts = ctx.ws.get("vf.tsin", (R, 256))
+        te1 = ctx.ws.get("vf.te1", (R, 256))
+        c = ctx.ws.get("vf.c", (R, 256))
+        if R == 1:
+            hip.check(L.mvd_timestep_embedding(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, st()))
+            hip.gemv(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
+            hip.gemv(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
+        else:
+            hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, R,
+                                                      sst, st()))
+            ctx.gemv_rows(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
+            ctx.gemv_rows(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
         # view-aligned features (:303-313)
         dsrc, dsteps = self.depth_geo()
         m.view_attn.run(ctx, self.x, self.depth_noise, self.steps, self.iter, self.cams, self.in_cam,
                         self.input_latents, c, self.vol, V, S, D, q0=q0, Vq=Vq, vol_planes=self.vol_planes,
                         vol_planes_col=self.vol_col, depth_src=None if self.depth_mode == 0 else dsrc,
-                        depth_steps=None if self.depth_mode == 0 else dsteps, scenes=N)
+                        depth_steps=None if self.depth_mode == 0 else dsteps, scenes=N, steps_scene_stride=sst)
         # cc_projection (:322)
         p = m.cc_projection
         c1 = ctx.ws.get("vf.cc1", (NVq, 768))
@@ -166,11 +197,11 @@ class StepEngine:
         ctx.gemv_rows(p[2].weight, p[2].bias, c1, c2, act_out=hip.ACT_SILU)
         ctx.gemv_rows(p[4].weight, p[4].bias, c2, self.context[:NVq])
         if self.drop_masks is not None:        # UNetWrapper.forward(is_train=True) condition dropout (eager only, never captured)
-            clip_m, vol_m, cat_m = self.drop_masks
-            self.context[:Vq] *= clip_m[:, None]
-            self.vol.view(B, -1)[:Vq] *= vol_m[:, None]
+            clip_m, vol_m, cat_m = self.drop_masks          # (N*Vq,) each, scene-major
+            self.context[:NVq] *= clip_m[:, None]
+            self.vol.view(B, -1)[:NVq] *= vol_m[:, None]
             vp = self.vol_planes.view(B, S * S * D, -1)
-            vp[:Vq, :, 2 * self.vol_col:] *= vol_m.to(torch.int16)[:, None, None]        # x * {0, 1} keeps / zeroes the planes
+            vp[:NVq, :, 2 * self.vol_col:] *= vol_m.to(torch.int16)[:, None, None]        # x * {0, 1} keeps / zeroes the planes
         ctx.context = self.context
         # UNet on the CFG batch (unet.py:167-196)
         xq, x0q, epsq = self.x[q0:q0 + NVq], self.x0[q0:q0 + NVq], self.eps[q0:q0 + NVq]
@@ -179,13 +210,17 @@ class StepEngine:
         if self.drop_masks is not None:        # x_concat channels 5..9 of the (rows, [32 hi | 32 lo]) input planes
             xin = self.x_in.view(B, S * S, 64)
             cm = self.drop_masks[2].to(torch.int16)[:, None, None]
-            xin[:Vq, :, 5:10] *= cm
-            xin[:Vq, :, 37:42] *= cm
+            xin[:NVq, :, 5:10] *= cm
+            xin[:NVq, :, 37:42] *= cm
         unet = m.unet_model.unet_model
         ctx.vol_levels = m.unet_model.volume_pyramid(ctx, self.vol.view(B, S, S, D, 768), B, S, D)
-        tsu = ctx.ws.get("vf.tsin_unet", (1, unet.model_channels))
-        hip.check(L.mvd_timestep_embedding(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
-                                           unet.model_channels, st()))
+        tsu = ctx.ws.get("vf.tsin_unet", (R, unet.model_channels))
+        if R == 1:
+            hip.check(L.mvd_timestep_embedding(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
+                                               unet.model_channels, st()))
+        else:
+            hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
+                                                      unet.model_channels, R, sst, st()))
         y = unet.run(ctx, self.x_in, tsu, S)
         hip.check(L.mvd_cfg_ddim_update(hip.ptr(y), 8, hip.ptr(xq), hip.ptr(x0q), hip.ptr(epsq),
                                         hip.ptr(self.ddim_noise[:, q0:q0 + NVq]), N * V * 5 * S * S, hip.ptr(self.steps),
@@ -193,8 +228,13 @@ class StepEngine:
         if do_update:
             hip.check(L.mvd_advance_iter(hip.ptr(self.iter), st()))
 
+    @property
+    def t_rows(self):
+        """Rows of the time conditioning (vf.tsin / vf.c / temb.emb ...): N with per-scene timesteps, else 1."""
+        return self.N if self.steps_scene_stride else 1
+
     def step(self, cfg_scale, do_update, use_graph=True):
-        key = (float(cfg_scale), bool(do_update), int(self.depth_mode))
+        key = (float(cfg_scale), bool(do_update), int(self.depth_mode), self.steps_scene_stride)
         if self.done >= self.n_rows:
             raise IndexError(f"StepEngine.step: iteration {self.done} is past the {self.n_rows}-row step table "
                              "(set_schedule() / rewind() before stepping again)")
@@ -251,6 +291,7 @@ class _HipTrainingLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, batch, trainer_config, names, *params):
         loss, grads = model.gradients(batch, trainer_config, noise_source=getattr(model, "_noise_source", None), only_trainable=True)
+        # (batch: one dict, or a list of them = one multi-scene step: gradients_scenes)
         ctx.grads = [grads.get(n) for n in names]
         ctx.shapes = [p.shape for p in params]
         return loss.clone()
@@ -519,6 +560,7 @@ class ViewFusion(nn.Module):
             drop_cat, drop_all = (r > 0.05) & (r <= 0.1), r <= 0.05
             eng.drop_masks = tuple(1.0 - (dm | drop_all).float() for dm in (drop_clip, drop_vol, drop_cat))
         self._last_drop_masks = eng.drop_masks
+        self._train_engine = eng
         keep = eng.ctx.keep_fp32
         eng.ctx.keep_fp32 = keep or bool(getattr(self, "_train_keep_fp32", False))      # this engine only (never a class-wide switch)
         try:
@@ -568,14 +610,7 @@ class ViewFusion(nn.Module):
         V, _, S, _ = batch_latents.shape
         D = self.view_attn.n_pts_per_ray
         dev = batch_latents.device
-        if noise_source is not None:
-            ns = noise_source(V, D, S)
-            t, noise = ns["t"].to(dev), ns["noise"].to(dev)
-            depth_noise, drop_rand = ns["depth_noise"].to(dev), ns["drop_rand"].to(dev)
-        else:
-            t = self.scheduler.sample_random_times(V, share_t=True, device=dev)
-            noise = torch.randn_like(batch_latents)
-            depth_noise, drop_rand = torch.randn(V, D, S, S, device=dev), torch.rand(V, device=dev)
+        t, noise, depth_noise, drop_rand = self._draw(batch_latents, D, noise_source)
         sac = self.scheduler.sqrt_alphas_cumprod.to(dev)[t].view(V, 1, 1, 1)
         s1m = self.scheduler.sqrt_one_minus_alphas_cumprod.to(dev)[t].view(V, 1, 1, 1)
         noisy = sac * batch_latents + s1m * noise                                          # scheduler.q_sample (:55-64)
@@ -599,6 +634,130 @@ class ViewFusion(nn.Module):
             _aux.update(pred=pred, target=target)
         return loss
 
+    def _draw(self, batch_latents, D, noise_source):
+        """The random draws of one scene's training step, in the reference's order: (t (V,) shared, noise, depth_noise (V, D, S, S),
+        drop_rand (V,)).  noise_source(V, D, S) -> dict(t, noise, depth_noise, drop_rand) replaces torch's generator."""
+        V, _, S, _ = batch_latents.shape
+        dev = batch_latents.device
+        if noise_source is not None:
+            ns = noise_source(V, D, S)
+            return ns["t"].to(dev), ns["noise"].to(dev), ns["depth_noise"].to(dev), ns["drop_rand"].to(dev)
+        t = self.scheduler.sample_random_times(V, share_t=True, device=dev)
+        noise = torch.randn_like(batch_latents)
+        return t, noise, torch.randn(V, D, S, S, device=dev), torch.rand(V, device=dev)
+
+    def scene_draws(self, latents, noise_source=None):
+        """The draws of an N-scene training step: scene after scene, each exactly what a single-scene p_losses on that scene draws
+        (noise_source called once per scene, in order; torch's generator consumed in the single-scene order).  latents: one (V, 5, S, S)
+        tensor per scene.  Returns a list of (t, noise, depth_noise, drop_rand)."""
+        D = self.view_attn.n_pts_per_ray
+        return [self._draw(bl, D, noise_source) for bl in latents]
+
+    def _prepare_scenes(self, batches, trainer_config):
+        """prepare_batch for every scene of a training step, after checking the list: non-empty, the same V and S everywhere."""
+        if isinstance(batches, dict) or not isinstance(batches, (list, tuple)):
+            raise TypeError("a multi-scene training step takes a list of batch dicts")
+        if len(batches) == 0:
+            raise ValueError("a multi-scene training step needs at least one scene")
+        prepared = [b["_prepared"] if isinstance(b, dict) and "_prepared" in b else self.prepare_batch(b, trainer_config) for b in batches]
+        V, _, S, _ = prepared[0][0].shape
+        for n, pr in enumerate(prepared):
+            Vn, _, Sn, _ = pr[0].shape
+            if Vn != V:
+                raise ValueError(f"scene {n} has {Vn} views, scene 0 has {V}: the scenes of a training step share V")
+            if Sn != S:
+                raise ValueError(f"scene {n} has {Sn}x{Sn} latents, scene 0 has {S}x{S}: the scenes of a training step share S")
+        return prepared
+
+    @torch.no_grad()
+    def p_losses_scenes(self, batches, trainer_config, noise_source=None, _aux=None):
+        """p_losses over N scenes in ONE batched step (scene-major views, global view scene*V + v): every scene draws its own timestep,
+        noise, depth noise and dropout exactly as a single-scene p_losses on it would (scene_draws), the GEMMs / attention / convolutions
+        run once over all N*V images, and the loss is the mean of the N single-scene losses (the MSE over all N*V views).  One batch: p_losses."""
+        prepared = self._prepare_scenes(batches, trainer_config)
+        if len(prepared) == 1:
+            return self.p_losses({"_prepared": prepared[0]}, trainer_config, noise_source=noise_source, _aux=_aux)
+        N = len(prepared)
+        V, _, S, _ = prepared[0][0].shape
+        D = self.view_attn.n_pts_per_ray
+        draws = self.scene_draws([pr[0] for pr in prepared], noise_source)
+        dev = prepared[0][0].device
+        sa, s1 = self.scheduler.sqrt_alphas_cumprod.to(dev), self.scheduler.sqrt_one_minus_alphas_cumprod.to(dev)
+        noisy = torch.cat([sa[t].view(V, 1, 1, 1) * pr[0] + s1[t].view(V, 1, 1, 1) * nz                  # q_sample per scene (:55-64)
+                           for pr, (t, nz, _, _) in zip(prepared, draws)])
+        ts = [int(t[0]) for t, _, _, _ in draws]
+        conds = [(bc, il, ic, ce) for _, bc, il, ic, ce in prepared]
+        prev = [pr[2][:, 4:].clone() for pr in prepared] if self.feed_prev_depth else None
+        force = getattr(self, "_force_eager", False)
+        self._train_keep_fp32, self._force_eager = True, True        # (as p_losses: the backward reads the step's fp32 intermediates)
+        try:
+            pred = self._apply_model_scenes(noisy, conds, ts, prev, torch.cat([d[2] for d in draws]), torch.cat([d[3] for d in draws]))
+        finally:
+            self._train_keep_fp32, self._force_eager = False, force
+        if self.objective == "noise":
+            target = torch.cat([d[1] for d in draws])
+        elif self.objective == "x_start":
+            target = torch.cat([pr[0] for pr in prepared])
+        else:
+            raise AssertionError(f"objective {self.objective} not implemented")
+        assert self.loss_type == "l2", "loss_type 'l2' is the only one the reference implements (:86-87)"
+        loss = torch.nn.functional.mse_loss(target, pred).mean()
+        if _aux is not None:
+            _aux.update(pred=pred, target=target)
+        return loss
+
+    def _apply_model_scenes(self, noisy, conds, ts, prev_depth, depth_noise, drop_rand):
+        """apply_model (cfg 1) for N scenes with a timestep per scene on the N-scene engine: noisy (N*V, 5, S, S), ts N ints, prev_depth None
+        or one (1, 1, S, S) map per scene, depth_noise (N*V, D, S, S), drop_rand (N*V,).  Returns eps (N*V, 5, S, S)."""
+        N = len(conds)
+        NV, _, S, _ = noisy.shape
+        V = NV // N
+        D = self.view_attn.n_pts_per_ray
+        eng = self.engine(V, S, D, False, scenes=N)
+        eng.set_conditioning_scenes(conds)
+        rows = []
+        for tv in ts:
+            sac = self.scheduler.sqrt_alphas_cumprod[tv]
+            dstd = self.scheduler.sqrt_one_minus_alphas_cumprod[tv] / sac / 10.0
+            rows.append([float(tv), float(sac), float(dstd), 1.0, 1.0, 0.0, 0.0, 0.0])
+        eng.set_schedule_scenes(torch.tensor(rows, dtype=torch.float32), depth_noise.reshape(1, NV, D, S, S))
+        eng.x.copy_(noisy)
+        eng.depth_mode = 0
+        if prev_depth is not None:
+            for n, pd in enumerate(prev_depth):
+                eng.prev[n * V:(n + 1) * V, 4:5].copy_(pd.to(eng.prev.device).expand(V, 1, S, S))
+            eng.depth_mode = 2
+        eng.drop_masks = None
+        if self.drop_conditions and (self.training or self.reference_eval_dropout):
+            r = drop_rand.to(noisy.device).float()
+            drop_clip, drop_vol = (r > 0.15) & (r <= 0.2), (r > 0.1) & (r <= 0.15)          # get_drop_scheme 'default' (unet.py:109-117)
+            drop_cat, drop_all = (r > 0.05) & (r <= 0.1), r <= 0.05
+            eng.drop_masks = tuple(1.0 - (dm | drop_all).float() for dm in (drop_clip, drop_vol, drop_cat))
+        self._last_drop_masks = eng.drop_masks
+        self._train_engine = eng
+        keep = eng.ctx.keep_fp32
+        eng.ctx.keep_fp32 = True
+        try:
+            eng.step(1.0, do_update=False, use_graph=False)
+        finally:
+            eng.ctx.keep_fp32 = keep
+            eng.drop_masks = None
+        return hip.check_finite(eng.eps.clone(), "ViewFusion.p_losses_scenes")
+
+    def _loss(self, batch, trainer_config, noise_source=None, _aux=None):
+        """p_losses for one batch dict, p_losses_scenes for a list of them."""
+        if isinstance(batch, (list, tuple)):
+            return self.p_losses_scenes(batch, trainer_config, noise_source=noise_source, _aux=_aux)
+        return self.p_losses(batch, trainer_config, noise_source=noise_source, _aux=_aux)
+
+    @torch.no_grad()
+    def gradients_scenes(self, batches, trainer_config, noise_source=None, only_trainable=False):
+        """`gradients` of an N-scene training step (p_losses_scenes): (loss = the mean of the N single-scene losses, {state_dict key:
+        gradient} = the mean of the N single-scene gradients), from one batched forward and backward."""
+        if not isinstance(batches, (list, tuple)):
+            raise TypeError("gradients_scenes takes a list of batch dicts (gradients takes one)")
+        return self.gradients(list(batches), trainer_config, noise_source=noise_source, only_trainable=only_trainable)
+
     @torch.no_grad()
     def unet_gradients(self, batch, trainer_config, noise_source=None, only_trainable=False):
         """`loss.backward()` (train.py:90-95) through the WHOLE UNet and the per-step vector paths on the HIP backward kernels
@@ -614,13 +773,14 @@ class ViewFusion(nn.Module):
             record = unet._record
         finally:
             unet._record, self._force_eager = None, False
-        V, mc, S, _ = dh.shape
+        V, mc, S, _ = dh.shape                     # (V = all N*V views of an N-scene step)
         D = self.view_attn.n_pts_per_ray
-        eng = self.engine(V, S, D, False)
+        eng = self._train_engine
         ctx = eng.ctx
         M = V * S * S
-        emb = ctx.ws.get("temb.emb", (1, unet.model_channels * 4))
-        t_sin = ctx.ws.get("vf.tsin_unet", (1, unet.model_channels))
+        R = eng.t_rows
+        emb = ctx.ws.get("temb.emb", (R, unet.model_channels * 4))
+        t_sin = ctx.ws.get("vf.tsin_unet", (R, unet.model_channels))
         tape = bb.Tape(dh.device, prec=ctx.prec, workspace=ctx.gemm_ws, only_trainable=only_trainable)
         dh_rows = dh.permute(0, 2, 3, 1).reshape(M, mc).contiguous()
         context = eng.context[:V].clone()
@@ -656,14 +816,14 @@ class ViewFusion(nn.Module):
         from . import backward_blocks as bb
         from . import backward_gridattn as bg
         loss, grads, dvol = self.unet_gradients(batch, trainer_config, noise_source=noise_source, only_trainable=only_trainable)
-        V, S, _, D, _ = dvol.shape
-        eng = self.engine(V, S, D, False)
+        B, S, _, D, _ = dvol.shape                 # (B = N*V views)
+        eng = self._train_engine
         ctx = eng.ctx
         tape = bb.Tape(dvol.device, prec=ctx.prec, workspace=ctx.gemm_ws, only_trainable=only_trainable)
-        c = ctx.ws.get("vf.c", (1, 256))
-        g, dc = bg.gridattn_backward(self.view_attn, tape, eng, c, dvol.reshape(V * S * S * D, -1).contiguous(), V, S, D)
+        c = ctx.ws.get("vf.c", (eng.t_rows, 256))
+        g, dc = bg.gridattn_backward(self.view_attn, tape, eng, c, dvol.reshape(B * S * S * D, -1).contiguous(), eng.V, S, D)
         grads.update({"view_attn." + k: v for k, v in g.items()})
-        t_sin = ctx.ws.get("vf.tsin", (1, 256))
+        t_sin = ctx.ws.get("vf.tsin", (eng.t_rows, 256))
         grads.update({"time_embed." + k: v for k, v in bg.time_embed_backward(self.time_embed, t_sin, dc).items()})
         return loss, grads
 
@@ -700,13 +860,13 @@ class ViewFusion(nn.Module):
         backward currently stops: LayerNorm / attention / GEGLU backward do not exist yet)."""
         from . import backward
         aux = {}
-        loss = self.p_losses(batch, trainer_config, noise_source=noise_source, _aux=aux)
+        loss = self._loss(batch, trainer_config, noise_source=noise_source, _aux=aux)
         unet = self.unet_model.unet_model
         pred, target = aux["pred"], aux["target"]
         V, C, S, _ = pred.shape
         h, a = unet._head_saved
         rows = lambda t: t.permute(0, 2, 3, 1).reshape(V * S * S, C).contiguous()
-        eng = self.engine(V, S, self.view_attn.n_pts_per_ray, False)
+        eng = self._train_engine
         grads, dh = backward.unet_head_backward(unet, h, a, rows(pred), rows(target), V, S, eng.ctx.gemm_ws)
         grads = {"unet_model.unet_model." + k: v for k, v in grads.items()}
         return loss, grads, dh.view(V, S, S, -1).permute(0, 3, 1, 2).contiguous()
@@ -716,12 +876,14 @@ class ViewFusion(nn.Module):
         scalar carries a graph node whose backward hands the HIP-computed gradients (self.gradients) to the parameters, so the
         reference's loop ``loss = model(batch, cfg); optimizer.zero_grad(); loss.backward(); optimizer.step()`` (train.py:86-95) runs
         unchanged -- under torch's DistributedDataParallel too: the parameters are inputs of that node, so DDP's gradient hooks fire and
-        all-reduce over RCCL as usual.  Without autograd (torch.no_grad / eval): the plain loss value."""
+        all-reduce over RCCL as usual.  Without autograd (torch.no_grad / eval): the plain loss value.
+        ``batch`` may also be a LIST of batch dicts: one multi-scene step (p_losses_scenes / gradients_scenes) whose loss and gradients are
+        the means over the scenes -- the reference's scene_batch_size > 1."""
         # (view_attn.t_embedder exists in the reference's module tree but its forward never calls it: those parameters stay outside
         #  the graph, exactly like the reference -- DDP(find_unused_parameters=True) treats them as unused)
         params = [(n, p) for n, p in self.named_parameters() if p.requires_grad and not n.startswith("view_attn.t_embedder.")]
         if not torch.is_grad_enabled() or not params:
-            return self.p_losses(batch, trainer_config, noise_source=getattr(self, "_noise_source", None))
+            return self._loss(batch, trainer_config, noise_source=getattr(self, "_noise_source", None))
         return _HipTrainingLoss.apply(self, batch, trainer_config, tuple(n for n, _ in params), *[p for _, p in params])
 
     def configure_optimizers(self, lr=None, verbose=False):

@@ -2,8 +2,9 @@
 the reference's loop ``loss = model(batch, cfg); optimizer.zero_grad(); loss.backward(); optimizer.step()`` on the HIP forward
 and the hand-written backward kernels (mvdfusion_amd/backward*.py), full-width SD1.x UNet, synthetic prepared batch.
 
-    python tools/bench_train.py [--views 8] [--depth-samples 3] [--steps 3] [--width 320]
-Prints one JSON line (not the headline metric: bench.py measures denoising steps/s).
+    python tools/bench_train.py [--views 8] [--depth-samples 3] [--steps 3] [--width 320] [--scenes N]
+--scenes N feeds N scenes (own cameras, latents and draws) to every step: model([batch_0 .. batch_N-1], cfg), one batched forward and
+backward with a timestep per scene.  Prints one JSON line (not the headline metric: bench.py measures denoising steps/s).
 """
 import argparse
 import json
@@ -22,6 +23,7 @@ def main():
     ap.add_argument("--depth-samples", type=int, default=3)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--width", type=int, default=320)
+    ap.add_argument("--scenes", type=int, default=1, help="scenes per training step (ViewFusion.forward on a list of batches)")
     ap.add_argument("--frozen-unet", action="store_true", help="finetune_unet: false (only the cross-attention / view-aligned parameters train); "
                     "default = configs/mvd_train.yaml:15 finetune_unet: true (all 1 039 M parameters)")
     ap.add_argument("--tuned", default=None, help="tuner cache file (hip.save_tuned / load_tuned): loaded when present, written after the first step -- "
@@ -44,10 +46,15 @@ def main():
     for n, p in m.named_parameters():
         if n.startswith(("vae.", "clip_image_encoder.")):
             p.requires_grad_(False)
-    inp = syn.make_inputs(V, S, seed=0)
-    g = torch.Generator().manual_seed(5)
-    lat = torch.randn(V, 5, S, S, generator=g).cuda()
-    batch = {"_prepared": (lat, inp["batch_cameras"], inp["input_latents"].cuda(), inp["input_cameras"], inp["clip_v_embed"].cuda())}
+    if a.scenes < 1:
+        ap.error("--scenes must be >= 1")
+    batches = []
+    for n in range(a.scenes):
+        inp = syn.make_inputs(V, S, seed=n)
+        g = torch.Generator().manual_seed(5 + n)
+        lat = torch.randn(V, 5, S, S, generator=g).cuda()
+        batches.append({"_prepared": (lat, inp["batch_cameras"], inp["input_latents"].cuda(), inp["input_cameras"], inp["clip_v_embed"].cuda())})
+    batch = batches[0] if a.scenes == 1 else batches
     opt = m.configure_optimizers(lr=1e-5)
     n_train = sum(p.numel() for p in m.parameters() if p.requires_grad)
     times, losses = [], []
@@ -90,7 +97,10 @@ def main():
     T = V * V * S * S * D
     f_fwd = V * f_unet + T * (3516416 + 3072 * V) + V * S * S * D * 393216 + (V + 1) * S * S * 2560
     flops = 4.0 * f_fwd
-    print(json.dumps({"metric": "training-steps/sec (fwd + bwd + AdamW, one scene)", "value": 1.0 / dt, "unit": "steps/s", "s_per_step": dt, "step_s": [round(t, 4) for t in times[1:]], "first_step_s": times[0],
+    flops *= a.scenes
+    print(json.dumps({"metric": "training-steps/sec (fwd + bwd + AdamW, " + ("one scene)" if a.scenes == 1 else f"{a.scenes} scenes per step)"),
+                      "value": 1.0 / dt, "unit": "steps/s", "s_per_step": dt, "scenes": a.scenes, "scene_steps_per_s": a.scenes / dt,
+                      "step_s": [round(t, 4) for t in times[1:]], "first_step_s": times[0],
                       "roofline": {"bound": "mfma", "achieved": flops / dt / 1e12, "peak": 2500.0, "unit": "TFLOP/s", "frac": flops / dt / 2.5e15,
                                    "traffic": None, "algorithmic_tflop_per_step": flops / 1e12,
                                    "note": "whole step (fwd + recompute + dgrad + wgrad) against the dense 16-bit MFMA peak; the step is "
