@@ -95,8 +95,8 @@ def _c(t):
 
 
 def resblock_backward(tape, rb, x, emb, dout, B, H, W):
-    """ResBlock (openaimodel.py:255-275; no scale-shift norm, dropout 0).  x (M, Cin) fp32 block input, emb (1, ted) the shared
-    time embedding -- or (R, ted): one per scene, each for M / R scene-major rows --, dout (M, Cout).  Returns (dx, {name: grad}, demb (R, ted))."""
+    """ResBlock (openaimodel.py:255-275; no scale-shift norm, dropout 0).  x (M, Cin) fp32 block input, emb (R, ted) the time embedding
+    (one per scene with per-scene timesteps, each for M / R scene-major rows), dout (M, Cout).  Returns (dx, {name: grad}, demb (R, ted))."""
     gn1, conv1 = rb.in_layers[0], rb.in_layers[2]
     gn2, conv2 = rb.out_layers[0], rb.out_layers[3]
     lin_e = rb.emb_layers[1]
@@ -104,10 +104,11 @@ def resblock_backward(tape, rb, x, emb, dout, B, H, W):
     HW = H * W
     # ---- forward (unfused)
     a1 = tape.groupnorm(x, gn1, B, HW, True)
-    se = torch.nn.functional.silu(emb)                                     # (1, ted)   host glue
+    se = torch.nn.functional.silu(emb)                                     # (R, ted)   host glue
     e = se @ lin_e.weight.t() + lin_e.bias                                 # (R, Co)
     R = emb.shape[0]
-    if R == 1:
+    shared = R == 1            # one time embedding for every row: folded into conv1's bias (and its gradient is conv1's bias gradient)
+    if shared:
         h1 = tape.conv3x3(a1, conv1.weight, conv1.bias + e[0], B, H, W)
     else:                                                                   # a time-embedding row per scene: added to its rows
         h1 = tape.conv3x3(a1, conv1.weight, conv1.bias, B, H, W)
@@ -124,15 +125,10 @@ def resblock_backward(tape, rb, x, emb, dout, B, H, W):
         db1 = bw.col_sum(_c(dh1), B * HW, Co)                               # time-embedding vector (always needed)
     g["in_layers.2.bias"] = db1
     # the time-embedding vector is added per channel to every row: its gradient is the same column sum (per scene: over the scene's rows)
-    if R == 1:
-        g["emb_layers.1.bias"] = db1.clone()
-        g["emb_layers.1.weight"] = torch.outer(db1, se[0])
-        demb = (db1[None, :] @ lin_e.weight) * (torch.sigmoid(emb) * (1 + emb * (1 - torch.sigmoid(emb))))
-    else:
-        dbs = bw.col_sum_groups(_c(dh1), R)                                 # (R, Co)
-        g["emb_layers.1.bias"] = dbs.sum(0)
-        g["emb_layers.1.weight"] = dbs.t() @ se
-        demb = (dbs @ lin_e.weight) * (torch.sigmoid(emb) * (1 + emb * (1 - torch.sigmoid(emb))))
+    dbs = db1[None, :] if shared else bw.col_sum_groups(_c(dh1), R)         # (R, Co)
+    g["emb_layers.1.bias"] = dbs.sum(0)
+    g["emb_layers.1.weight"] = torch.outer(db1, se[0]) if shared else dbs.t() @ se
+    demb = (dbs @ lin_e.weight) * (torch.sigmoid(emb) * (1 + emb * (1 - torch.sigmoid(emb))))
     dx, g["in_layers.0.weight"], g["in_layers.0.bias"] = bw.groupnorm_backward(_c(x), _c(da1), gn1.weight, gn1.bias, B, HW, Ci, gn1.eps, True)
     if has_skip:
         sk = rb.skip_connection

@@ -32,41 +32,28 @@ def _silu_grad(z):
 
 
 def _modulation(blk, c):
-    """(SiLU(c), the six adaLN vectors): (C,) each for one conditioning row, (R, C) views of the (R, 6C) modulation for one row per scene."""
+    """(SiLU(c), the six adaLN vectors): (R, C) views of the (R, 6C) modulation, one row per conditioning row c (R, C)."""
     C = blk.hidden_size
     lin = blk.adaLN_modulation[1]
     sc_ = F.silu(c)
     mod = sc_ @ lin.weight.t() + lin.bias                                    # (R, 6C)   host glue
-    if c.shape[0] == 1:
-        return sc_, [mod[0, i * C:(i + 1) * C].contiguous() for i in range(6)]
     return sc_, [mod[:, i * C:(i + 1) * C] for i in range(6)]
 
 
 def _ln_modulate(h, out, scale, shift, T, C):
     """LayerNorm(h) * (1 + scale) + shift; scale / shift (R, C) apply to R equal scene-major row groups (mvd_layernorm_groups)."""
-    if scale.dim() == 1:
-        return hip.layernorm(h, out, scale, shift, T, C, eps=1e-6, w_plus_one=True)
     return hip.layernorm_groups(h, out, scale, shift, T, C, T // scale.shape[0], eps=1e-6, w_plus_one=True)
 
 
 def _gate(g, x):
-    """g * x with the gate g (C,) shared by every row, or (R, C): one row per scene over R equal scene-major row groups of x (rows, C)."""
-    if g.dim() == 1:
-        return g * x
+    """g * x with the gate g (R, C): one row per R equal scene-major row groups of x (rows, C)."""
     R, C = g.shape
     return (x.reshape(R, -1, C) * g[:, None, :]).reshape(x.shape)
 
 
-def _col_sums(x, R, T, C):
-    """Column sums of x (T, C): (C,) for one conditioning row, (R, C) per scene row group."""
-    if R == 1:
-        return bw.col_sum(x.contiguous(), T, C)
-    return bw.col_sum_groups(x.contiguous(), R)
-
-
 def _dit_block_backward(tape, blk, h, c, dh2, T, V):
-    """One DiTBlock (view_attn_efficient2.py:42-67).  h (T, C) block input, c (1, C) conditioning -- or (R, C): one row per scene, each
-    conditioning T / R scene-major rows --, dh2 gradient at the block output.  Returns (dh, {name: grad}, dc (R, C))."""
+    """One DiTBlock (view_attn_efficient2.py:42-67).  h (T, C) block input, c (R, C) conditioning (one row per scene with per-scene
+    timesteps, each conditioning T / R scene-major rows), dh2 gradient at the block output.  Returns (dh, {name: grad}, dc (R, C))."""
     C, H = blk.hidden_size, blk.num_heads
     R = c.shape[0]
     dh_ = C // H
@@ -88,30 +75,20 @@ def _dit_block_backward(tape, blk, h, c, dh2, T, V):
     f2 = tape.linear(gel, blk.mlp.fc2.weight, blk.mlp.fc2.bias)
     # ---- backward
     g = {}
-    dg2 = _col_sums(dh2 * f2, R, T, C)
+    dg2 = bw.col_sum_groups(dh2 * f2, R)
     dgel, g["mlp.fc2.weight"], g["mlp.fc2.bias"] = tape.linear_bwd(gel, blk.mlp.fc2.weight, _gate(g2, dh2))
     dm2, g["mlp.fc1.weight"], g["mlp.fc1.bias"] = tape.linear_bwd(m2, blk.mlp.fc1.weight, bw.act_backward(dgel, f1, hip.ACT_GELU))
-    if R == 1:
-        dx, ds2, dsh2 = bw.layernorm_backward(h1.contiguous(), dm2.contiguous(), (1.0 + s2).contiguous(), 1e-6)
-    else:
-        dx, ds2, dsh2 = bw.layernorm_backward_groups(h1.contiguous(), dm2.contiguous(), (1.0 + s2).contiguous(), 1e-6, R)
+    dx, ds2, dsh2 = bw.layernorm_backward_groups(h1.contiguous(), dm2.contiguous(), (1.0 + s2).contiguous(), 1e-6, R)
     dh1 = dh2 + dx
-    dg1 = _col_sums(dh1 * a_out, R, T, C)
+    dg1 = bw.col_sum_groups(dh1 * a_out, R)
     datt, g["attn.proj.weight"], g["attn.proj.bias"] = tape.linear_bwd(att, blk.attn.proj.weight, _gate(g1, dh1))
     q, k, v = (qkv[:, i * C:(i + 1) * C].contiguous() for i in range(3))
     dq, dk, dv = bw.attention_backward(q, k, v, datt.contiguous(), T // V, H, V, dh_)
     dm1, g["attn.qkv.weight"], g["attn.qkv.bias"] = tape.linear_bwd(m1, blk.attn.qkv.weight, torch.cat([dq, dk, dv], dim=1))
-    if R == 1:
-        dx, ds1, dsh1 = bw.layernorm_backward(h.contiguous(), dm1.contiguous(), (1.0 + s1).contiguous(), 1e-6)
-    else:
-        dx, ds1, dsh1 = bw.layernorm_backward_groups(h.contiguous(), dm1.contiguous(), (1.0 + s1).contiguous(), 1e-6, R)
+    dx, ds1, dsh1 = bw.layernorm_backward_groups(h.contiguous(), dm1.contiguous(), (1.0 + s1).contiguous(), 1e-6, R)
     dh = dh1 + dx
-    if R == 1:
-        dmod = torch.cat([dsh1, ds1, dg1, dsh2, ds2, dg2])[None, :]           # (1, 6C)
-        g["adaLN_modulation.1.bias"] = dmod[0].clone()
-    else:
-        dmod = torch.cat([dsh1, ds1, dg1, dsh2, ds2, dg2], dim=1)            # (R, 6C): one row per scene
-        g["adaLN_modulation.1.bias"] = dmod.sum(0)
+    dmod = torch.cat([dsh1, ds1, dg1, dsh2, ds2, dg2], dim=1)                # (R, 6C): one row per scene
+    g["adaLN_modulation.1.bias"] = dmod.sum(0)
     g["adaLN_modulation.1.weight"] = dmod.t() @ sc_
     dc = (dmod @ lin.weight) * _silu_grad(c)
     return dh, g, dc
@@ -119,9 +96,8 @@ def _dit_block_backward(tape, blk, h, c, dh2, T, V):
 
 def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     """ga: GridAttn; eng: the StepEngine whose buffers hold this step's inputs (x, depth noise, step table, cameras, input latents);
-    c (1, 256) conditioning; dvol (V*S*S*D, 768) gradient of the frustum.  Returns ({view_attn-relative name: grad}, dc (1, 256)).
-    An engine of N scenes: its N*V views scene-major, dvol (N*V*S*S*D, 768); with per-scene timesteps (eng.steps_scene_stride) c and dc
-    are (N, 256), one row per scene."""
+    c (R, 256) conditioning (eng.t_rows: N rows with per-scene timesteps, else 1); dvol (N*V*S*S*D, 768) gradient of the frustum of the
+    engine's N*V views, scene-major.  Returns ({view_attn-relative name: grad}, dc (R, 256))."""
     L = hip.lib()
     dev = dvol.device
     C = ga.hidden_size
@@ -140,12 +116,8 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     tokens = hip.planes_like(T, hip.TOKEN_LD, dev)
     dsrc, dsteps = eng.depth_geo()          # (the depth source the forward used: x itself, or an overwrite_attn_depth map)
     geo = (hip.ptr(dsrc), hip.ptr(eng.depth_noise), hip.ptr(dsteps), hip.ptr(eng.iter), hip.ptr(grid_lin))
-    if N == 1:
-        hip.check(L.mvd_gridattn_tokens(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens), V, 0,
-                                        V, S, D, float(ga.depth_scale), float(ga.depth_shift), hip.stream()))
-    else:
-        hip.check(L.mvd_gridattn_tokens_scenes_t(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens),
-                                                 N, V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift), sst, hip.stream()))
+    hip.check(L.mvd_gridattn_tokens_scenes_t(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens),
+                                             N, V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift), sst, hip.stream()))
     pre = ga.pre_layer_b[0]
     z0 = tape.linear(tokens, pre.weight, pre.bias)                             # (T, 256) pre-activation
     hs = [bw.act_planes(z0, hip.ACT_GELU, planes=False, f32=True)[1]]
@@ -182,14 +154,9 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     scale = 2.0 ** (40 - math.floor(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 1.0
     dfeat_acc = torch.zeros(N * V, S, S, 256, dtype=torch.int64, device=dev)
     din_acc = torch.zeros(N, S, S, 256, dtype=torch.int64, device=dev)
-    if N == 1:
-        hip.check(L.mvd_gridattn_tokens_backward(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
-                                                 hip.ptr(din_acc), float(scale), V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift),
-                                                 hip.stream()))
-    else:
-        hip.check(L.mvd_gridattn_tokens_backward_scenes(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
-                                                        hip.ptr(din_acc), float(scale), N, V, 0, V, S, D, float(ga.depth_scale),
-                                                        float(ga.depth_shift), sst, hip.stream()))
+    hip.check(L.mvd_gridattn_tokens_backward_scenes(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
+                                                    hip.ptr(din_acc), float(scale), N, V, 0, V, S, D, float(ga.depth_scale),
+                                                    float(ga.depth_shift), sst, hip.stream()))
     dW = torch.zeros_like(z.weight)
     db = torch.zeros_like(z.bias)
     for lat, acc, n in ((eng.x, dfeat_acc, N * V), (eng.input_latents, din_acc, N)):
@@ -203,8 +170,7 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
 
 
 def _dit_forward(tape, blk, h, c, T, V):
-    """Unfused DiTBlock forward returning the block output (same algebra as _dit_block_backward's forward half); c (1, C) or (R, C) per
-    scene."""
+    """Unfused DiTBlock forward returning the block output (same algebra as _dit_block_backward's forward half); c (R, C)."""
     C, H = blk.hidden_size, blk.num_heads
     _, (sh1, s1, g1, sh2, s2, g2) = _modulation(blk, c)
     dev = h.device
@@ -213,16 +179,18 @@ def _dit_forward(tape, blk, h, c, T, V):
     qkv = tape.linear(m1, blk.attn.qkv.weight, blk.attn.qkv.bias)
     att = hip.planes_like(T, C, dev)
     hip.check(hip.lib().mvd_view_mha(hip.ptr(qkv), hip.ptr(att), T // V, V, H, C // H, hip.stream()))
-    if c.shape[0] == 1:
-        h1 = tape.linear(att, blk.attn.proj.weight, blk.attn.proj.bias, res=h, colscale=g1)    # h + g1 * proj(att): the GEMM's own epilogue
-    else:                                                                                       # (the epilogue's gate is one row: per scene
-        h1 = h + _gate(g1, tape.linear(att, blk.attn.proj.weight, blk.attn.proj.bias))           #  it is elementwise glue)
+    h1 = _gated_residual(tape, att, blk.attn.proj, h, g1)
     m2 = hip.planes_like(T, C, dev)
     _ln_modulate(h1, m2, s2, sh2, T, C)
     f1 = tape.linear(m2, blk.mlp.fc1.weight, blk.mlp.fc1.bias)
-    if c.shape[0] == 1:
-        return tape.linear(bw.act_planes(f1, hip.ACT_GELU)[0], blk.mlp.fc2.weight, blk.mlp.fc2.bias, res=h1, colscale=g2)
-    return h1 + _gate(g2, tape.linear(bw.act_planes(f1, hip.ACT_GELU)[0], blk.mlp.fc2.weight, blk.mlp.fc2.bias))
+    return _gated_residual(tape, bw.act_planes(f1, hip.ACT_GELU)[0], blk.mlp.fc2, h1, g2)
+
+
+def _gated_residual(tape, a, lin, res, g):
+    """res + g * lin(a).  A gate shared by every row (g (1, C)) is the GEMM's own epilogue; one gate row per scene is elementwise glue."""
+    if g.shape[0] == 1:
+        return tape.linear(a, lin.weight, lin.bias, res=res, colscale=g[0])
+    return res + _gate(g, tape.linear(a, lin.weight, lin.bias))
 
 
 def time_embed_backward(time_embed, t_sin, dc):
@@ -231,8 +199,7 @@ def time_embed_backward(time_embed, t_sin, dc):
     l1, l2 = time_embed[0], time_embed[2]
     z1 = t_sin @ l1.weight.t() + l1.bias
     e1 = F.silu(z1)
-    row_sum = (lambda t: t[0].clone()) if dc.shape[0] == 1 else (lambda t: t.sum(0))      # (one row per scene: summed over the scenes)
-    g = {"2.weight": dc.t() @ e1, "2.bias": row_sum(dc)}
+    g = {"2.weight": dc.t() @ e1, "2.bias": dc.sum(0)}                      # (one row per scene: summed over the scenes)
     dz1 = (dc @ l2.weight) * _silu_grad(z1)
-    g["0.weight"], g["0.bias"] = dz1.t() @ t_sin, row_sum(dz1)
+    g["0.weight"], g["0.bias"] = dz1.t() @ t_sin, dz1.sum(0)
     return g

@@ -59,8 +59,9 @@ def _pooled_volumes(vol, B, S, D, levels):
 
 
 def unet_backward(unet, ctx, tape, record, dh, B, S, D, emb, t_sin, context, vol):
-    """dh: gradient at the input of the output head (B*S*S, mc).  record: UNetModel._record of the forward.  emb (1, 4 mc) time
-    embedding, t_sin (1, mc) its sinusoid input (or (N, .): one row per scene, B = N * V scene-major images), context (B, 768), vol (B, S, S, D, 768) fp32 volume features (after dropout).
+    """dh: gradient at the input of the output head (B*S*S, mc).  record: UNetModel._record of the forward.  emb (R, 4 mc) time
+    embedding and t_sin (R, mc) its sinusoid input (R = N with one row per scene, B = N * V scene-major images, else 1), context (B, 768),
+    vol (B, S, S, D, 768) fp32 volume features (after dropout).
     Returns ({UNetModel-relative parameter name: gradient}, dcontext (B, 768), dvol (B, S, S, D, 768))."""
     grads = {}
     n_in = len(unet.input_blocks)
@@ -122,14 +123,13 @@ def unet_backward(unet, ctx, tape, record, dh, B, S, D, emb, t_sin, context, vol
             skip_grad[n_in - 1 - out_index[id(blk)]] = d[:, ca:].contiguous()
             d = d[:, :ca].contiguous()
     assert not skip_grad
-    # ---- time embedding MLP (unet.py:537-538; openaimodel time_embed): emb = L2(silu(L1(t_sin)))      host glue, (1 x 4 mc)
+    # ---- time embedding MLP (unet.py:537-538; openaimodel time_embed): emb = L2(silu(L1(t_sin)))      host glue, (R x 4 mc)
     l1, l2 = unet.time_embed[0], unet.time_embed[2]
     z1 = t_sin @ l1.weight.t() + l1.bias
     e1 = F.silu(z1)
-    row_sum = (lambda t: t[0].clone()) if demb.shape[0] == 1 else (lambda t: t.sum(0))      # (one row per scene: summed over the scenes)
-    grads["time_embed.2.weight"], grads["time_embed.2.bias"] = demb.t() @ e1, row_sum(demb)
+    grads["time_embed.2.weight"], grads["time_embed.2.bias"] = demb.t() @ e1, demb.sum(0)      # (one row per scene: summed over the scenes)
     dz1 = (demb @ l2.weight) * _silu_grad(z1)
-    grads["time_embed.0.weight"], grads["time_embed.0.bias"] = dz1.t() @ t_sin, row_sum(dz1)
+    grads["time_embed.0.weight"], grads["time_embed.0.bias"] = dz1.t() @ t_sin, dz1.sum(0)
     # ---- volume pyramid: area pooling backward (each fine cell receives 1 / f^2 of its coarse cell's gradient)
     dvol = torch.zeros(B, S, S, D, vol.shape[-1], dtype=torch.float32, device=vol.device)
     for h_, dv in dvols.items():

@@ -75,7 +75,7 @@ class Ctx:
         self.D = 1                  # depth samples per ray
         self.context = None         # (B, 768) projected CLIP context
         self.vol_levels = None      # list of (B*h*w*D, 768)
-        self.emb_bias = None        # dict: ResBlock -> (Cout,) slice of the per-step time-embedding biases
+        self.emb_bias = None        # dict: ResBlock -> (R, Cout) slice of the per-step time-embedding biases
         self._rot = {}
         self.capturing = False      # set by StepEngine around graph capture: no new workspace buffer may appear then
         self.gemm_ws = torch.empty(64 * 1024 * 1024, dtype=torch.float32, device=self.device)  # 256 MB split-K slabs

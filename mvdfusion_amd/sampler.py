@@ -78,39 +78,14 @@ class DDIMSampler:
     def sample(self, batch_cameras, input_latents, input_cameras, clip_embed, unconditional_scale=1.0, depth=False,
                return_intermediates=False, verbose=True, x_T=None, num_steps=None, use_graph=True):
         """Returns x_0 (V, 5, S, S) [and the per-step {'t','xt','x0'} list].  ``x_T``/``num_steps`` are extensions:
-        inject the initial noise / run only the first ``num_steps`` iterations (parity tests, bench warm-up)."""
-        assert depth, "MVD-Fusion samples RGB-D latents (depth=True at every call site: demo.py:85-90)"
-        m = self.model
-        dev = m._device.device
-        V, S, D = clip_embed.shape[0], self.latent_size, m.view_attn.n_pts_per_ray
-        total = self.ddim_timesteps.shape[0]
-        n_run = total if num_steps is None else int(num_steps)
-        cfg = unconditional_scale != 1.0
-        eng = m.engine(V, S, D, cfg)
-        eng.set_conditioning(batch_cameras, input_latents.to(dev), input_cameras, clip_embed.to(dev))
-        st, dd = self.tables()
-        table = ddim_step_table(st, dd, [total - i - 1 for i in range(total)])
-        if x_T is None:
-            x_T = torch.randn([V, self.z_dim + 1, S, S], device=dev)
-        if self.noise_source is not None:
-            dn, sn = self.noise_source(V, S, D, total)
-        else:
-            dn = torch.randn(total, V, D, S, S, device=dev)
-            sn = torch.randn(total, V, 5, S, S, device=dev)
-        eng.set_schedule(table, dn, sn)
-        eng.x.copy_(x_T)
-        inter = []
-        for i in range(n_run):
-            # feed_prev_depth (:135-140): from the second iteration on GridAttn samples depth around the previous step's x0 estimate, which
-            # the step engine keeps in eng.x0 (a second captured graph; the first iteration has no estimate yet)
-            eng.depth_mode = 1 if (self.feed_prev_depth and i > 0) else 0
-            eng.step(unconditional_scale, do_update=True, use_graph=use_graph)
-            if return_intermediates:
-                inter.append({"t": int(self.ddim_timesteps[total - i - 1]), "xt": eng.x.clone(), "x0": eng.x0.clone()})
-        eng.depth_mode = 0
-        from . import hip
-        out = hip.check_finite(eng.x.clone(), "DDIMSampler.sample")
-        return (out, inter) if return_intermediates else out
+        inject the initial noise / run only the first ``num_steps`` iterations (parity tests, bench warm-up).  One scene of
+        ``sample_scenes``."""
+        res = self._sample([(batch_cameras, input_latents, input_cameras, clip_embed)], unconditional_scale, depth,
+                           return_intermediates, None if x_T is None else x_T.reshape(1, *x_T.shape), num_steps, use_graph)
+        if not return_intermediates:
+            return res[0]
+        x, inter = res
+        return x[0], [{"t": it["t"], "xt": it["xt"][0], "x0": it["x0"][0]} for it in inter]
 
     @torch.no_grad()
     def sample_scenes(self, conds, unconditional_scale, depth=True, return_intermediates=False, verbose=True, x_T=None,
@@ -120,6 +95,10 @@ class DDIMSampler:
         N V conditional rows scene-major, then the N V null rows) and the update once for all scenes.  Returns x_0 (N, V, 5, S, S)
         [and the per-step {'t','xt','x0'} list with (N, V, 5, S, S) tensors].  ``x_T``: (N, V, 5, S, S) initial noise.
         ``noise_source`` is called once per scene, in scene order, exactly as ``sample`` calls it for that scene alone."""
+        return self._sample(conds, unconditional_scale, depth, return_intermediates, x_T, num_steps, use_graph)
+
+    def _sample(self, conds, unconditional_scale, depth, return_intermediates, x_T, num_steps, use_graph):
+        """The DDIM loop of ``sample`` (one scene) and ``sample_scenes``."""
         assert depth, "MVD-Fusion samples RGB-D latents (depth=True at every call site: demo.py:85-90)"
         m = self.model
         N = len(conds)
@@ -154,6 +133,8 @@ class DDIMSampler:
         eng.x.copy_(x_T)
         inter = []
         for i in range(n_run):
+            # feed_prev_depth (:135-140): from the second iteration on GridAttn samples depth around the previous step's x0 estimate, which
+            # the step engine keeps in eng.x0 (a second captured graph; the first iteration has no estimate yet)
             eng.depth_mode = 1 if (self.feed_prev_depth and i > 0) else 0
             eng.step(unconditional_scale, do_update=True, use_graph=use_graph)
             if return_intermediates:
@@ -161,5 +142,5 @@ class DDIMSampler:
                               "x0": eng.x0.clone().view(N, V, 5, S, S)})
         eng.depth_mode = 0
         from . import hip
-        out = hip.check_finite(eng.x.clone(), "DDIMSampler.sample_scenes").view(N, V, 5, S, S)
+        out = hip.check_finite(eng.x.clone(), "DDIMSampler.sample").view(N, V, 5, S, S)
         return (out, inter) if return_intermediates else out

@@ -107,8 +107,8 @@ class ResBlock(TimestepBlock):
         # conv bias + Linear(SiLU(emb)) are folded into one per-step bias vector (UNetModel._time_biases)
         a2 = ctx.ws.planes("res.a2", M, Co)
         # GroupNorm + SiLU of h right behind the convolution (inside its split-K reduce when it splits); h itself has no other reader
-        eb = ctx.emb_bias[self]             # (Cout,) shared by every row, or (N, Cout): one row per scene (scene-major rows, M / N each)
-        ctx.gemm(a, w1, h, conv=dict(Cin=Ci, **geo), bias=False, bias_b=eb, rows_per_batch=M if eb.dim() == 1 else M // eb.shape[0],
+        eb = ctx.emb_bias[self]             # (R, Cout): one row per time-conditioning row, each for M / R scene-major rows
+        ctx.gemm(a, w1, h, conv=dict(Cin=Ci, **geo), bias=False, bias_b=eb, rows_per_batch=M // eb.shape[0],
                  gn=(B, H * W), kind="conv",
                  gn_apply=(self.out_layers[0], a2, True, True))
         skip = x
@@ -267,24 +267,16 @@ class UNetModel(nn.Module):
             for b in blocks:
                 offs[b] = (o, o + b.out_channels)
                 o += b.out_channels
-            self._temb = (w, bias, offs, torch.empty(1, o, dtype=torch.float32, device=w.device))
-        w, bias, offs, out = self._temb
+            self._temb = (w, bias, offs)
+        w, bias, offs = self._temb
         ted = self.model_channels * 4
-        R = t_sin.shape[0]
-        if R > 1:           # one timestep per scene (training): an (N, total) bias table, row n for the rows of scene n
-            e1, emb = ctx.ws.get("temb.e1", (R, ted)), ctx.ws.get("temb.emb", (R, ted))
-            out = ctx.ws.get("temb.bias", (R, out.shape[1]))
-            ctx.gemv_rows(self.time_embed[0].weight, self.time_embed[0].bias, t_sin, e1, act_out=hip.ACT_SILU)
-            ctx.gemv_rows(self.time_embed[2].weight, self.time_embed[2].bias, e1, emb)
-            ctx.gemv_rows(w, bias, emb, out, act_in=hip.ACT_SILU)
-            ctx.emb_bias = {b: out[:, lo:hi] for b, (lo, hi) in offs.items()}
-            return
-        e1 = ctx.ws.get("temb.e1", (1, ted))
-        hip.gemv(self.time_embed[0].weight, self.time_embed[0].bias, t_sin, e1, act_out=hip.ACT_SILU)
-        emb = ctx.ws.get("temb.emb", (1, ted))
-        hip.gemv(self.time_embed[2].weight, self.time_embed[2].bias, e1, emb)
-        hip.gemv(w, bias, emb, out, act_in=hip.ACT_SILU)
-        ctx.emb_bias = {b: out[0, lo:hi] for b, (lo, hi) in offs.items()}
+        R = t_sin.shape[0]        # one row per scene with per-scene timesteps (training): row n biases the rows of scene n
+        e1, emb = ctx.ws.get("temb.e1", (R, ted)), ctx.ws.get("temb.emb", (R, ted))
+        out = ctx.ws.get("temb.bias", (R, w.shape[0]))
+        ctx.gemv_rows(self.time_embed[0].weight, self.time_embed[0].bias, t_sin, e1, act_out=hip.ACT_SILU)
+        ctx.gemv_rows(self.time_embed[2].weight, self.time_embed[2].bias, e1, emb)
+        ctx.gemv_rows(w, bias, emb, out, act_in=hip.ACT_SILU)
+        ctx.emb_bias = {b: out[:, lo:hi] for b, (lo, hi) in offs.items()}
 
     def cross_attn_vectors(self, ctx):
         """attn2 of every SpatialTransformer sees the length-1 CLIP context: softmax over one key is 1, so its output is

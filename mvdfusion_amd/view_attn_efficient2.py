@@ -285,39 +285,28 @@ class GridAttn(nn.Module):
                 raise NotImplementedError(f"GridAttn.run: per-scene timesteps need the fused aggregation kernel (V={V}, T={T // N} per scene); "
                                           "the unfused chain shares one adaLN modulation")
             fused = True
-        if fused and sst:
-            stream, vecs1 = self.packed_fused(ctx.device)
-            nv = vecs1.numel()
-            vecs = ctx.ws.get("ga.vecs_scenes", (N, nv))
-            vecs.copy_(vecs1.view(1, nv).expand(N, nv))          # biases / scales per scene, then each scene's adaLN modulation
-            for bi, blk in enumerate(self.aggregation_transformer.layer_list):
+        if fused:
+            assert self.fused_supported(V, T // N), (V, T // N)
+            stream, vecs = self.packed_fused(ctx.device)
+            nv = vecs.numel()
+            vecs = vecs.view(1, nv)
+            if sst:            # one vector table per scene: the shared biases / scales, then each scene's adaLN modulation
+                vecs = ctx.ws.get("ga.vecs_scenes", (N, nv)).copy_(vecs.expand(N, nv))
+            for bi, blk in enumerate(self.aggregation_transformer.layer_list):      # adaLN modulation of this step -> vecs
                 lin = blk.adaLN_modulation[1]
                 ctx.gemv_rows(lin.weight, lin.bias, c, vecs[:, bi * _G4_VEC_BLOCK:bi * _G4_VEC_BLOCK + 1536], act_in=hip.ACT_SILU)
             pool = ctx.ws.planes("ga.pool", nseq, self.hidden_size)
             hip.check(L.mvd_gridattn_fused_scenes_t(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
                                                     hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec), hip.ptr(stream),
                                                     hip.ptr(vecs), hip.ptr(pool), N, V, q0, Vq, S, D, float(self.depth_scale),
-                                                    float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, sst, nv, hip.stream()))
-            ctx.gemm(pool, w_fin, vol_out, M=nseq, out_planes=vol_planes, out_planes_col=vol_planes_col, kind="ga")
-            return vol_out
-        if fused:
-            assert self.fused_supported(V, T // N), (V, T // N)
-            stream, vecs = self.packed_fused(ctx.device)
-            for bi, blk in enumerate(self.aggregation_transformer.layer_list):      # adaLN modulation of this step -> vecs
-                lin = blk.adaLN_modulation[1]
-                hip.gemv(lin.weight, lin.bias, c, vecs[bi * _G4_VEC_BLOCK:bi * _G4_VEC_BLOCK + 1536].view(1, 1536), act_in=hip.ACT_SILU)
-            pool = ctx.ws.planes("ga.pool", nseq, self.hidden_size)
-            hip.check(L.mvd_gridattn_fused_scenes(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
-                                                  hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec), hip.ptr(stream),
-                                                  hip.ptr(vecs), hip.ptr(pool), N, V, q0, Vq, S, D, float(self.depth_scale),
-                                                  float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, hip.stream()))
+                                                    float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, sst, sst * nv, hip.stream()))
             ctx.gemm(pool, w_fin, vol_out, M=nseq, out_planes=vol_planes, out_planes_col=vol_planes_col, kind="ga")
             return vol_out
         tokens = ctx.ws.planes("ga.tokens", T, hip.TOKEN_LD)
-        hip.check(L.mvd_gridattn_tokens_scenes(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
-                                               hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec),
-                                               hip.ptr(tokens), N, V, q0, Vq, S, D, float(self.depth_scale), float(self.depth_shift),
-                                               hip.stream()))
+        hip.check(L.mvd_gridattn_tokens_scenes_t(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
+                                                 hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec),
+                                                 hip.ptr(tokens), N, V, q0, Vq, S, D, float(self.depth_scale), float(self.depth_shift),
+                                                 0, hip.stream()))
         h = ctx.ws.get("ga.h", (T, self.hidden_size))
         h_alt = ctx.ws.get("ga.h_alt", (T, self.hidden_size))
         ctx.gemm(tokens, w_pre, h, act=hip.ACT_GELU, kind="ga")

@@ -90,12 +90,7 @@ class StepEngine:
 
     # -- host-side inputs ----------------------------------------------------------------------------
     def set_conditioning(self, batch_cameras, input_latents, input_cameras, clip_v_embed):
-        if self.N != 1:
-            raise ValueError(f"set_conditioning on a {self.N}-scene engine: use set_conditioning_scenes")
-        self.cams.copy_(pack_cameras(batch_cameras).to(self.cams.device))
-        self.in_cam.copy_(pack_cameras(input_cameras).to(self.cams.device))
-        self.input_latents.copy_(input_latents.reshape(1, 5, self.S, self.S))
-        self.clip_v_embed.copy_(clip_v_embed.reshape(self.V, 796))
+        self.set_conditioning_scenes([(batch_cameras, input_latents, input_cameras, clip_v_embed)])
 
     def set_conditioning_scenes(self, conds):
         """conds: one (batch_cameras, input_latents, input_cameras, clip_v_embed) per scene, in scene order."""
@@ -109,10 +104,7 @@ class StepEngine:
             self.clip_v_embed[n * V:(n + 1) * V].copy_(ce.reshape(V, 796))
 
     def set_schedule(self, steps_table, depth_noise, ddim_noise):
-        self.steps_scene_stride = 0
-        self._set_tables(steps_table, depth_noise, ddim_noise)
-        self.n_rows = int(steps_table.shape[0])
-        self.rewind()
+        self._set_tables(steps_table, depth_noise, ddim_noise, scene_stride=0)
 
     def set_schedule_scenes(self, steps_table, depth_noise, ddim_noise=None):
         """One training step with a timestep PER SCENE: steps_table (N, STEP_STRIDE) holds scene n's row n, depth_noise (1, N*V, D, S, S).
@@ -125,12 +117,10 @@ class StepEngine:
                              f"(expected ({self.N}, {hip.STEP_STRIDE}))")
         if ddim_noise is None:
             ddim_noise = torch.zeros(1, self.N * self.V, 5, self.S, self.S)
-        self._set_tables(steps_table, depth_noise, ddim_noise)
-        self.steps_scene_stride = 1 if self.N > 1 else 0
-        self.n_rows = 1
-        self.rewind()
+        self._set_tables(steps_table, depth_noise, ddim_noise, scene_stride=1 if self.N > 1 else 0)
 
-    def _set_tables(self, steps_table, depth_noise, ddim_noise):
+    def _set_tables(self, steps_table, depth_noise, ddim_noise, scene_stride):
+        """Load the step table and noise, then rewind: scene n reads step row iter + n * scene_stride (scene_stride 0: one shared row)."""
         dev = self.ctx.device
         if self.steps.shape != steps_table.shape:
             self.graphs.clear()                # table buffers are re-allocated: captured pointers go stale
@@ -145,6 +135,9 @@ class StepEngine:
             self.ddim_noise.copy_(ddim_noise)
         self.steps_nodiv.copy_(self.steps)
         self.steps_nodiv[:, 1] = 1.0
+        self.steps_scene_stride = scene_stride
+        self.n_rows = int(steps_table.shape[0]) - (self.N - 1) * scene_stride      # the kernels index steps[iter + n * stride] unchecked
+        self.rewind()
 
     def rewind(self, it=0):
         """Reset the device iteration counter (and its host mirror) to row `it` of the step table."""
@@ -174,15 +167,10 @@ class StepEngine:
         ts = ctx.ws.get("vf.tsin", (R, 256))
         te1 = ctx.ws.get("vf.te1", (R, 256))
         c = ctx.ws.get("vf.c", (R, 256))
-        if R == 1:
-            hip.check(L.mvd_timestep_embedding(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, st()))
-            hip.gemv(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
-            hip.gemv(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
-        else:
-            hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, R,
-                                                      sst, st()))
-            ctx.gemv_rows(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
-            ctx.gemv_rows(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
+        hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, R, sst,
+                                                  st()))
+        ctx.gemv_rows(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
+        ctx.gemv_rows(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
         # view-aligned features (:303-313)
         dsrc, dsteps = self.depth_geo()
         m.view_attn.run(ctx, self.x, self.depth_noise, self.steps, self.iter, self.cams, self.in_cam,
@@ -215,12 +203,8 @@ class StepEngine:
         unet = m.unet_model.unet_model
         ctx.vol_levels = m.unet_model.volume_pyramid(ctx, self.vol.view(B, S, S, D, 768), B, S, D)
         tsu = ctx.ws.get("vf.tsin_unet", (R, unet.model_channels))
-        if R == 1:
-            hip.check(L.mvd_timestep_embedding(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
-                                               unet.model_channels, st()))
-        else:
-            hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
-                                                      unet.model_channels, R, sst, st()))
+        hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
+                                                  unet.model_channels, R, sst, st()))
         y = unet.run(ctx, self.x_in, tsu, S)
         hip.check(L.mvd_cfg_ddim_update(hip.ptr(y), 8, hip.ptr(xq), hip.ptr(x0q), hip.ptr(epsq),
                                         hip.ptr(self.ddim_noise[:, q0:q0 + NVq]), N * V * 5 * S * S, hip.ptr(self.steps),
@@ -537,25 +521,42 @@ class ViewFusion(nn.Module):
         drop_conditions=True and is in training mode, the per-view condition dropout of unet.py:109-151 is applied
         (``drop_rand`` (V,) optionally injects its torch.rand draw)."""
         V, _, S, _ = noisy_latents.shape
+        if depth_noise is None:
+            depth_noise = torch.randn(V, self.view_attn.n_pts_per_ray, S, S, device=noisy_latents.device)
+        return self._step_scenes(noisy_latents, [(batch_cameras, input_latents, input_cameras, clip_v_embed)], [int(t[0])],
+                                 None if prev_depth is None else [prev_depth], depth_noise, drop_rand, cfg_scale)
+
+    def _step_scenes(self, noisy, conds, ts, prev_depth, depth_noise, drop_rand, cfg_scale=1.0):
+        """One denoising step of N scenes on the N-scene engine, without the DDIM update: noisy (N*V, 5, S, S) scene-major, conds one
+        (batch_cameras, input_latents, input_cameras, clip_v_embed) per scene, ts one timestep per scene (one in all for a guided step),
+        prev_depth None or one (V or 1, 1, S, S) overwrite_attn_depth map per scene, depth_noise (N*V, D, S, S), drop_rand None (drawn
+        here when the condition dropout applies) or (N*V,).  Returns eps (N*V, 5, S, S)."""
+        N = len(conds)
+        NV, _, S, _ = noisy.shape
+        V = NV // N
         D = self.view_attn.n_pts_per_ray
         cfg = cfg_scale != 1.0
-        eng = self.engine(V, S, D, cfg)
-        eng.set_conditioning(batch_cameras, input_latents, input_cameras, clip_v_embed)
-        tv = int(t[0])
-        sac = self.scheduler.sqrt_alphas_cumprod[tv]
-        dstd = self.scheduler.sqrt_one_minus_alphas_cumprod[tv] / sac / 10.0
-        table = torch.tensor([[float(tv), float(sac), float(dstd), 1.0, 1.0, 0.0, 0.0, 0.0]], dtype=torch.float32)
-        if depth_noise is None:
-            depth_noise = torch.randn(V, D, S, S, device=noisy_latents.device)
-        eng.set_schedule(table, depth_noise.reshape(1, V, D, S, S), torch.zeros(1, V, 5, S, S))
-        eng.x.copy_(noisy_latents)
+        eng = self.engine(V, S, D, cfg, scenes=N)
+        eng.set_conditioning_scenes(conds)
+        rows = []
+        for tv in ts:
+            sac = self.scheduler.sqrt_alphas_cumprod[tv]
+            dstd = self.scheduler.sqrt_one_minus_alphas_cumprod[tv] / sac / 10.0
+            rows.append([float(tv), float(sac), float(dstd), 1.0, 1.0, 0.0, 0.0, 0.0])
+        table = torch.tensor(rows, dtype=torch.float32)
+        if cfg:                                # (a guided step shares one timestep)
+            eng.set_schedule(table, depth_noise.reshape(1, NV, D, S, S), torch.zeros(1, NV, 5, S, S))
+        else:
+            eng.set_schedule_scenes(table, depth_noise.reshape(1, NV, D, S, S))
+        eng.x.copy_(noisy)
         eng.depth_mode = 0
-        if prev_depth is not None:             # overwrite_attn_depth (:312; view_attn_efficient2.py:418-426): (V or 1, 1, S, S)
-            eng.prev[:, 4:5].copy_(prev_depth.to(eng.prev.device).expand(V, 1, S, S))
+        if prev_depth is not None:             # overwrite_attn_depth (:312; view_attn_efficient2.py:418-426)
+            for n, pd in enumerate(prev_depth):
+                eng.prev[n * V:(n + 1) * V, 4:5].copy_(pd.to(eng.prev.device).expand(V, 1, S, S))
             eng.depth_mode = 2
         eng.drop_masks = None
         if not cfg and self.drop_conditions and (self.training or self.reference_eval_dropout):
-            r = torch.rand(V, device=noisy_latents.device) if drop_rand is None else drop_rand.to(noisy_latents.device).float()
+            r = torch.rand(NV, device=noisy.device) if drop_rand is None else drop_rand.to(noisy.device).float()
             drop_clip, drop_vol = (r > 0.15) & (r <= 0.2), (r > 0.1) & (r <= 0.15)          # get_drop_scheme 'default' (unet.py:109-117)
             drop_cat, drop_all = (r > 0.05) & (r <= 0.1), r <= 0.05
             eng.drop_masks = tuple(1.0 - (dm | drop_all).float() for dm in (drop_clip, drop_vol, drop_cat))
@@ -573,12 +574,9 @@ class ViewFusion(nn.Module):
     def sample(self, batch, trainer_config, cfg_scale, return_input=False, depth=False, verbose=True):
         """viewfusion_zero_depth_rgb.py:348-359."""
         batch_latents, batch_cameras, input_latents, input_cameras, clip_v_embed = self.prepare_batch(batch, trainer_config)
-        res = self.ddim.sample(batch_cameras, input_latents, input_cameras, clip_v_embed, unconditional_scale=cfg_scale,
-                               depth=depth, return_intermediates=return_input, verbose=verbose)
-        if return_input:
-            x_sample, intermediates = res
-            return x_sample, batch_latents, input_latents, batch_cameras, intermediates
-        return res
+        res = self.ddim.sample(batch_cameras, input_latents, input_cameras, clip_v_embed, unconditional_scale=cfg_scale, depth=depth,
+                               return_intermediates=return_input, verbose=verbose)
+        return (res[0], batch_latents, input_latents, batch_cameras, res[1]) if return_input else res
 
     def sample_scenes(self, batches, trainer_config, cfg_scale, return_input=False, depth=False, verbose=True):
         """``sample`` for several objects at once: every DDIM step denoises all of them in one batched step (DDIMSampler.sample_scenes;
@@ -600,39 +598,10 @@ class ViewFusion(nn.Module):
     def p_losses(self, batch, trainer_config, noise_source=None, _aux=None):
         """viewfusion_zero_depth_rgb.py:362-392 -- the training objective's FORWARD pass on the HIP path: prepare_batch, shared
         random timestep, q_sample, apply_model (cfg 1, condition dropout when self.training), MSE against the noise.
-        The value is a plain tensor: there are no backward kernels yet, so it serves validation /
-        loss monitoring, not optimisation.  ``noise_source(V, D, S) -> dict(t, noise, depth_noise, drop_rand)`` injects the
-        reference's random draws (parity tests); default: torch's device generator in the reference's order."""
-        if isinstance(batch, dict) and "_prepared" in batch:      # (batch_latents, batch_cameras, input_latents, input_cameras,
-            batch_latents, batch_cameras, input_latents, input_cameras, clip_v_embed = batch["_prepared"]      # clip_v_embed): benches
-        else:
-            batch_latents, batch_cameras, input_latents, input_cameras, clip_v_embed = self.prepare_batch(batch, trainer_config)
-        V, _, S, _ = batch_latents.shape
-        D = self.view_attn.n_pts_per_ray
-        dev = batch_latents.device
-        t, noise, depth_noise, drop_rand = self._draw(batch_latents, D, noise_source)
-        sac = self.scheduler.sqrt_alphas_cumprod.to(dev)[t].view(V, 1, 1, 1)
-        s1m = self.scheduler.sqrt_one_minus_alphas_cumprod.to(dev)[t].view(V, 1, 1, 1)
-        noisy = sac * batch_latents + s1m * noise                                          # scheduler.q_sample (:55-64)
-        prev_depth = input_latents[:, 4:].clone() if self.feed_prev_depth else None          # (:377-379)
-        force = getattr(self, "_force_eager", False)
-        self._train_keep_fp32, self._force_eager = True, True      # the backward reads block inputs from the workspace: every fp32 tensor is
-        try:                                                      # written (apply_model sets keep_fp32 on ITS engine's context only: ADVICE
-            pred = self.apply_model(noisy, batch_cameras, input_latents, input_cameras, clip_v_embed, t, prev_depth=prev_depth,   # r04), and
-                                    depth_noise=depth_noise, drop_rand=drop_rand)              # no graph captured in inference mode is replayed
-        finally:
-            self._train_keep_fp32, self._force_eager = False, force
-        if self.objective == "noise":
-            target = noise
-        elif self.objective == "x_start":
-            target = batch_latents
-        else:
-            raise AssertionError(f"objective {self.objective} not implemented")
-        assert self.loss_type == "l2", "loss_type 'l2' is the only one the reference implements (:86-87)"
-        loss = torch.nn.functional.mse_loss(target, pred).mean()
-        if _aux is not None:
-            _aux.update(pred=pred, target=target)
-        return loss
+        ``noise_source(V, D, S) -> dict(t, noise, depth_noise, drop_rand)`` injects the reference's random draws (parity tests);
+        default: torch's device generator in the reference's order.  A ``{"_prepared": prepare_batch output}`` dict skips
+        prepare_batch (benches)."""
+        return self.p_losses_scenes([batch], trainer_config, noise_source=noise_source, _aux=_aux)
 
     def _draw(self, batch_latents, D, noise_source):
         """The random draws of one scene's training step, in the reference's order: (t (V,) shared, noise, depth_noise (V, D, S, S),
@@ -673,13 +642,9 @@ class ViewFusion(nn.Module):
     def p_losses_scenes(self, batches, trainer_config, noise_source=None, _aux=None):
         """p_losses over N scenes in ONE batched step (scene-major views, global view scene*V + v): every scene draws its own timestep,
         noise, depth noise and dropout exactly as a single-scene p_losses on it would (scene_draws), the GEMMs / attention / convolutions
-        run once over all N*V images, and the loss is the mean of the N single-scene losses (the MSE over all N*V views).  One batch: p_losses."""
+        run once over all N*V images, and the loss is the mean of the N single-scene losses (the MSE over all N*V views)."""
         prepared = self._prepare_scenes(batches, trainer_config)
-        if len(prepared) == 1:
-            return self.p_losses({"_prepared": prepared[0]}, trainer_config, noise_source=noise_source, _aux=_aux)
-        N = len(prepared)
-        V, _, S, _ = prepared[0][0].shape
-        D = self.view_attn.n_pts_per_ray
+        V = prepared[0][0].shape[0]
         draws = self.scene_draws([pr[0] for pr in prepared], noise_source)
         dev = prepared[0][0].device
         sa, s1 = self.scheduler.sqrt_alphas_cumprod.to(dev), self.scheduler.sqrt_one_minus_alphas_cumprod.to(dev)
@@ -687,11 +652,15 @@ class ViewFusion(nn.Module):
                            for pr, (t, nz, _, _) in zip(prepared, draws)])
         ts = [int(t[0]) for t, _, _, _ in draws]
         conds = [(bc, il, ic, ce) for _, bc, il, ic, ce in prepared]
-        prev = [pr[2][:, 4:].clone() for pr in prepared] if self.feed_prev_depth else None
+        prev = [pr[2][:, 4:].clone() for pr in prepared] if self.feed_prev_depth else None          # (:377-379)
         force = getattr(self, "_force_eager", False)
-        self._train_keep_fp32, self._force_eager = True, True        # (as p_losses: the backward reads the step's fp32 intermediates)
-        try:
-            pred = self._apply_model_scenes(noisy, conds, ts, prev, torch.cat([d[2] for d in draws]), torch.cat([d[3] for d in draws]))
+        self._train_keep_fp32, self._force_eager = True, True      # the backward reads block inputs from the workspace: every fp32 tensor is
+        try:                                                      # written (on the step's engine only: ADVICE r04); no graph is replayed
+            if len(prepared) == 1:             # one scene: through the public single-scene step (callers and tests may wrap it)
+                (t, _, dn, dr), = draws
+                pred = self.apply_model(noisy, *conds[0], t, prev_depth=None if prev is None else prev[0], depth_noise=dn, drop_rand=dr)
+            else:
+                pred = self._step_scenes(noisy, conds, ts, prev, torch.cat([d[2] for d in draws]), torch.cat([d[3] for d in draws]))
         finally:
             self._train_keep_fp32, self._force_eager = False, force
         if self.objective == "noise":
@@ -706,49 +675,10 @@ class ViewFusion(nn.Module):
             _aux.update(pred=pred, target=target)
         return loss
 
-    def _apply_model_scenes(self, noisy, conds, ts, prev_depth, depth_noise, drop_rand):
-        """apply_model (cfg 1) for N scenes with a timestep per scene on the N-scene engine: noisy (N*V, 5, S, S), ts N ints, prev_depth None
-        or one (1, 1, S, S) map per scene, depth_noise (N*V, D, S, S), drop_rand (N*V,).  Returns eps (N*V, 5, S, S)."""
-        N = len(conds)
-        NV, _, S, _ = noisy.shape
-        V = NV // N
-        D = self.view_attn.n_pts_per_ray
-        eng = self.engine(V, S, D, False, scenes=N)
-        eng.set_conditioning_scenes(conds)
-        rows = []
-        for tv in ts:
-            sac = self.scheduler.sqrt_alphas_cumprod[tv]
-            dstd = self.scheduler.sqrt_one_minus_alphas_cumprod[tv] / sac / 10.0
-            rows.append([float(tv), float(sac), float(dstd), 1.0, 1.0, 0.0, 0.0, 0.0])
-        eng.set_schedule_scenes(torch.tensor(rows, dtype=torch.float32), depth_noise.reshape(1, NV, D, S, S))
-        eng.x.copy_(noisy)
-        eng.depth_mode = 0
-        if prev_depth is not None:
-            for n, pd in enumerate(prev_depth):
-                eng.prev[n * V:(n + 1) * V, 4:5].copy_(pd.to(eng.prev.device).expand(V, 1, S, S))
-            eng.depth_mode = 2
-        eng.drop_masks = None
-        if self.drop_conditions and (self.training or self.reference_eval_dropout):
-            r = drop_rand.to(noisy.device).float()
-            drop_clip, drop_vol = (r > 0.15) & (r <= 0.2), (r > 0.1) & (r <= 0.15)          # get_drop_scheme 'default' (unet.py:109-117)
-            drop_cat, drop_all = (r > 0.05) & (r <= 0.1), r <= 0.05
-            eng.drop_masks = tuple(1.0 - (dm | drop_all).float() for dm in (drop_clip, drop_vol, drop_cat))
-        self._last_drop_masks = eng.drop_masks
-        self._train_engine = eng
-        keep = eng.ctx.keep_fp32
-        eng.ctx.keep_fp32 = True
-        try:
-            eng.step(1.0, do_update=False, use_graph=False)
-        finally:
-            eng.ctx.keep_fp32 = keep
-            eng.drop_masks = None
-        return hip.check_finite(eng.eps.clone(), "ViewFusion.p_losses_scenes")
-
     def _loss(self, batch, trainer_config, noise_source=None, _aux=None):
         """p_losses for one batch dict, p_losses_scenes for a list of them."""
-        if isinstance(batch, (list, tuple)):
-            return self.p_losses_scenes(batch, trainer_config, noise_source=noise_source, _aux=_aux)
-        return self.p_losses(batch, trainer_config, noise_source=noise_source, _aux=_aux)
+        return self.p_losses_scenes(batch if isinstance(batch, (list, tuple)) else [batch], trainer_config, noise_source=noise_source,
+                                    _aux=_aux)
 
     @torch.no_grad()
     def gradients_scenes(self, batches, trainer_config, noise_source=None, only_trainable=False):
