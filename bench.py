@@ -13,12 +13,15 @@ one replay of the captured hipGraph (DDIMSampler.sample's loop body, mvdfusion/s
          all V references) and reports the projected view-parallel speed-up bound t(unsharded) / t(shard).
 
 Weights: deterministic non-zero synthetic fill of the real architecture (no checkpoints offline); data: synthetic GSO rig.
-Prints ONE JSON line on rank 0.  Extra objects: `roofline` (dominant kernel family, HIP-event timed, algorithmic FLOPs
-against the dense 16-bit MFMA peak), `roofline_groups` (attention, GroupNorm, LayerNorm, GridAttn aggregation) and
-`cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set up, warm up, time the steps, write
+--dump-outputs.  `--full` adds what takes work of its own: at N = 1 `roofline` (dominant kernel family, HIP-event timed in an extra
+eager step, algorithmic FLOPs against the dense 16-bit MFMA peak), `roofline_groups` (attention, GroupNorm, LayerNorm, GridAttn
+aggregation), `cpu_baseline` (the CPU oracle timed on this host's cores on a bounded sample) and `secondary` (the V=8 workload, same
+process); at N > 1 `view_parallel` (the same V-view workload unsharded on one GPU).
 Environment: MVD_PREFETCH=ws|0 (weight prefetch of the captured step; `config.weight_prefetch` records it), MVD_HIP_LIB=<.so>
-(another build of the same ABI, tools/probes/ab_build.sh: same-box A/B runs), MVD_BENCH_DUMP_GEMMS=<file> (one line per mvd_gemm launch of
-the eager profile pass: kernel, shape, microseconds -- the tool that found round 5's occupancy regression).
+(another build of the same ABI, tools/probes/ab_build.sh: same-box A/B runs), MVD_BENCH_DUMP_GEMMS=<file> (with --full: one line per
+mvd_gemm launch of the eager profile pass: kernel, shape, microseconds -- the tool that found round 5's occupancy regression, DESIGN.md
+section 6.00 (6)).
 """
 import argparse
 import json
@@ -64,7 +67,8 @@ def weight_prefetch_label():
     return "in-kernel (role-split consumer wavefronts request the following launches' weights)" + (f" [{opts}]" if opts else "")
 
 
-def build(V, S, D, precision, sd=None):
+def build(V, S, D, precision, sd=None, keep_sd=True):
+    """-> (model on the GPU, CPU copy of its weights for the CPU baseline: None when keep_sd is False and no sd was given)."""
     from mvdfusion_amd import synthetic as syn
     from mvdfusion_amd.configs import model_config
     from mvdfusion_amd.viewfusion_zero_depth_rgb import ViewFusion
@@ -73,7 +77,8 @@ def build(V, S, D, precision, sd=None):
         m = ViewFusion(**model_config(320, D=D, S=S, precision=precision))
     if sd is None:      # deterministic non-zero fill keyed by the parameter names (the reference zero-inits every residual branch: SURVEY T1)
         syn.fill_module_(m)
-        sd = {k: v.detach().clone() for k, v in m.state_dict().items() if not k.startswith("scheduler.")}
+        if keep_sd:
+            sd = {k: v.detach().clone() for k, v in m.state_dict().items() if not k.startswith("scheduler.")}
     else:
         missing, unexpected = m.load_state_dict(sd, strict=False)
         assert not unexpected and all(k.startswith("scheduler.") for k in missing), (missing[:5], unexpected[:5])
@@ -401,12 +406,15 @@ def main():
     ap.add_argument("--depth-samples", type=int, default=1)
     ap.add_argument("--precision", default=None, help="f16x4 | f16x3 | bf16x3 | f16 | bf16, or a per-layer-class policy "
                     "'f16x4:conv=3,geglu=3' (mvdfusion_amd.hip.parse_precision); default: mvdfusion_amd.configs.DEFAULT_PRECISION")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, by work of its own: at N=1 the rooflines (an extra eager step), "
+                         "the CPU baseline and the V=8 secondary workload; at N>1 the same workload unsharded on one GPU")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=16, help="threads of the CPU baseline (0 = all host cores)")
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the V=8 x 256^2 single-GPU workload (north-star 1-GPU target) "
-                    "that the default N=1 run times in the same process")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the V=8 x 256^2 single-GPU workload (north-star 1-GPU "
+                    "target) that an N=1 --full run times in the same process")
     ap.add_argument("--gn-two-pass", action="store_true", help="A/B: GroupNorm statistics by their own kernels instead of the producers")
     ap.add_argument("--ln-kernels", action="store_true", help="A/B: LayerNorm kernels instead of the fold into the QKV / GEGLU GEMMs")
     ap.add_argument("--gn-apply-kernels", action="store_true", help="A/B: GroupNorm apply always as its own launch (not inside the split-K reduce)")
@@ -467,7 +475,7 @@ def main():
     p_fmt, p_default, p_policy = hip.parse_precision(a.precision)
     if a.tune_cache and os.path.exists(a.tune_cache):
         log(f"[bench] {hip.load_tuned(a.tune_cache)} tuned GEMM configurations loaded from {a.tune_cache}")
-    m, sd = build(V, S, D, a.precision)
+    m, sd = build(V, S, D, a.precision, keep_sd=a.full and not a.no_cpu_baseline)
     ex = ViewExchange(V) if world > 1 else None
     q0, Vq = (ex.q0, ex.Vq) if ex else (0, None)
     eng, inp, dn, sn = prepare(m, V, S, D, cfg_scale, q0=q0, Vq=Vq)
@@ -537,8 +545,8 @@ def main():
             "algorithmic_tflop_per_step": step_flops / 1e12,
             "algorithmic_tflops": step_flops / (dt / a.steps) / 1e12,
         }
-    # ---- roofline of the dominant kernel family + per-group rooflines (N == 1 only; HIP events on the launch stream)
-    if world == 1:
+    # ---- --full: roofline of the dominant kernel family + per-group rooflines (N == 1 only; HIP events on the launch stream)
+    if world == 1 and a.full:
         by, gsum, family_replay_ms = profile_kernel_groups(m, eng, cfg_scale)
         tot = sum(b["ms"] for b in by.values())
         for k, b in sorted(by.items(), key=lambda kv: -kv[1]["ms"]):
@@ -631,7 +639,8 @@ def main():
                                                    "blocks + pooling in one launch; the north-star 'cross-view attention kernel'. "
                                                    "mfma_pipe_frac = fraction of the dense 16-bit MFMA peak actually issued (mfma_products_per_mac products per MAC)")
         out["roofline_groups"] = rg
-        if a.shard_emulate:
+    if world == 1:
+        if a.shard_emulate:          # (asked for by name: runs with or without --full)
             from mvdfusion_amd.parallel import view_range
             shards = []
             for item in a.shard_emulate.split(","):          # "0/8" or several ranks "0/8,7/8" (the slowest rank bounds the job)
@@ -647,11 +656,11 @@ def main():
                                         note="time of ONE rank's share (its Vq query views against all V references, CFG batch "
                                              "2*Vq) on one GPU; projected_speedup = t(V views unsharded) / t(slowest emulated shard) bounds the "
                                              "N-GPU strong-scaling result (the all-gather of 20 KB latent rows is not included)")
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             cb, _ = cpu_baseline(sd, V, S, D, cfg_scale, n_timed=a.cpu_steps, threads=a.cpu_threads)
             out["cpu_baseline"] = cb
             out["speedup_vs_cpu_baseline"] = out["value"] / cb["value"]
-        if not a.no_secondary and (V, S, D) == (4, 32, 1):
+        if a.full and not a.no_secondary and (V, S, D) == (4, 32, 1):
             # BASELINE.json north_star's 1-GPU target workload (8 views x 256^2 x 50 DDIM steps), timed in this same process
             V2 = 8
             eng2, *_ = prepare(m, V2, S, D, cfg_scale)
@@ -668,8 +677,8 @@ def main():
                 sec["speedup_vs_cpu_baseline"] = sec["value"] / cb2["value"]
             out["secondary"] = sec
     else:
-        # view-parallel speed-up reference: the same V-view workload on ONE GPU (rank 0), unsharded
-        if rank == 0:
+        # --full: view-parallel speed-up reference, the same V-view workload on ONE GPU (rank 0), unsharded
+        if rank == 0 and a.full:
             eng1, *_ = prepare(m, V, S, D, cfg_scale)
             run_steps(eng1, a.warmup, cfg_scale, None, graph)
             torch.cuda.synchronize()

@@ -152,7 +152,7 @@ def test_rccl_one_rank_ddp_training_step():
 @pytest.mark.skipif(os.environ.get("MVD_TEST_FULL") != "1", reason="50 s: MVD_TEST_FULL=1 (the N > 1 JSON contract is covered on CPU by "
                     "tests/test_cpu_distributed.py::test_bench_gpus8_dry_run_contract, the 2-rank data path by the tests above)")
 def test_bench_two_ranks_json_contract():
-    """`python bench.py --gpus 2` end to end on this box's single GPU (MVD_DIST_SHARE_GPU=1: functional only): bench.py spawns the two
+    """`python bench.py --gpus 2 --full` end to end on this box's single GPU (MVD_DIST_SHARE_GPU=1: functional only): bench.py spawns the two
     ranks itself under torch.distributed.run, the ranks shard BASELINE configs[2]'s 8 views, exchange latent rows once per step, and
     rank 0 prints ONE JSON line with the multi-GPU contract the driver reads at N > 1 (n_gpus, scaling, rccl_ranks / backend,
     config.parallelism, view_parallel.speedup_over_single_gpu).  RCCL when it accepts two ranks on one device, else gloo."""
@@ -161,7 +161,7 @@ def test_bench_two_ranks_json_contract():
     # (RCCL refuses two ranks on one device -- known on the 1-GPU test boxes, 30 s per attempt -- so it is only tried where two exist)
     for backend in (("nccl", "gloo") if torch.cuda.device_count() >= 2 else ("gloo",)):
         env = dict(os.environ, MVD_DIST_SHARE_GPU="1", MVD_DIST_BACKEND=backend, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1")
-        r = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+        r = subprocess.run([sys.executable, bench, "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
                            capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         if r.returncode == 0 and len(lines) == 1:

@@ -10,12 +10,12 @@ cd $R
 # ONE kernel mix everywhere: every process loads the committed tuner cache mvdfusion_amd/tuned/gemm_f16.json (hip.load_default_tuned;
 # tools/tune_all.py wrote it) -- the bench runs, the kernel traces and the counter passes below launch identical kernels, and so does the
 # driver's own run (bench config.gemm_tuning says how many problems were tuned in the run: 0 expected)
-python bench.py --steps 100 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.log
-python bench.py --views 8 --steps 50 --warmup 3 --no-cpu-baseline --shard-emulate 0/8,7/8 > $O/bench_v8_s32.json 2> $O/bench_v8_s32.log
-python bench.py --views 8 --latent 64 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_v8_s64.json 2> $O/bench_v8_s64.log
+python bench.py --full --steps 100 --warmup 5 > $O/bench_n1.json 2> $O/bench_n1.log
+python bench.py --full --views 8 --steps 50 --warmup 3 --no-cpu-baseline --shard-emulate 0/8,7/8 > $O/bench_v8_s32.json 2> $O/bench_v8_s32.log
+python bench.py --full --views 8 --latent 64 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_v8_s64.json 2> $O/bench_v8_s64.log
 # the as-shipped inference view count (configs/mvd_gso.yaml:97), the D = 3 geometry, the training step, the VAE, the 2-rank bench contract
-python bench.py --views 15 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_v15_s32.json 2> $O/bench_v15_s32.log
-python bench.py --views 8 --depth-samples 3 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_v8_s32_d3.json 2> $O/bench_v8_s32_d3.log
+python bench.py --full --views 15 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_v15_s32.json 2> $O/bench_v15_s32.log
+python bench.py --full --views 8 --depth-samples 3 --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/bench_v8_s32_d3.json 2> $O/bench_v8_s32_d3.log
 python tools/bench_train.py --steps 5 > $O/train_step.json 2> $O/train_step.log
 python tools/bench_vae.py --steps 20 > $O/decode_n1.json 2> $O/decode_n1.log
 python tools/bench_vae.py --steps 20 --encode > $O/encode_n1.json 2> $O/encode_n1.log
