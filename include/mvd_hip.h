@@ -426,7 +426,27 @@ int mvd_gridattn_fused_scenes_t(const float* x, const float* depth_noise, const 
                                 const float* feat, const float* in_feat, const float* cams, const float* in_cam, const void* wstream,
                                 const float* vecs, void* pooled_sp, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale,
                                 float depth_shift, int prec, int steps_scene_stride, int vecs_scene_stride, mvd_stream_t stream);
-/* timm Attention core over the V reference views (:52): qkv (Nseq*V, 3*heads*dhead) -> out (Nseq*V, heads*dhead) */
+/* Windowed cross-view aggregation (GridAttn keep_top_k_views, :375-384): a 3-D point of query view b is aggregated over W rig
+ * neighbours of b, not over all V views.  `window` = W = 2*(top_k/2) + 1 (odd); window = 0 = all views, which is exactly the
+ * _scenes_t form of the same name (bit-identical: every entry point above is the window = 0 case).
+ *   rows     : (scene, (query view, pixel, depth sample), slot) -- scene*(Vq*S*S*D*W) + ((qv*S*S + pix)*D + d)*W + slot for the token
+ *              matrix (T = nscene*Vq*S*S*D*W rows); the fused kernel pads the W slots of a point to the next power of two internally.
+ *   slot j   : reference view (b + j - W/2) mod V of the query view's own rig, b = q0 + qv = the view's index in the WHOLE rig (not in a
+ *              shard [q0, q0+Vq)).  W > V repeats views through the modulo, as the reference does.
+ * The rig size V indexes cameras, feature maps, latents and depth noise only; the rows per point -- hence the 16-row bound of the
+ * kernels, mvd_view_mha / mvd_view_pool sequence lengths and the padded-row multiple of 64 -- go by W, so V > 16 runs with W <= 16
+ * (fused: V <= 65535). */
+int mvd_gridattn_tokens_window(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                               const float* feat, const float* in_feat, const float* cams, const float* in_cam, void* tokens_sp,
+                               int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
+                               int steps_scene_stride, int window, mvd_stream_t stream);
+int mvd_gridattn_fused_window(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                              const float* feat, const float* in_feat, const float* cams, const float* in_cam, const void* wstream,
+                              const float* vecs, void* pooled_sp, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale,
+                              float depth_shift, int prec, int steps_scene_stride, int vecs_scene_stride, int window,
+                              mvd_stream_t stream);
+/* timm Attention core over the V reference views (:52): qkv (Nseq*V, 3*heads*dhead) -> out (Nseq*V, heads*dhead); V = the sequence
+ * length: the window W with mvd_gridattn_tokens_window rows */
 int mvd_view_mha(const float* qkv, void* out_sp, int Nseq, int V, int heads, int dhead,
                  mvd_stream_t stream); /* output: split planes */
 /* weight_layer + softmax over V + weighted sum (:83,396-397): x (Nseq*V, C) -> out (Nseq, C) */
@@ -536,6 +556,12 @@ int mvd_gridattn_tokens_backward_scenes(const float* x, const float* depth_noise
                                         const float* cams, const float* in_cam, const float* dtok, int ldt, long long* dfeat_acc,
                                         long long* din_feat_acc, float scale, int nscene, int V, int q0, int Vq, int S, int D,
                                         float depth_scale, float depth_shift, int steps_scene_stride, mvd_stream_t stream);
+/* mvd_gridattn_tokens_backward_scenes over the rows of mvd_gridattn_tokens_window (dtok row pt*W + slot scatters into view
+ * (b + slot - W/2) mod V; a view repeated by W > V accumulates every repeat).  window = 0 is mvd_gridattn_tokens_backward_scenes. */
+int mvd_gridattn_tokens_backward_window(const float* x, const float* depth_noise, const float* steps, const int* iter, const float* grid_lin,
+                                        const float* cams, const float* in_cam, const float* dtok, int ldt, long long* dfeat_acc,
+                                        long long* din_feat_acc, float scale, int nscene, int V, int q0, int Vq, int S, int D,
+                                        float depth_scale, float depth_shift, int steps_scene_stride, int window, mvd_stream_t stream);
 
 #ifdef __cplusplus
 }

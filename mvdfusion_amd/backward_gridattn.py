@@ -10,7 +10,7 @@ keeping its intermediates, then
   <- bilinear gathers of the z-embedded latents (grid_sample backward = mvd_gridattn_tokens_backward)  <- z_embedder.
 
 Matrix products run on the split-operand MFMA GEMM (backward.linear_backward), attention over V on mvd_attention_backward with
-sequences of length V, LayerNorm+modulate on mvd_layernorm_backward with weight (1 + scale); elementwise glue (GELU', gates, the
+sequences of length V (the window W with keep_top_k_views: the chain below runs over W rows per 3-D point), LayerNorm+modulate on mvd_layernorm_backward with weight (1 + scale); elementwise glue (GELU', gates, the
 (nseq, V, C) pooling algebra, the 5-channel z-embedding) is torch.
 """
 import math
@@ -103,7 +103,9 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     C = ga.hidden_size
     N, sst = eng.N, eng.steps_scene_stride
     nseq = N * V * S * S * D
-    T = nseq * V
+    W = ga.window                   # keep_top_k_views: W rig neighbours per point instead of all V views (0 = all)
+    R = ga.rows_per_point(V)        # rows per 3-D point = the attention / pooling sequence length of everything below
+    T = nseq * R
     agg = ga.aggregation_transformer
     # ---- forward (unfused chain, view_attn_efficient2.py GridAttn.run)
     z = ga.z_embedder[0]
@@ -116,16 +118,16 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     tokens = hip.planes_like(T, hip.TOKEN_LD, dev)
     dsrc, dsteps = eng.depth_geo()          # (the depth source the forward used: x itself, or an overwrite_attn_depth map)
     geo = (hip.ptr(dsrc), hip.ptr(eng.depth_noise), hip.ptr(dsteps), hip.ptr(eng.iter), hip.ptr(grid_lin))
-    hip.check(L.mvd_gridattn_tokens_scenes_t(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens),
-                                             N, V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift), sst, hip.stream()))
+    hip.check(L.mvd_gridattn_tokens_window(*geo, hip.ptr(feat), hip.ptr(in_feat), hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(tokens),
+                                           N, V, 0, V, S, D, float(ga.depth_scale), float(ga.depth_shift), sst, W, hip.stream()))
     pre = ga.pre_layer_b[0]
     z0 = tape.linear(tokens, pre.weight, pre.bias)                             # (T, 256) pre-activation
     hs = [bw.act_planes(z0, hip.ACT_GELU, planes=False, f32=True)[1]]
     for blk in agg.layer_list:
         hcur = hs[-1]
         # block output via the inference path's own kernels (DiTBlock.run mutates its buffers: use the unfused algebra here)
-        hs.append(_dit_forward(tape, blk, hcur, c, T, V))
-    hL = hs[-1].view(nseq, V, C)
+        hs.append(_dit_forward(tape, blk, hcur, c, T, R))
+    hL = hs[-1].view(nseq, R, C)
     wl = agg.weight_layer
     lg = hL @ wl.weight[0] + wl.bias                                           # (nseq, V)        host glue
     p = torch.softmax(lg, dim=1)
@@ -142,7 +144,7 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     g["aggregation_transformer.weight_layer.bias"] = dlg.sum().reshape(1)
     dc = torch.zeros_like(c)
     for bi in range(len(agg.layer_list) - 1, -1, -1):
-        dh, gb, dcb = _dit_block_backward(tape, agg.layer_list[bi], hs[bi], c, dh.contiguous(), T, V)
+        dh, gb, dcb = _dit_block_backward(tape, agg.layer_list[bi], hs[bi], c, dh.contiguous(), T, R)
         g.update({f"aggregation_transformer.layer_list.{bi}.{k}": v for k, v in gb.items()})
         dc += dcb
     dtok, g["pre_layer_b.0.weight"], g["pre_layer_b.0.bias"] = tape.linear_bwd(tokens, pre.weight, bw.act_backward(dh, z0, hip.ACT_GELU))
@@ -154,9 +156,9 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     scale = 2.0 ** (40 - math.floor(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 1.0
     dfeat_acc = torch.zeros(N * V, S, S, 256, dtype=torch.int64, device=dev)
     din_acc = torch.zeros(N, S, S, 256, dtype=torch.int64, device=dev)
-    hip.check(L.mvd_gridattn_tokens_backward_scenes(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
+    hip.check(L.mvd_gridattn_tokens_backward_window(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
                                                     hip.ptr(din_acc), float(scale), N, V, 0, V, S, D, float(ga.depth_scale),
-                                                    float(ga.depth_shift), sst, hip.stream()))
+                                                    float(ga.depth_shift), sst, W, hip.stream()))
     dW = torch.zeros_like(z.weight)
     db = torch.zeros_like(z.bias)
     for lat, acc, n in ((eng.x, dfeat_acc, N * V), (eng.input_latents, din_acc, N)):

@@ -2,8 +2,9 @@
 // depth-sample -> unproject -> reproject -> bilinear gather -> Plucker/harmonic embedding kernel that writes the token
 // matrix consumed by the aggregation transformer's first GEMM.
 //
-// One wavefront per 3-D query point ([scene,] query view b, pixel, depth sample d); it loops over the V reference views and
-// writes one coalesced 736-float row per view: lanes own 4 feature channels each (float4 gathers from the
+// One wavefront per 3-D query point ([scene,] query view b, pixel, depth sample d); it loops over the point's reference view slots -- the
+// V views of the rig, or with a window (mvd_gridattn_tokens_window) the W rig neighbours (b + j - W/2) mod V, j = 0 .. W-1 -- and
+// writes one coalesced 736-float row per slot: lanes own 4 feature channels each (float4 gathers from the
 // channels-last feature maps, which stay L2/MALL resident: (V+1) x S x S x 256 fp32 = 1 MB per view), and the 210
 // sin/cos embedding values are spread over the lanes.
 #include "gridattn_common.hpp"
@@ -15,7 +16,7 @@ __global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ x
                                                      const float* __restrict__ grid_lin, const float* __restrict__ feat,
                                                      const float* __restrict__ in_feat, const float* __restrict__ cams,
                                                      const float* __restrict__ in_cam, u16* __restrict__ tok, int nscene, int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
-                                                     int steps_scene_stride) {
+                                                     int steps_scene_stride, int window) {
   const int lane = threadIdx.x & 63;
   const int SS = S * S;
   const size_t npts = (size_t)nscene * Vq * SS * D;
@@ -74,8 +75,10 @@ __global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ x
     project(ci, X, u, v);
     fin = bilinear4(in_feat, S, lane * 4, -u, -v);
   }
-  // ---- per reference view
-  for (int vr = 0; vr < V; ++vr) {
+  // ---- per reference view slot: all V views in order, or the window's W neighbours of b starting at (b - W/2) mod V (wave-uniform)
+  const int W = window ? window : V;
+  int vr = window ? ((b - window / 2) % V + V) % V : 0;
+  for (int slot = 0; slot < W; ++slot, vr = vr + 1 == V ? 0 : vr + 1) {
     const Cam cv = load_cam(cams + (size_t)(gv0 + vr) * MVD_CAM_RECORD);
     float u, v;
     project(cv, X, u, v);
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ x
     rpl[3] = cv.C[1] * rpl[2] - cv.C[2] * rpl[1];
     rpl[4] = cv.C[2] * rpl[0] - cv.C[0] * rpl[2];
     rpl[5] = cv.C[0] * rpl[1] - cv.C[1] * rpl[0];
-    const size_t row = pt * V + vr;
+    const size_t row = pt * W + slot;
     store_sp4(tok, row, MVD_TOKEN_LD, lane * 4, fr.x, fr.y, fr.z, fr.w);
     store_sp4(tok, row, MVD_TOKEN_LD, 256 + lane * 4, fin.x, fin.y, fin.z, fin.w);
     {
@@ -179,7 +182,7 @@ __global__ __launch_bounds__(256) void tokens_bwd_kernel(const float* __restrict
                                                          const float* __restrict__ in_cam, const float* __restrict__ dtok, int ldt,
                                                          long long* __restrict__ dfeat, long long* __restrict__ din_feat, float scale, int nscene,
                                                          int V, int q0, int Vq, int S, int D, float depth_scale, float depth_shift,
-                                                         int steps_scene_stride) {
+                                                         int steps_scene_stride, int window) {
   const int lane = threadIdx.x & 63;
   const int SS = S * S;
   const size_t npts = (size_t)nscene * Vq * SS * D;
@@ -213,15 +216,17 @@ __global__ __launch_bounds__(256) void tokens_bwd_kernel(const float* __restrict
     X[j] = (p1[j] - dir) + depth * dir;
   }
   float4 gin = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int vr = 0; vr < V; ++vr) {
+  const int W = window ? window : V;      // the forward's slots (tokens_kernel): row pt * W + slot was gathered from view vr
+  int vr = window ? ((b - window / 2) % V + V) % V : 0;
+  for (int slot = 0; slot < W; ++slot, vr = vr + 1 == V ? 0 : vr + 1) {
     const Cam cv = load_cam(cams + (size_t)(gv0 + vr) * MVD_CAM_RECORD);
     float u, v;
     project(cv, X, u, v);
     const Taps4 t = bilinear_taps(S, -u, -v);
-    const float* row = dtok + (pt * V + vr) * (size_t)ldt;
+    const float* row = dtok + (pt * W + slot) * (size_t)ldt;
     const float4 g = *(const float4*)(row + lane * 4);
     scatter4(dfeat + (size_t)vr * SS * 256, t, lane * 4, g, scale);
-    const float4 gi = *(const float4*)(row + 256 + lane * 4);     // the input-view block is the same sample in all V rows
+    const float4 gi = *(const float4*)(row + 256 + lane * 4);     // the input-view block is the same sample in all the point's rows
     gin.x += gi.x; gin.y += gi.y; gin.z += gi.z; gin.w += gi.w;
   }
   {
@@ -242,24 +247,33 @@ extern "C" int mvd_zembed(const float* lat, const float* w, const float* b, floa
   return 0;
 }
 
-extern "C" int mvd_gridattn_tokens_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter,
-                                            const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
-                                            const float* in_cam, void* tokens_sp, int nscene, int V, int q0, int Vq, int S, int D,
-                                            float depth_scale, float depth_shift, int steps_scene_stride, mvd_stream_t stream) {
+extern "C" int mvd_gridattn_tokens_window(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                          const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                          const float* in_cam, void* tokens_sp, int nscene, int V, int q0, int Vq, int S, int D,
+                                          float depth_scale, float depth_shift, int steps_scene_stride, int window, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && tokens_sp,
                 "mvd_gridattn_tokens: null pointer");
   MVD_CHECK_ARG(nscene >= 1, "mvd_gridattn_tokens_scenes: nscene=%d (>= 1)", nscene);
   MVD_CHECK_ARG(steps_scene_stride >= 0 && (nscene > 1 || steps_scene_stride == 0),
                 "mvd_gridattn_tokens_scenes_t: steps_scene_stride=%d (>= 0; 0 when nscene = 1)", steps_scene_stride);
-  MVD_CHECK_ARG(V > 0 && V <= 16 && S > 1 && D > 0, "mvd_gridattn_tokens: bad shape (V <= 16)");
+  MVD_CHECK_ARG(window == 0 || (window >= 1 && (window & 1)), "mvd_gridattn_tokens_window: window=%d (0 = all views, else odd)", window);
+  MVD_CHECK_ARG(V > 0 && (window ? window : V) <= 16 && S > 1 && D > 0, "mvd_gridattn_tokens: bad shape (at most 16 rows per point)");
   MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V, "mvd_gridattn_tokens: bad query-view range [%d, %d) of %d", q0, q0 + Vq, V);
   const size_t npts = (size_t)nscene * Vq * S * S * D;      // one wavefront per point: a point never straddles two scenes
   MVD_CHECK_ARG((size_t)nscene * V <= 0x7fffffff && (npts + 3) / 4 <= 0x7fffffff, "mvd_gridattn_tokens: grid too large");
   hipLaunchKernelGGL(tokens_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, x, depth_noise, steps, iter,
                      grid_lin, feat, in_feat, cams, in_cam, (u16*)tokens_sp, nscene, V, q0, Vq, S, D, depth_scale, depth_shift,
-                     steps_scene_stride);
+                     steps_scene_stride, window);
   MVD_CHECK_LAUNCH("mvd_gridattn_tokens");
   return 0;
+}
+
+extern "C" int mvd_gridattn_tokens_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                            const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                            const float* in_cam, void* tokens_sp, int nscene, int V, int q0, int Vq, int S, int D,
+                                            float depth_scale, float depth_shift, int steps_scene_stride, mvd_stream_t stream) {
+  return mvd_gridattn_tokens_window(x, depth_noise, steps, iter, grid_lin, feat, in_feat, cams, in_cam, tokens_sp, nscene, V, q0, Vq, S, D,
+                                    depth_scale, depth_shift, steps_scene_stride, 0, stream);
 }
 
 extern "C" int mvd_gridattn_tokens_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
@@ -278,25 +292,37 @@ extern "C" int mvd_gridattn_tokens(const float* x, const float* depth_noise, con
                                     depth_scale, depth_shift, stream);
 }
 
-extern "C" int mvd_gridattn_tokens_backward_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
+extern "C" int mvd_gridattn_tokens_backward_window(const float* x, const float* depth_noise, const float* steps, const int* iter,
                                                    const float* grid_lin, const float* cams, const float* in_cam, const float* dtok, int ldt,
                                                    long long* dfeat_acc, long long* din_feat_acc, float scale, int nscene, int V, int q0,
                                                    int Vq, int S, int D, float depth_scale, float depth_shift, int steps_scene_stride,
-                                                   mvd_stream_t stream) {
+                                                   int window, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && cams && in_cam && dtok && dfeat_acc && din_feat_acc,
                 "mvd_gridattn_tokens_backward: null pointer");
   MVD_CHECK_ARG(nscene >= 1 && steps_scene_stride >= 0 && (nscene > 1 || steps_scene_stride == 0),
                 "mvd_gridattn_tokens_backward_scenes: nscene=%d (>= 1), steps_scene_stride=%d (>= 0; 0 when nscene = 1)", nscene,
                 steps_scene_stride);
-  MVD_CHECK_ARG(V > 0 && V <= 16 && S > 1 && D > 0 && ldt >= 512 && ldt % 4 == 0 && ((uintptr_t)dtok & 15) == 0 && scale > 0.f,
+  MVD_CHECK_ARG(window == 0 || (window >= 1 && (window & 1)), "mvd_gridattn_tokens_backward_window: window=%d (0 = all views, else odd)",
+                window);
+  MVD_CHECK_ARG(V > 0 && (window ? window : V) <= 16 && S > 1 && D > 0 && ldt >= 512 && ldt % 4 == 0 && ((uintptr_t)dtok & 15) == 0 && scale > 0.f,
                 "mvd_gridattn_tokens_backward: bad shape (ldt >= 512, 16-byte aligned dtok)");
   MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V, "mvd_gridattn_tokens_backward: bad query-view range");
   const size_t npts = (size_t)nscene * Vq * S * S * D;
   MVD_CHECK_ARG((size_t)nscene * V <= 0x7fffffff && (npts + 3) / 4 <= 0x7fffffff, "mvd_gridattn_tokens_backward: grid too large");
   hipLaunchKernelGGL(tokens_bwd_kernel, dim3(cdiv(npts, 4)), dim3(256), 0, (hipStream_t)stream, x, depth_noise, steps, iter, grid_lin, cams,
-                     in_cam, dtok, ldt, dfeat_acc, din_feat_acc, scale, nscene, V, q0, Vq, S, D, depth_scale, depth_shift, steps_scene_stride);
+                     in_cam, dtok, ldt, dfeat_acc, din_feat_acc, scale, nscene, V, q0, Vq, S, D, depth_scale, depth_shift, steps_scene_stride,
+                     window);
   MVD_CHECK_LAUNCH("mvd_gridattn_tokens_backward");
   return 0;
+}
+
+extern "C" int mvd_gridattn_tokens_backward_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                                   const float* grid_lin, const float* cams, const float* in_cam, const float* dtok, int ldt,
+                                                   long long* dfeat_acc, long long* din_feat_acc, float scale, int nscene, int V, int q0,
+                                                   int Vq, int S, int D, float depth_scale, float depth_shift, int steps_scene_stride,
+                                                   mvd_stream_t stream) {
+  return mvd_gridattn_tokens_backward_window(x, depth_noise, steps, iter, grid_lin, cams, in_cam, dtok, ldt, dfeat_acc, din_feat_acc, scale,
+                                             nscene, V, q0, Vq, S, D, depth_scale, depth_shift, steps_scene_stride, 0, stream);
 }
 
 extern "C" int mvd_gridattn_tokens_backward(const float* x, const float* depth_noise, const float* steps, const int* iter,

@@ -6,9 +6,11 @@
 // and writes the pooled (Nseq, 256) rows as split planes for the last Linear 256->768 (a plain mvd_gemm).
 //
 // Mapping.  Token rows are ordered (scene, (query view, pixel, depth sample), reference view slot): Vp consecutive rows = one 3-D point =
-// one attention sequence, Vp = the next power of two >= V (so a sequence never straddles a wavefront's 16 rows).  Slots vr >= V are
-// PADDING: they run the arithmetic on a copy of the last reference view (finite values), are masked out as attention KEYS and in the
-// softmax-over-V pooling, and are never stored -- the reference's view counts 15 / 7 / 5 / 3 (configs/mvd_gso.yaml:97, mvd_train.yaml:90,97)
+// one attention sequence of W slots, Vp = the next power of two >= W (so a sequence never straddles a wavefront's 16 rows).  W = V and slot j =
+// view j by default; with a window (mvd_gridattn_fused_window, GridAttn keep_top_k_views) W = 2 * (top_k / 2) + 1 and slot j of query view b
+// is view (b + j - W/2) mod V of b's rig -- the rig size V then only indexes cameras, feature maps, latents and noise, and is not bounded by
+// the 16 rows.  Slots >= W are PADDING: they run the arithmetic on a copy of the last real slot (finite values), are masked out as attention
+// KEYS and in the softmax-over-slots pooling, and are never stored -- the reference's view counts 15 / 7 / 5 / 3 (configs/mvd_gso.yaml:97, mvd_train.yaml:90,97)
 // take this kernel at 16 / 8 / 8 / 4 slots.  A wavefront owns 16 consecutive rows for the whole kernel; a workgroup is 4 wavefronts (64 rows).
 // Scenes (mvd_gridattn_fused_scenes): N independent rigs in one launch, each with its own cameras, input view and latents, addressed by the
 // global view index scene * V + view; a scene's rows are a whole number of workgroups (checked at launch), so the scene is workgroup-uniform
@@ -64,7 +66,9 @@ struct G4Params {
   const unsigned char* wstream;   // nslots x 32 KiB
   const float* vecs;              // G4_VEC_GRANULES * 256 floats
   u16* pooled_sp;                 // (Nseq, 256) split planes
-  int V, Vp, lv, q0, Vq, S, D, nslots;      // Vp = 2^lv >= V: rows per 3-D point (reference views padded to a power of two)
+  int V, W, Vp, lv, q0, Vq, S, D, nslots;   // V views in the rig; W slots per 3-D point (V, or the window); Vp = 2^lv >= W rows per point
+  int windowed;                             // launch-uniform: 0 = slot j is view j (W = V); 1 = slot j of query view b is (b + win_off[j]) mod V
+  unsigned win_off[8];                      // windowed: (j - W/2) mod V of slot j as 16 bits, two slots per word; slots >= W repeat slot W - 1
   int nscene, wg_per_scene;                 // scenes in the launch; workgroups per scene (Vq*S*S*D*Vp / 64)
   int steps_scene_stride, vecs_scene_stride;  // scene n: step row *iter + n * steps_scene_stride, vector table vecs + n * vecs_scene_stride
   float depth_scale, depth_shift;
@@ -204,7 +208,7 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, g = lane >> 4;
   const float* const smisc = (const float*)(smem + G4_OFF_MISC);        // index = global index - G4_VEC_MISC
-  const int V = p.V, Vp = p.Vp, lv = p.lv, S = p.S, D = p.D, SS = S * S;
+  const int V = p.V, W = p.W, Vp = p.Vp, lv = p.lv, S = p.S, D = p.D, SS = S * S;
   const int scene = (int)(blockIdx.x / (unsigned)p.wg_per_scene);        // workgroup-uniform (scalar)
   // the scene's own timestep: its vector table (adaLN modulation) and step row; both strides are 0 for a shared timestep
   const float* const vecs = p.vecs + (size_t)scene * p.vecs_scene_stride;
@@ -345,11 +349,24 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   const size_t t_row = (size_t)blockIdx.x * 64 + wave * 16 + r16;
   const size_t pt = t_row >> lv;
   const int vslot = (int)(t_row & (size_t)(Vp - 1));
-  const bool pad_row = vslot >= V;                       // padding slot: computed like the last real view, masked below
-  const int vr = pad_row ? V - 1 : vslot;
+  const bool pad_row = vslot >= W;                       // padding slot: computed like the last real slot, masked below
   const int d = (int)(pt % D);
   const int pix = (int)((pt / D) % SS);
-  const int b = p.q0 + (int)(pt / ((size_t)D * SS)) - scene * p.Vq;      // query view inside the scene
+  const int b = p.q0 + (int)(pt / ((size_t)D * SS)) - scene * p.Vq;      // query view inside the scene (its index in the whole rig)
+  int vr = pad_row ? W - 1 : vslot;                      // reference view of this row: all views -> the slot itself
+  if (p.windowed) {                                      // window -> the rig neighbour (b + slot - W/2) mod V, offsets from the host
+    const int pr = vslot >> 1;
+    unsigned w = p.win_off[0];
+    w = pr == 1 ? p.win_off[1] : w;
+    w = pr == 2 ? p.win_off[2] : w;
+    w = pr == 3 ? p.win_off[3] : w;
+    w = pr == 4 ? p.win_off[4] : w;
+    w = pr == 5 ? p.win_off[5] : w;
+    w = pr == 6 ? p.win_off[6] : w;
+    w = pr == 7 ? p.win_off[7] : w;
+    vr = b + (int)((w >> ((vslot & 1) * 16)) & 0xffffu);
+    if (vr >= V) vr -= V;
+  }
   const int gv0 = scene * V;                                             // global index of the scene's view 0
   // geometry of this lane's row: world point, Plucker coordinates, bilinear taps in the reference view and the input view
   Vec6 qpl, rpl;
@@ -582,7 +599,7 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
       bool ok[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        ok[r] = ((4 * g + r) >> lv) == (r16 >> lv) && ((4 * g + r) & (Vp - 1)) < V;
+        ok[r] = ((4 * g + r) >> lv) == (r16 >> lv) && ((4 * g + r) & (Vp - 1)) < W;
         if (ok[r]) mx = fmaxf(mx, st[r]);
       }
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -709,11 +726,11 @@ extern "C" int mvd_gridattn_fused_slots(void) { return 23 + 3 * 64; }
 extern "C" size_t mvd_gridattn_fused_stream_bytes(void) { return (size_t)(23 + 3 * 64) * G4_SLOT_BYTES; }
 extern "C" size_t mvd_gridattn_fused_vec_floats(void) { return (size_t)G4_VEC_GRANULES * 256; }
 
-extern "C" int mvd_gridattn_fused_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter,
-                                           const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+extern "C" int mvd_gridattn_fused_window(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                         const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
                                          const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int nscene, int V,
                                          int q0, int Vq, int S, int D, float depth_scale, float depth_shift, int prec, int steps_scene_stride,
-                                         int vecs_scene_stride, mvd_stream_t stream) {
+                                         int vecs_scene_stride, int window, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && wstream && vecs && pooled_sp,
                 "mvd_gridattn_fused: null pointer");
   MVD_CHECK_ARG(nscene >= 1, "mvd_gridattn_fused_scenes: nscene=%d (>= 1)", nscene);
@@ -721,9 +738,13 @@ extern "C" int mvd_gridattn_fused_scenes_t(const float* x, const float* depth_no
                     (nscene > 1 || (steps_scene_stride == 0 && vecs_scene_stride == 0)),
                 "mvd_gridattn_fused_scenes_t: steps_scene_stride=%d, vecs_scene_stride=%d (>= 0, vecs stride a multiple of 4; both 0 when "
                 "nscene = 1)", steps_scene_stride, vecs_scene_stride);
-  MVD_CHECK_ARG(V >= 1 && V <= 16, "mvd_gridattn_fused: V=%d outside [1, 16] (use the unfused path)", V);
+  MVD_CHECK_ARG(window == 0 || (window >= 1 && (window & 1)), "mvd_gridattn_fused_window: window=%d (0 = all views, else odd)", window);
+  const int W = window ? window : V;                      // slots (attention sequence) per 3-D point
+  MVD_CHECK_ARG(V >= 1 && W <= 16, "mvd_gridattn_fused: %d slots per point outside [1, 16] (V=%d, window=%d; use the unfused path)", W, V,
+                window);
+  MVD_CHECK_ARG(window == 0 || V <= 0xffff, "mvd_gridattn_fused_window: V=%d (<= 65535 with a window)", V);
   int lv = 0;
-  while ((1 << lv) < V) ++lv;
+  while ((1 << lv) < W) ++lv;
   const int Vp = 1 << lv;
   MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V && S > 1 && D > 0, "mvd_gridattn_fused: bad shape");
   MVD_CHECK_ARG(prec == MVD_PREC_X3 || prec == MVD_PREC_X4, "mvd_gridattn_fused: prec %d (MVD_PREC_X3 or MVD_PREC_X4)", prec);
@@ -737,15 +758,32 @@ extern "C" int mvd_gridattn_fused_scenes_t(const float* x, const float* depth_no
   p.dbg = g_g4_dbg;
   p.x = x; p.depth_noise = depth_noise; p.steps = steps; p.iter = iter; p.grid_lin = grid_lin; p.feat = feat;
   p.in_feat = in_feat; p.cams = cams; p.in_cam = in_cam; p.wstream = (const unsigned char*)wstream; p.vecs = vecs;
-  p.pooled_sp = (u16*)pooled_sp; p.V = V; p.Vp = Vp; p.lv = lv; p.q0 = q0; p.Vq = Vq; p.S = S; p.D = D; p.nslots = 23 + 3 * 64;
+  p.pooled_sp = (u16*)pooled_sp; p.V = V; p.W = W; p.Vp = Vp; p.lv = lv; p.q0 = q0; p.Vq = Vq; p.S = S; p.D = D; p.nslots = 23 + 3 * 64;
   p.nscene = nscene; p.wg_per_scene = (int)(Ts / 64);
   p.steps_scene_stride = steps_scene_stride; p.vecs_scene_stride = vecs_scene_stride;
   p.depth_scale = depth_scale; p.depth_shift = depth_shift;
+  p.windowed = window != 0;
+  for (int j = 0; j < 8; ++j) p.win_off[j] = 0;
+  if (window)
+    for (int j = 0; j < 16; ++j) {
+      const int s = j < W ? j : W - 1;                     // padding slots copy the last real one
+      const unsigned off = (unsigned)((((s - W / 2) % V) + V) % V);
+      p.win_off[j >> 1] |= off << ((j & 1) * 16);
+    }
   const dim3 grid((unsigned)(Ts / 64 * nscene));
   if (prec == MVD_PREC_X3) hipLaunchKernelGGL(g4_fused_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(g4_fused_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
   MVD_CHECK_LAUNCH("mvd_gridattn_fused");
   return 0;
+}
+
+extern "C" int mvd_gridattn_fused_scenes_t(const float* x, const float* depth_noise, const float* steps, const int* iter,
+                                           const float* grid_lin, const float* feat, const float* in_feat, const float* cams,
+                                           const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int nscene, int V,
+                                           int q0, int Vq, int S, int D, float depth_scale, float depth_shift, int prec,
+                                           int steps_scene_stride, int vecs_scene_stride, mvd_stream_t stream) {
+  return mvd_gridattn_fused_window(x, depth_noise, steps, iter, grid_lin, feat, in_feat, cams, in_cam, wstream, vecs, pooled_sp, nscene, V,
+                                   q0, Vq, S, D, depth_scale, depth_shift, prec, steps_scene_stride, vecs_scene_stride, 0, stream);
 }
 
 extern "C" int mvd_gridattn_fused_scenes(const float* x, const float* depth_noise, const float* steps, const int* iter,

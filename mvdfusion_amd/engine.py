@@ -19,7 +19,9 @@ GN_SLOT_ELEMS = 64 * 32 * 2     # up to 64 images per batch, 32 groups, {sum, su
 
 
 class Workspace:
-    """Named static buffers.  get(tag, shape) returns the same tensor (same address) on every call."""
+    """Named static buffers.  get(tag, shape) returns the same tensor (same address) on every call.  Buffers are keyed by shape, so the
+    arena follows what the model asks for: GridAttn's token / attention buffers have nseq * W rows with a window (keep_top_k_views), nseq * V
+    without -- a construction-time property of the model (a flip on a live model needs ViewFusion.invalidate_packed(): new engines)."""
 
     def __init__(self, device):
         self.device = torch.device(device)

@@ -115,6 +115,8 @@ SIGNATURES = {
     "mvd_gridattn_tokens_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _f, _f, _vp]),
     "mvd_gridattn_tokens_backward_scenes": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _f, _f, _i,
                                                  _vp]),
+    "mvd_gridattn_tokens_backward_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _f, _f, _i,
+                                                 _i, _vp]),
     "mvd_layernorm_backward": (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     "mvd_layernorm_backward_groups": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvd_geglu_backward": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
@@ -143,6 +145,8 @@ SIGNATURES = {
     "mvd_gridattn_fused": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "mvd_gridattn_fused_scenes": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "mvd_gridattn_fused_scenes_t": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _vp]),
+    "mvd_gridattn_tokens_window": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _vp]),
+    "mvd_gridattn_fused_window": (_i, [_vp] * 12 + [_i, _i, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i, _vp]),
     "mvd_view_mha": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "mvd_view_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvd_cfg_ddim_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _f, _i, _vp]),

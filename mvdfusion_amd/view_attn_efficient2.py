@@ -10,6 +10,10 @@ Per step (one launch each unless noted):
   -> 3 x [adaLN GEMV, LN+modulate, QKV GEMM, attention over the V views, proj GEMM (+gate +residual),
           LN+modulate, fc1 GEMM(+GELU), fc2 GEMM (+gate +residual)]
   -> weight-softmax pooling over V -> final GEMM -> (V, S, S, D, 768) feature frustum.
+
+keep_top_k_views=True (:375-384) aggregates a 3-D point of query view b over the W = 2 * (top_k // 2) + 1 rig neighbours of b instead of
+all V views: the attention sequence, the pooling and every row count go by W (window_size / window_view_table below), the rig size V only
+indexes cameras, feature maps, latents and noise -- so rigs of more than 16 views run, at W <= 16 rows per point.
 """
 import torch
 import torch.nn as nn
@@ -22,6 +26,19 @@ from .cameras import pack_cameras
 # weight stream of the fused aggregation kernel (csrc/gridattn_fused.hip)
 # ------------------------------------------------------------------------------------------------
 _G4_VEC_BLOCK, _G4_VEC_MISC = 3328, 3 * 3328
+
+
+def window_size(keep_top_k_views, top_k):
+    """Rows (reference view slots) per 3-D point of the windowed aggregation: W = 2 * (top_k // 2) + 1 -- top_k = 4 and 5 both give 5;
+    0 = no window, every view of the rig (the `window` argument of the mvd_gridattn_*_window entry points)."""
+    return 2 * (int(top_k) // 2) + 1 if keep_top_k_views else 0
+
+
+def window_view_table(V, top_k):
+    """(W, V) int64: entry [j, b] = the reference view in slot j of query view b = (b + j - top_k // 2) mod V, b being the view's index in
+    the whole rig (view_attn_efficient2.py:376-380).  W > V repeats views through the modulo, as the reference does."""
+    half = int(top_k) // 2
+    return (torch.arange(-half, half + 1)[:, None] + torch.arange(int(V))[None, :]) % int(V)
 
 
 _MT_INDEX = {}
@@ -198,7 +215,10 @@ class GridAttn(nn.Module):
                  num_layers=3, side_length=32, world_scale=0.6, z_near_far_scale=0.8, depth_scale=2.0,
                  depth_shift=0.5, n_pts_per_ray=3, use_t=True, keep_top_k_views=False, top_k=4, device="cpu"):
         super().__init__()
-        assert not keep_top_k_views, "top-k view selection is dead code in the reference configs"
+        # windowed aggregation (:375-384).  A construction-time property like n_pts_per_ray: the engines' buffers are sized by it, so
+        # flipping it on a live model needs ViewFusion.invalidate_packed().  The parameters are the same either way.
+        self.keep_top_k_views, self.top_k = bool(keep_top_k_views), int(top_k)
+        assert not self.keep_top_k_views or 1 <= self.window <= 16, f"top_k={top_k}: the window {self.window} exceeds 16 rows per 3-D point"
         assert hidden_size == 256, "the token kernel is specialised for 256-channel feature maps"
         assert in_channels == 5, "mvd_zembed reads 4 VAE + 1 depth latent channels (configs/*.yaml: in_channels: 5)"
         self.input_size, self.hidden_size, self.output_dim = input_size, hidden_size, output_dim
@@ -230,12 +250,23 @@ class GridAttn(nn.Module):
             self._fused = (stream.to(device), vecs.to(device))
         return self._fused
 
+    @property
+    def window(self):
+        """W, the reference view slots per 3-D point with keep_top_k_views; 0 = all V views (window_size)."""
+        return window_size(self.keep_top_k_views, self.top_k)
+
+    def rows_per_point(self, V):
+        """Token rows (attention sequence length) per 3-D point of a V-view rig: the window, else V."""
+        return self.window or int(V)
+
     def fused_supported(self, V, T):
-        """Whether the single-launch aggregation kernel serves V reference views / T = nseq * V tokens: any 1 <= V <= 16 (the kernel
-        pads the views of a 3-D point to the next power of two and masks the padding: the reference's 15 / 7 / 5 views included)."""
+        """Whether the single-launch aggregation kernel serves a V-view rig with T = nseq * rows_per_point(V) tokens: any 1 <= rows <= 16
+        (the kernel pads the slots of a 3-D point to the next power of two and masks the padding: the reference's 15 / 7 / 5 views
+        included).  Without a window rows = V, as before; with one V itself is not bounded."""
         blocks = self.aggregation_transformer.layer_list
-        Vp = 1 << max(int(V) - 1, 0).bit_length()
-        return (1 <= V <= 16 and (T // V * Vp) % 64 == 0 and T % V == 0 and self.hidden_size == 256 and len(blocks) == 3 and
+        R = self.rows_per_point(V)
+        Vp = 1 << max(R - 1, 0).bit_length()
+        return (V >= 1 and 1 <= R <= 16 and (T // R * Vp) % 64 == 0 and T % R == 0 and self.hidden_size == 256 and len(blocks) == 3 and
                 all(b.num_heads == 8 and b.mlp.fc1.out_features == 512 for b in blocks))
 
     def run(self, ctx, x, depth_noise, steps, it, cams_rec, in_cam_rec, input_latents, c, vol_out, V, S, D, q0=0, Vq=None,
@@ -244,8 +275,11 @@ class GridAttn(nn.Module):
         whose first Vq*S*S*D rows receive the feature frustum (row = ((v*S + y)*S + x)*D + d) of the query views
         [q0, q0+Vq) (all V views by default; a view-parallel rank passes the range it owns).  vol_planes: optional planes
         buffer receiving the frustum as well, in columns [vol_planes_col, vol_planes_col + 768) of its rows.
-        fused: None = the single-launch aggregation kernel (mvd_gridattn_fused) whenever V <= 16, else the unfused chain
+        fused: None = the single-launch aggregation kernel (mvd_gridattn_fused) whenever a point has <= 16 rows, else the unfused chain
         of token kernel + GEMMs; True / False force one of them.
+        With keep_top_k_views a point has W = self.window rows (slot j of query view b = view (b + j - W // 2) mod V, b counted in the whole
+        rig also for a shard q0 / Vq) instead of V; everything below is the same over those rows, and it combines with scenes,
+        per-scene timesteps and q0 / Vq.
         depth_src / depth_steps (overwrite_attn_depth, view_attn_efficient2.py:418-426): a (V,5,S,S) buffer whose channel 4 is the depth
         map to sample around INSTEAD of the x0-style estimate x[:,4] / sqrt(alpha_bar), with a step table whose sqrt(alpha_bar) column
         is 1 (x / 1 is exact) and whose depth-std column is unchanged -- the kernels themselves are the same.
@@ -267,7 +301,9 @@ class GridAttn(nn.Module):
         hip.check(L.mvd_zembed(hip.ptr(input_latents), hip.ptr(z.weight), hip.ptr(z.bias), hip.ptr(in_feat), N, S,
                                hip.stream()))
         nseq = N * Vq * S * S * D
-        T = nseq * V
+        W = self.window                     # 0: all V views
+        R = self.rows_per_point(V)          # rows (slots) per 3-D point
+        T = nseq * R
         dsrc = x if depth_src is None else depth_src
         dsteps = steps if depth_steps is None else depth_steps
         assert (depth_src is None) == (depth_steps is None) and dsrc.shape == x.shape
@@ -296,25 +332,25 @@ class GridAttn(nn.Module):
                 lin = blk.adaLN_modulation[1]
                 ctx.gemv_rows(lin.weight, lin.bias, c, vecs[:, bi * _G4_VEC_BLOCK:bi * _G4_VEC_BLOCK + 1536], act_in=hip.ACT_SILU)
             pool = ctx.ws.planes("ga.pool", nseq, self.hidden_size)
-            hip.check(L.mvd_gridattn_fused_scenes_t(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
-                                                    hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec), hip.ptr(stream),
-                                                    hip.ptr(vecs), hip.ptr(pool), N, V, q0, Vq, S, D, float(self.depth_scale),
-                                                    float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, sst, sst * nv, hip.stream()))
+            hip.check(L.mvd_gridattn_fused_window(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
+                                                  hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec), hip.ptr(stream),
+                                                  hip.ptr(vecs), hip.ptr(pool), N, V, q0, Vq, S, D, float(self.depth_scale),
+                                                  float(self.depth_shift), 3 if ctx.prec_of("ga") == 3 else 4, sst, sst * nv, W, hip.stream()))
             ctx.gemm(pool, w_fin, vol_out, M=nseq, out_planes=vol_planes, out_planes_col=vol_planes_col, kind="ga")
             return vol_out
         tokens = ctx.ws.planes("ga.tokens", T, hip.TOKEN_LD)
-        hip.check(L.mvd_gridattn_tokens_scenes_t(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
-                                                 hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec),
-                                                 hip.ptr(tokens), N, V, q0, Vq, S, D, float(self.depth_scale), float(self.depth_shift),
-                                                 0, hip.stream()))
+        hip.check(L.mvd_gridattn_tokens_window(hip.ptr(dsrc), hip.ptr(depth_noise), hip.ptr(dsteps), hip.ptr(it), hip.ptr(grid_lin),
+                                               hip.ptr(feat), hip.ptr(in_feat), hip.ptr(cams_rec), hip.ptr(in_cam_rec),
+                                               hip.ptr(tokens), N, V, q0, Vq, S, D, float(self.depth_scale), float(self.depth_shift),
+                                               0, W, hip.stream()))
         h = ctx.ws.get("ga.h", (T, self.hidden_size))
         h_alt = ctx.ws.get("ga.h_alt", (T, self.hidden_size))
         ctx.gemm(tokens, w_pre, h, act=hip.ACT_GELU, kind="ga")
         for blk in self.aggregation_transformer.layer_list:
-            h = blk.run(ctx, h, h_alt, c, T, V)
+            h = blk.run(ctx, h, h_alt, c, T, R)
         wl = self.aggregation_transformer.weight_layer
         pool = ctx.ws.planes("ga.pool", nseq, self.hidden_size)
-        hip.check(L.mvd_view_pool(hip.ptr(h), hip.ptr(wl.weight), hip.ptr(wl.bias), hip.ptr(pool), nseq, V, self.hidden_size,
+        hip.check(L.mvd_view_pool(hip.ptr(h), hip.ptr(wl.weight), hip.ptr(wl.bias), hip.ptr(pool), nseq, R, self.hidden_size,
                                   hip.stream()))
         # the frustum is consumed as fp32 (area pooling) and as planes (level-0 to_k / to_v GEMMs): write both
         ctx.gemm(pool, w_fin, vol_out, M=nseq, out_planes=vol_planes, out_planes_col=vol_planes_col, kind="ga")

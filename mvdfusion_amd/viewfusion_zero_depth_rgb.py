@@ -44,7 +44,11 @@ class StepEngine:
 
     scenes = N independent objects denoised together (same V, S, D, cfg, schedule and weights; own cameras, input view, CLIP embedding
     and noise): every per-view buffer holds N*V views scene-major (global view scene*V + v), the per-scene ones (input latents, input
-    camera) N, and the UNet's CFG batch is [N*V conditional rows | N*V null rows].  View-parallel sharding (q0 / Vq) is single-scene only."""
+    camera) N, and the UNet's CFG batch is [N*V conditional rows | N*V null rows].  View-parallel sharding (q0 / Vq) is single-scene only.
+
+    The buffers here go by the rig size V whatever GridAttn's window is; the token / attention arenas that go by the rows of a 3-D point
+    (W with model.view_attn.keep_top_k_views, else V) are workspace buffers keyed by their shape (engine.Workspace), allocated by the
+    first eager step with the window the model was built with and captured by its graphs."""
 
     def __init__(self, model, V, S, D, cfg, device, prec, q0=0, Vq=None, policy=None, scenes=1):
         self.m, self.V, self.S, self.D, self.cfg = model, V, S, D, bool(cfg)
@@ -420,7 +424,10 @@ class ViewFusion(nn.Module):
     def engine(self, V, S, D, cfg, q0=0, Vq=None, scenes=1):
         """The StepEngine of one (V, S, D, cfg, view range, scenes) signature (created on first use, then reused).  scenes = N objects
         denoised together in every step (scene-major buffers, see StepEngine); view-parallel sharding (q0 / Vq) is single-scene only.
-        Engines are kept until invalidate_packed(): each distinct N holds its own workspace, graphs and tuned GEMM shapes."""
+        Engines are kept until invalidate_packed(): each distinct N holds its own workspace, graphs and tuned GEMM shapes.
+        GridAttn's window (view_attn.keep_top_k_views / top_k) is, like n_pts_per_ray, a construction-time property of the model: an
+        engine's GridAttn buffers and captured graphs are sized by the W rows per 3-D point it had when the engine first ran, so
+        flipping it on a live model needs invalidate_packed()."""
         if int(scenes) < 1:
             raise ValueError(f"engine(scenes={scenes}): at least one scene")
         if int(scenes) > 1 and (q0 != 0 or (Vq is not None and Vq != V)):
