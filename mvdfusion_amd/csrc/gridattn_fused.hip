@@ -15,6 +15,9 @@
 // Scenes (mvd_gridattn_fused_scenes): N independent rigs in one launch, each with its own cameras, input view and latents, addressed by the
 // global view index scene * V + view; a scene's rows are a whole number of workgroups (checked at launch), so the scene is workgroup-uniform
 // and no point, wavefront or workgroup straddles two scenes.  The weight stream is shared: every scene's rows read the same slots.
+// The geometry of a row (G1-G3: its point, world point, Plucker coordinates and taps, and the window rule behind win_off) is
+// gridattn_common.hpp, shared with the unfused token kernel and its backward; this file owns what is particular to the fused kernel: the
+// branch-free sin / cos and gather, the row -> slot mapping with its padding, and G4.
 // Activations never touch LDS or HBM: every GEMM is computed as  out^T = W x^T  (MFMA A operand = 16 weight rows, B operand =
 // the wave's 16 activation rows), so a lane holds, for row (lane & 15), four consecutive output channels 16j + 4(lane>>4) + r
 // of each 16-channel tile j -- exactly the register image of the NEXT GEMM's B fragment once the weight k-order inside
@@ -59,19 +62,18 @@ static_assert(G4_SMEM <= 160 * 1024 && G4_BLK_BYTES == 13 * 1024, "LDS budget");
 #endif
 
 struct G4Params {
+  GridGeom g;                     // the point geometry (gridattn_common.hpp)
   long long* dbg;
-  const float *x, *depth_noise, *steps;
-  const int* iter;
-  const float *grid_lin, *feat, *in_feat, *cams, *in_cam;
+  const float *feat, *in_feat;
   const unsigned char* wstream;   // nslots x 32 KiB
   const float* vecs;              // G4_VEC_GRANULES * 256 floats
   u16* pooled_sp;                 // (Nseq, 256) split planes
-  int V, W, Vp, lv, q0, Vq, S, D, nslots;   // V views in the rig; W slots per 3-D point (V, or the window); Vp = 2^lv >= W rows per point
-  int windowed;                             // launch-uniform: 0 = slot j is view j (W = V); 1 = slot j of query view b is (b + win_off[j]) mod V
-  unsigned win_off[8];                      // windowed: (j - W/2) mod V of slot j as 16 bits, two slots per word; slots >= W repeat slot W - 1
-  int nscene, wg_per_scene;                 // scenes in the launch; workgroups per scene (Vq*S*S*D*Vp / 64)
-  int steps_scene_stride, vecs_scene_stride;  // scene n: step row *iter + n * steps_scene_stride, vector table vecs + n * vecs_scene_stride
-  float depth_scale, depth_shift;
+  int W, Vp, lv, nslots;          // W = slots_per_point(g) slots per 3-D point (kept here: deriving it in the kernel costs registers);
+                                  // Vp = 2^lv >= W rows per point
+  unsigned win_off[8];            // g.window != 0: slot j of query view b is view (b + off_j) mod V; off_j = window_view(0, j, W, V) as 16 bits,
+                                  // two slots per word; slots >= W repeat slot W - 1
+  int wg_per_scene;               // workgroups per scene (Vq*S*S*D*Vp / 64)
+  int vecs_scene_stride;          // scene n: vector table vecs + n * vecs_scene_stride
 };
 
 struct Frag {   // one MFMA operand fragment (8 elements) as hi + lo
@@ -104,40 +106,13 @@ __device__ __forceinline__ void mmu_lohi(f32x4& acc, const Frag& w, const Frag& 
 __device__ __forceinline__ void mmu_hilo(f32x4& acc, const Frag& w, const Frag& x) { acc = MVD_MFMA_16x16x32(x.hi, w.lo, acc, 0, 0, 0); }
 __device__ __forceinline__ void mmu_hihi(f32x4& acc, const Frag& w, const Frag& x) { acc = MVD_MFMA_16x16x32(x.hi, w.hi, acc, 0, 0, 0); }
 
-struct Taps {   // grid_sample(bilinear, border, align_corners=True): pixel offsets (in floats, 256 channels / pixel) and weights
-  int o[4];
-  float w[4];
-};
-
-__device__ __forceinline__ Taps make_taps(int S, float gx, float gy) {
-  float ix = ((gx + 1.f) / 2.f) * (float)(S - 1);
-  float iy = ((gy + 1.f) / 2.f) * (float)(S - 1);
-  ix = fminf(fmaxf(ix, 0.f), (float)(S - 1));
-  iy = fminf(fmaxf(iy, 0.f), (float)(S - 1));
-  if (!(ix == ix)) ix = 0.f;
-  if (!(iy == iy)) iy = 0.f;
-  const float x0f = floorf(ix), y0f = floorf(iy);
-  const int x0 = (int)x0f, y0 = (int)y0f;
-  const int x1 = x0 + 1, y1 = y0 + 1;
-  const float wx1 = ix - x0f, wy1 = iy - y0f;
-  const float wx0 = (x0f + 1.f) - ix, wy0 = (y0f + 1.f) - iy;
-  Taps t;
-  const int ys[4] = {y0, y0, y1, y1}, xs[4] = {x0, x1, x0, x1};
-  const float ws[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool ok = ys[k] < S && xs[k] < S;
-    t.o[k] = ok ? (ys[k] * S + xs[k]) * 256 : 0;
-    t.w[k] = ok ? ws[k] : 0.f;      // bilinear4() skips such taps; a zero weight on an in-range pixel adds exactly 0
-  }
-  return t;
-}
-
+// the bilinear sample of bilinear_taps<true> taps (branch-free: every tap is loaded, the ones beyond the border with weight 0 from pixel 0;
+// bilinear4() skips those, and a zero weight on an in-range pixel adds exactly 0)
 __device__ __forceinline__ f32x4 gather4(const float* __restrict__ fmap, const Taps& t, int ch) {
   f32x4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const float4 v = *(const float4*)(fmap + t.o[k] + ch);
+    const float4 v = *(const float4*)(fmap + t.pix[k] * 256 + ch);
     o[0] += v.x * t.w[k];
     o[1] += v.y * t.w[k];
     o[2] += v.z * t.w[k];
@@ -163,10 +138,8 @@ __device__ __forceinline__ float sincos_sel(float a, bool want_cos) {
   return (q & 2) ? -v : v;
 }
 
-// harmonic embedding element e of [sin(dim*7) | cos(dim*7) | x(dim)] without runtime-indexed arrays
-struct Vec6 {   // named members (not an array): the selects below must stay selects, not become a runtime-indexed load
-  float a, b, c, d, e, f;
-};
+// harmonic embedding element e of [sin(dim*7) | cos(dim*7) | x(dim)] without runtime-indexed arrays: Plucker has named members so that the
+// selects below stay selects and never become a runtime-indexed load
 __device__ __forceinline__ float pick6(float a, float b, float c, float d, float e, float f, int i) {   // by VALUE: SSA, never memory
   float r = a;
   r = i == 1 ? b : r;
@@ -178,7 +151,7 @@ __device__ __forceinline__ float pick6(float a, float b, float c, float d, float
 }
 // token columns 512 + e: [ref plucker 90 | ref depth 15 | query plucker 90 | query depth 15 | 1 | zero pad]; each 105-block is
 // [6-vector: sin 42 | cos 42 | x 6][scalar: sin 7 | cos 7 | x 1], harmonic index = dim * 7 + k, omega_k = 0.1 * 2^k
-__device__ __forceinline__ float token_embedding(Vec6 rpl, float rdep, Vec6 qpl, float qdep, int e) {
+__device__ __forceinline__ float token_embedding(Plucker rpl, float rdep, Plucker qpl, float qdep, int e) {
   if (e >= 210) return e == 210 ? 1.0f : 0.0f;
   const bool query = e >= 105;
   const int i = query ? e - 105 : e;                     // index inside one 105-block
@@ -208,11 +181,10 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15, g = lane >> 4;
   const float* const smisc = (const float*)(smem + G4_OFF_MISC);        // index = global index - G4_VEC_MISC
-  const int V = p.V, W = p.W, Vp = p.Vp, lv = p.lv, S = p.S, D = p.D, SS = S * S;
+  const int V = p.g.V, W = p.W, Vp = p.Vp, lv = p.lv, S = p.g.S, SS = S * S;
   const int scene = (int)(blockIdx.x / (unsigned)p.wg_per_scene);        // workgroup-uniform (scalar)
-  // the scene's own timestep: its vector table (adaLN modulation) and step row; both strides are 0 for a shared timestep
+  // the scene's own timestep: its vector table (adaLN modulation; stride 0 for a shared timestep)
   const float* const vecs = p.vecs + (size_t)scene * p.vecs_scene_stride;
-  const float* const steps = p.steps + (size_t)scene * p.steps_scene_stride * MVD_STEP_STRIDE;
 
   // ------------------------------------------------------------------ LDS-DMA engine
   // This wave copies granules [8 wave, 8 wave + 8) of every slot.  The copy is linear (source stride = destination stride = 1 KiB), so
@@ -347,14 +319,11 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
 
   // ------------------------------------------------------------------ G1-G3: this lane's row of the token matrix
   const size_t t_row = (size_t)blockIdx.x * 64 + wave * 16 + r16;
-  const size_t pt = t_row >> lv;
   const int vslot = (int)(t_row & (size_t)(Vp - 1));
   const bool pad_row = vslot >= W;                       // padding slot: computed like the last real slot, masked below
-  const int d = (int)(pt % D);
-  const int pix = (int)((pt / D) % SS);
-  const int b = p.q0 + (int)(pt / ((size_t)D * SS)) - scene * p.Vq;      // query view inside the scene (its index in the whole rig)
+  const GeomPoint q = decode_point(p.g, t_row >> lv, scene);
   int vr = pad_row ? W - 1 : vslot;                      // reference view of this row: all views -> the slot itself
-  if (p.windowed) {                                      // window -> the rig neighbour (b + slot - W/2) mod V, offsets from the host
+  if (p.g.window) {                                      // window -> the rig neighbour window_view(b, slot, W, V), offsets from the host
     const int pr = vslot >> 1;
     unsigned w = p.win_off[0];
     w = pr == 1 ? p.win_off[1] : w;
@@ -364,64 +333,24 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
     w = pr == 5 ? p.win_off[5] : w;
     w = pr == 6 ? p.win_off[6] : w;
     w = pr == 7 ? p.win_off[7] : w;
-    vr = b + (int)((w >> ((vslot & 1) * 16)) & 0xffffu);
+    vr = q.b + (int)((w >> ((vslot & 1) * 16)) & 0xffffu);
     if (vr >= V) vr -= V;
   }
-  const int gv0 = scene * V;                                             // global index of the scene's view 0
   // geometry of this lane's row: world point, Plucker coordinates, bilinear taps in the reference view and the input view
-  Vec6 qpl, rpl;
-  float rdep, depth;
+  Plucker qpl, rpl;
+  float depth;
   Taps tr, ti;
   {
-    const int it = p.iter[0];
-    const float sqrt_ac = steps[(size_t)it * MVD_STEP_STRIDE + 1];
-    const float dstd = steps[(size_t)it * MVD_STEP_STRIDE + 2];
-    const float dch = p.x[((size_t)(gv0 + b) * 5 + 4) * SS + pix] / sqrt_ac;
-    const float smp = dch + dstd * p.depth_noise[(((size_t)it * p.nscene * V + gv0 + b) * D + d) * SS + pix];
-    depth = fminf(fmaxf((smp + 1.0f) / 2.0f, 0.f), 1.f) * p.depth_scale + p.depth_shift;
-    const Cam cb = load_cam(p.cams + (size_t)(gv0 + b) * MVD_CAM_RECORD);
-    const float ndx = p.grid_lin[pix % S], ndy = p.grid_lin[pix / S];
-    float p1[3], p2[3], dir[3], org[3], X[3];
-    unproject(cb, ndx, ndy, 1.f, p1);
-    unproject(cb, ndx, ndy, 2.f, p2);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      dir[j] = p2[j] - p1[j];
-      org[j] = p1[j] - dir[j];
-      X[j] = org[j] + depth * dir[j];
-    }
-    {
-      const float nrm = fmaxf(sqrtf(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2]), 1e-12f);
-      qpl.a = dir[0] / nrm;
-      qpl.b = dir[1] / nrm;
-      qpl.c = dir[2] / nrm;
-      qpl.d = cb.C[1] * qpl.c - cb.C[2] * qpl.b;
-      qpl.e = cb.C[2] * qpl.a - cb.C[0] * qpl.c;
-      qpl.f = cb.C[0] * qpl.b - cb.C[1] * qpl.a;
-    }
-    const Cam cv = load_cam(p.cams + (size_t)(gv0 + vr) * MVD_CAM_RECORD);
-    {
-      const float rd[3] = {X[0] - cv.C[0], X[1] - cv.C[1], X[2] - cv.C[2]};
-      const float nr = sqrtf(rd[0] * rd[0] + rd[1] * rd[1] + rd[2] * rd[2]);
-      rdep = nr;
-      const float nn = fmaxf(nr, 1e-12f);
-      rpl.a = rd[0] / nn;
-      rpl.b = rd[1] / nn;
-      rpl.c = rd[2] / nn;
-      rpl.d = cv.C[1] * rpl.c - cv.C[2] * rpl.b;
-      rpl.e = cv.C[2] * rpl.a - cv.C[0] * rpl.c;
-      rpl.f = cv.C[0] * rpl.b - cv.C[1] * rpl.a;
-    }
-    {
-      float u, v;
-      project(cv, X, u, v);
-      tr = make_taps(S, -u, -v);
-      const Cam ci = load_cam(p.in_cam + (size_t)scene * MVD_CAM_RECORD);
-      project(ci, X, u, v);
-      ti = make_taps(S, -u, -v);
-    }
+    const Cam cb = view_cam(p.g, q, q.b);
+    float X[3], dir[3];
+    depth = world_point(p.g, q, cb, X, dir);
+    qpl = plucker(dir[0], dir[1], dir[2], cb.C);
+    const Cam cv = view_cam(p.g, q, vr);
+    rpl = plucker_to(cv, X);
+    tr = view_taps<true>(cv, X, S);
+    ti = view_taps<true>(input_cam(p.g, q), X, S);
   }
-  const float* fref = p.feat + (size_t)(gv0 + vr) * SS * 256;
+  const float* fref = p.feat + (size_t)(q.gv0 + vr) * SS * 256;
   const float* const fin = p.in_feat + (size_t)scene * SS * 256;
   // ------------------------------------------------------------------ pre_layer: Linear(723 -> 256) + GELU
   f32x4 h[16];          // residual stream: tile j = channels 16j + 4g + r of row r16
@@ -466,7 +395,7 @@ __global__ __launch_bounds__(256) void g4_fused_kernel(G4Params p) {
     float v[8];
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj)
-      v[jj] = token_embedding(rpl, rdep, qpl, depth, 32 * ks + (jj < 4 ? 4 * g + jj : 16 + 4 * g + jj - 4));
+      v[jj] = token_embedding(rpl, rpl.norm, qpl, depth, 32 * ks + (jj < 4 ? 4 * g + jj : 16 + 4 * g + jj - 4));
     slot_16tiles(make_frag(v));
   }
   {
@@ -731,49 +660,37 @@ extern "C" int mvd_gridattn_fused_window(const float* x, const float* depth_nois
                                          const float* in_cam, const void* wstream, const float* vecs, void* pooled_sp, int nscene, int V,
                                          int q0, int Vq, int S, int D, float depth_scale, float depth_shift, int prec, int steps_scene_stride,
                                          int vecs_scene_stride, int window, mvd_stream_t stream) {
-  MVD_CHECK_ARG(x && depth_noise && steps && iter && grid_lin && feat && in_feat && cams && in_cam && wstream && vecs && pooled_sp,
-                "mvd_gridattn_fused: null pointer");
-  MVD_CHECK_ARG(nscene >= 1, "mvd_gridattn_fused_scenes: nscene=%d (>= 1)", nscene);
-  MVD_CHECK_ARG(steps_scene_stride >= 0 && vecs_scene_stride >= 0 && vecs_scene_stride % 4 == 0 &&
-                    (nscene > 1 || (steps_scene_stride == 0 && vecs_scene_stride == 0)),
-                "mvd_gridattn_fused_scenes_t: steps_scene_stride=%d, vecs_scene_stride=%d (>= 0, vecs stride a multiple of 4; both 0 when "
-                "nscene = 1)", steps_scene_stride, vecs_scene_stride);
-  MVD_CHECK_ARG(window == 0 || (window >= 1 && (window & 1)), "mvd_gridattn_fused_window: window=%d (0 = all views, else odd)", window);
-  const int W = window ? window : V;                      // slots (attention sequence) per 3-D point
-  MVD_CHECK_ARG(V >= 1 && W <= 16, "mvd_gridattn_fused: %d slots per point outside [1, 16] (V=%d, window=%d; use the unfused path)", W, V,
-                window);
+  G4Params p;
+  p.g = {x, depth_noise, steps, iter, grid_lin, cams, in_cam, nscene, V, q0, Vq, S, D, depth_scale, depth_shift, steps_scene_stride, window};
+  if (const int e = check_geom("mvd_gridattn_fused_window", p.g)) return e;      // (more than 16 slots per point: the unfused path)
+  MVD_CHECK_ARG(feat && in_feat && wstream && vecs && pooled_sp, "mvd_gridattn_fused_window: null pointer");
+  MVD_CHECK_ARG(vecs_scene_stride >= 0 && vecs_scene_stride % 4 == 0 && (nscene > 1 || vecs_scene_stride == 0),
+                "mvd_gridattn_fused_window: vecs_scene_stride=%d (>= 0, a multiple of 4; 0 when nscene = 1)", vecs_scene_stride);
   MVD_CHECK_ARG(window == 0 || V <= 0xffff, "mvd_gridattn_fused_window: V=%d (<= 65535 with a window)", V);
+  const int W = slots_per_point(p.g);                     // slots (attention sequence) per 3-D point
   int lv = 0;
   while ((1 << lv) < W) ++lv;
   const int Vp = 1 << lv;
-  MVD_CHECK_ARG(q0 >= 0 && Vq > 0 && q0 + Vq <= V && S > 1 && D > 0, "mvd_gridattn_fused: bad shape");
-  MVD_CHECK_ARG(prec == MVD_PREC_X3 || prec == MVD_PREC_X4, "mvd_gridattn_fused: prec %d (MVD_PREC_X3 or MVD_PREC_X4)", prec);
+  MVD_CHECK_ARG(prec == MVD_PREC_X3 || prec == MVD_PREC_X4, "mvd_gridattn_fused_window: prec %d (MVD_PREC_X3 or MVD_PREC_X4)", prec);
   MVD_CHECK_ARG(((uintptr_t)wstream & 15) == 0 && ((uintptr_t)vecs & 15) == 0 && ((uintptr_t)pooled_sp & 127) == 0,
-                "mvd_gridattn_fused: wstream / vecs must be 16-byte, pooled_sp 128-byte aligned");
+                "mvd_gridattn_fused_window: wstream / vecs must be 16-byte, pooled_sp 128-byte aligned");
   const size_t Ts = (size_t)Vq * S * S * D * Vp;          // token rows of one scene incl. the padding slots
   // a scene = whole workgroups: the kernel takes the scene from blockIdx.x, and no point / wavefront / workgroup straddles two scenes
-  MVD_CHECK_ARG(Ts % 64 == 0, "mvd_gridattn_fused: padded token count %zu per scene must be a multiple of 64", Ts);
-  MVD_CHECK_ARG(Ts / 64 <= 0x7fffffff && (Ts / 64) * (size_t)nscene <= 0x7fffffff, "mvd_gridattn_fused: grid too large");
-  G4Params p;
+  MVD_CHECK_ARG(Ts % 64 == 0, "mvd_gridattn_fused_window: padded token count %zu per scene must be a multiple of 64", Ts);
+  MVD_CHECK_ARG(Ts / 64 <= 0x7fffffff && (Ts / 64) * (size_t)nscene <= 0x7fffffff, "mvd_gridattn_fused_window: grid too large");
   p.dbg = g_g4_dbg;
-  p.x = x; p.depth_noise = depth_noise; p.steps = steps; p.iter = iter; p.grid_lin = grid_lin; p.feat = feat;
-  p.in_feat = in_feat; p.cams = cams; p.in_cam = in_cam; p.wstream = (const unsigned char*)wstream; p.vecs = vecs;
-  p.pooled_sp = (u16*)pooled_sp; p.V = V; p.W = W; p.Vp = Vp; p.lv = lv; p.q0 = q0; p.Vq = Vq; p.S = S; p.D = D; p.nslots = 23 + 3 * 64;
-  p.nscene = nscene; p.wg_per_scene = (int)(Ts / 64);
-  p.steps_scene_stride = steps_scene_stride; p.vecs_scene_stride = vecs_scene_stride;
-  p.depth_scale = depth_scale; p.depth_shift = depth_shift;
-  p.windowed = window != 0;
+  p.feat = feat; p.in_feat = in_feat; p.wstream = (const unsigned char*)wstream; p.vecs = vecs; p.pooled_sp = (u16*)pooled_sp;
+  p.W = W; p.Vp = Vp; p.lv = lv; p.nslots = 23 + 3 * 64;
+  p.wg_per_scene = (int)(Ts / 64);
+  p.vecs_scene_stride = vecs_scene_stride;
   for (int j = 0; j < 8; ++j) p.win_off[j] = 0;
   if (window)
-    for (int j = 0; j < 16; ++j) {
-      const int s = j < W ? j : W - 1;                     // padding slots copy the last real one
-      const unsigned off = (unsigned)((((s - W / 2) % V) + V) % V);
-      p.win_off[j >> 1] |= off << ((j & 1) * 16);
-    }
+    for (int j = 0; j < 16; ++j)      // padding slots copy the last real one
+      p.win_off[j >> 1] |= (unsigned)window_view(0, j < W ? j : W - 1, W, V) << ((j & 1) * 16);
   const dim3 grid((unsigned)(Ts / 64 * nscene));
   if (prec == MVD_PREC_X3) hipLaunchKernelGGL(g4_fused_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, p);
   else hipLaunchKernelGGL(g4_fused_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  MVD_CHECK_LAUNCH("mvd_gridattn_fused");
+  MVD_CHECK_LAUNCH("mvd_gridattn_fused_window");
   return 0;
 }
 
