@@ -230,7 +230,21 @@ typedef struct mvd_gemm_desc {
    * role-split convolutions have idle consumer wavefronts and idle HBM bandwidth to spend on the launches behind them.  NULL = off. */
   const struct mvd_prefetch_item_s* pf_items;
   int pf_n;
+  /* Tap schedule of a convolution (a_mode == MVD_A_CONV3X3): which (operand, 32-channel block, tap) each k-tile reads.
+   *   MVD_TAPS_FULL        every channel block of A at all nine taps: K = 9 * Cin (the default).
+   *   MVD_TAPS_CENTRE_TAIL the nine taps of A's Cin / 32 blocks, then Cin2 / 32 blocks of a SECOND operand A2 (split planes, (M, lda2),
+   *                        lda2 >= Cin2, multiples of 32) at the centre tap only: K = 9 * Cin + Cin2 and
+   *                          out = conv3x3(A, W[:, :9 Cin]) + A2 W[:, 9 Cin:]^T
+   *                        in one launch -- a ResBlock's conv2 and its 1x1 skip convolution (openaimodel.py:241,274) without the skip's own
+   *                        GEMM, its fp32 output and the residual read.  The packed weight is the k-tile concatenation of the conv image
+   *                        and the linear image (same N padding and pack scale).  Stride 1, padded, no upsample, Hin == Hout, Win == Wout;
+   *                        served by every cfg except the input-patch kernel (loop 6). */
+  int tap_mode;
+  const void* A2;
+  int lda2, Cin2;
 } mvd_gemm_desc;
+#define MVD_TAPS_FULL 0
+#define MVD_TAPS_CENTRE_TAIL 2 /* (1 is reserved for the four-tap form of a convolution behind a nearest-2x upsample) */
 #define MVD_GNA_SILU 1
 #define MVD_GNA_ROUND_F16 2
 #define MVD_GNA_OUT_UNUSED 4

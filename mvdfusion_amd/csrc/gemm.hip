@@ -413,6 +413,7 @@ static int choose_splits(long tiles, int nk, const TileInfo& ti, int loop, size_
 // returns the patch DMAs per wave and k-tile (1 or 2), 0 when the problem does not fit.
 static int patch_shares(const mvd_gemm_desc& d, const TileInfo& ti) {
   if (d.a_mode != MVD_A_CONV3X3 || d.b_mode != MVD_B_PACKED || d.stride != 1 || d.upsample || d.no_pad_tl) return 0;
+  if (d.tap_mode != MVD_TAPS_FULL) return 0;      // (the patch pipeline walks whole nine-tap channel blocks of one operand)
   if (d.Hin != d.Hout || d.Win != d.Wout || ti.bm != 128) return 0;
   const int W = d.Wout, HW = d.Hout * d.Wout;
   if (ti.bm % W != 0 || (HW >= ti.bm ? HW % ti.bm != 0 : ti.bm % HW != 0)) return 0;
@@ -456,12 +457,25 @@ extern "C" int mvd_gemm(const mvd_gemm_desc* dp, mvd_stream_t stream) {
   MVD_CHECK_ARG(d.A && d.Wp, "mvd_gemm: null operand");
   MVD_CHECK_ARG(((uintptr_t)d.A & 127) == 0 && ((uintptr_t)d.Wp & 127) == 0, "mvd_gemm: operands must be 128-byte aligned");
   if (d.a_mode == MVD_A_CONV3X3) {
-    MVD_CHECK_ARG(d.Cin % 32 == 0 && d.K == 9 * d.Cin, "mvd_gemm: conv needs Cin %% 32 == 0 and K == 9*Cin (Cin=%d K=%d)", d.Cin, d.K);
+    MVD_CHECK_ARG(d.tap_mode == MVD_TAPS_FULL || d.tap_mode == MVD_TAPS_CENTRE_TAIL, "mvd_gemm: tap_mode %d is not served", d.tap_mode);
+    const bool tail = d.tap_mode == MVD_TAPS_CENTRE_TAIL;
+    if (tail) {
+      MVD_CHECK_ARG(d.A2 != nullptr && ((uintptr_t)d.A2 & 127) == 0 && d.Cin2 > 0 && d.Cin2 % 32 == 0 && d.lda2 >= d.Cin2 && d.lda2 % 32 == 0,
+                    "mvd_gemm: the centre-tap tail needs A2 (128-byte aligned), Cin2 %% 32 == 0 and lda2 >= Cin2, a multiple of 32 (Cin2=%d lda2=%d)",
+                    d.Cin2, d.lda2);
+      MVD_CHECK_ARG(d.stride == 1 && !d.upsample && !d.no_pad_tl && d.Hin == d.Hout && d.Win == d.Wout && d.b_mode == MVD_B_PACKED,
+                    "mvd_gemm: the centre-tap tail serves stride-1 padded convolutions with Hin == Hout, Win == Wout and a packed weight");
+      MVD_CHECK_ARG((long long)d.M * 2 * d.lda2 < (1ll << 31), "mvd_gemm: A2 is addressed with 32-bit offsets (M=%d lda2=%d)", d.M, d.lda2);
+    }
+    MVD_CHECK_ARG(d.Cin % 32 == 0 && d.K == 9 * d.Cin + (tail ? d.Cin2 : 0),
+                  "mvd_gemm: conv needs Cin %% 32 == 0 and K == 9*Cin (+ Cin2 with a centre-tap tail) (Cin=%d Cin2=%d K=%d)", d.Cin,
+                  tail ? d.Cin2 : 0, d.K);
     MVD_CHECK_ARG(d.M == d.B * d.Hout * d.Wout, "mvd_gemm: conv M mismatch");
     MVD_CHECK_ARG(d.stride == 1 || d.stride == 2, "mvd_gemm: conv stride must be 1 or 2");
     if (d.upsample) MVD_CHECK_ARG(d.stride == 1 && d.Hout == 2 * d.Hin && d.Wout == 2 * d.Win, "mvd_gemm: upsample geometry");
   } else {
     MVD_CHECK_ARG(d.a_mode == MVD_A_DENSE, "mvd_gemm: bad a_mode");
+    MVD_CHECK_ARG(d.tap_mode == MVD_TAPS_FULL, "mvd_gemm: tap_mode %d needs a_mode == MVD_A_CONV3X3", d.tap_mode);
     MVD_CHECK_ARG(d.lda >= d.K && d.lda % 32 == 0, "mvd_gemm: lda=%d must be >= K=%d and a multiple of 32", d.lda, d.K);
   }
   if (d.out_sp) MVD_CHECK_ARG(d.ldp > 0 && d.ldp % 32 == 0 && ((uintptr_t)d.out_sp & 127) == 0,

@@ -107,6 +107,12 @@ __device__ __forceinline__ float4 epi_store4(const mvd_gemm_desc& d, int m, int 
   return v;
 }
 
+// Tap schedule of the conv k loops (mvd_gemm_desc.tap_mode): k-tile kt < conv_tail_start reads channel block kt / 9 of A at tap kt % 9;
+// the k-tiles from there on -- MVD_TAPS_CENTRE_TAIL only -- read channel block kt - conv_tail_start of A2 at the centre pixel of the row.
+__device__ __forceinline__ int conv_tail_start(const mvd_gemm_desc& d) {
+  return d.tap_mode == MVD_TAPS_CENTRE_TAIL ? 9 * (d.Cin >> 5) : 0x7fffffff;
+}
+
 // conv_patch_kernel: slots of the input patch (128 B each) a workgroup may hold (BM = 128: 288 = 8 images of 4x4 with halo)
 #define MVD_PATCH_SLOTS_MAX 288
 // ... and the depth of its ring of weight stages, by tile width (two patch buffers of 37 KiB + the ring fit the CU's 160 KiB)

@@ -118,6 +118,7 @@ void gemm_kernel(GemmParams p) {
   const u16* a_src[AI];     // dense: per A granule source row base (k = 0, + this lane's chunk)
   bool a_ok[AI];
   int a_tab[AI], a_chunk[AI];   // conv: LDS index of this lane's row in the tap table, chunk offset inside the 128-byte line
+  int a_tail[AI];               // conv, centre-tap tail (mvd_gemm_desc.tap_mode): offset of this lane's row in the second operand A2, -1 past M
 #pragma unroll
   for (int i = 0; i < AI; ++i) {
     const int gi = wave + i * NW;            // A granule index = 8-row group of the block tile
@@ -128,6 +129,7 @@ void gemm_kernel(GemmParams p) {
     a_src[i] = (const u16*)d.A + (size_t)(a_ok[i] ? m : 0) * 2 * d.lda + gc * 8;
     a_tab[i] = (gi * 8 + gr) * 9;
     a_chunk[i] = gc * 8;
+    a_tail[i] = a_ok[i] ? m * 2 * d.lda2 : -1;     // (read in the centre-tap tail only; stride 1, Hin == Hout: the centre pixel of row m is m)
   }
   // conv: source offset (u16 units from d.A, channel 0) of every (tile row, filter tap), -1 where the tap falls into
   // the zero padding or the row is outside M.  Filled once per workgroup; the k loop reads one entry per granule.
@@ -187,6 +189,8 @@ void gemm_kernel(GemmParams p) {
   int a_step[AI];
   int a_off[AI];                              // conv: table entry of the tap staged next
   int c_tap = 0, c_cb = 0;                    // conv: tap and channel block of the k-tile staged next (uniform)
+  int c_kt = kt0;                             // ... and its index: k-tiles >= c_main are the centre-tap tail over A2 (conv_tail_start)
+  const int c_main = conv_tail_start(d);
   if (AMODE == MVD_A_DENSE) {
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
@@ -216,7 +220,11 @@ void gemm_kernel(GemmParams p) {
         src = a_cur[i];
         a_cur[i] += a_step[i];
       } else {
-        src = a_off[i] >= 0 ? (const u16*)d.A + (unsigned)(a_off[i] + c_cb * 64 + a_chunk[i]) : zero;
+        // (no branch: the tail only swaps the operand, the channel block and the row offset -- the steady state stays one basic block)
+        const bool tail = c_kt >= c_main;
+        const u16* const base = (const u16*)(tail ? d.A2 : d.A);
+        const int off = tail ? a_tail[i] : a_off[i];
+        src = off >= 0 ? base + (unsigned)(off + (tail ? c_kt - c_main : c_cb) * 64 + a_chunk[i]) : zero;
       }
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                        (__attribute__((address_space(3))) void*)(sbase + (wave + i * NW) * 1024), 16, 0, 0);
@@ -231,6 +239,7 @@ void gemm_kernel(GemmParams p) {
   };
   auto advance_tap = [&]() {                  // conv bookkeeping after each stage(): next tap, prefetch its table entries
     if (AMODE != MVD_A_DENSE) {
+      ++c_kt;
       if (++c_tap == 9) {
         c_tap = 0;
         ++c_cb;

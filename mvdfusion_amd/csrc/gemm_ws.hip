@@ -88,8 +88,9 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
     const int gr = lane >> 3;
     const u16* zero = (const u16*)g_zero_page;
     const u16* a_cur[AI];
-    int a_step[AI], a_tab[AI], a_chunk[AI], a_off[AI];
-    int c_tap = 0, c_cb = 0;
+    int a_step[AI], a_tab[AI], a_chunk[AI], a_off[AI], a_tail[AI];
+    int c_tap = 0, c_cb = 0, c_kt = kt0;       // (c_kt >= c_main: the centre-tap tail over A2, as gemm_kernel)
+    const int c_main = conv_tail_start(d);
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
       const int gi = lw + i * NL;
@@ -101,6 +102,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
       a_step[i] = ok ? 64 : 0;
       a_tab[i] = (gi * 8 + gr) * 9;
       a_chunk[i] = gc * 8;
+      a_tail[i] = ok ? m * 2 * d.lda2 : -1;
     }
     if (AMODE != MVD_A_DENSE) {
       c_cb = kt0 / 9;
@@ -138,7 +140,10 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
           src = a_cur[i];
           a_cur[i] += a_step[i];
         } else {
-          src = a_off[i] >= 0 ? (const u16*)d.A + (unsigned)(a_off[i] + c_cb * 64 + a_chunk[i]) : zero;
+          const bool tail = c_kt >= c_main;
+          const u16* const base = (const u16*)(tail ? d.A2 : d.A);
+          const int off = tail ? a_tail[i] : a_off[i];
+          src = off >= 0 ? base + (unsigned)(off + (tail ? c_kt - c_main : c_cb) * 64 + a_chunk[i]) : zero;
         }
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                          (__attribute__((address_space(3))) void*)(sbase + (lw + i * NL) * 1024), 16, 0, 0);
@@ -150,6 +155,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
         b_cur[i] += b_step[i];
       }
       if (AMODE != MVD_A_DENSE) {
+        ++c_kt;
         if (++c_tap == 9) {
           c_tap = 0;
           ++c_cb;

@@ -40,6 +40,7 @@ def parse_precision(name):
         policy[k] = int(v)
     return fmt, default, policy
 A_DENSE, A_CONV3X3 = 0, 1
+TAPS_FULL, TAPS_CENTRE_TAIL = 0, 2      # mvd_gemm_desc.tap_mode
 EPI_STORE, EPI_GEGLU, EPI_QKV = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_QUICKGELU = 0, 1, 2, 3
 STEP_STRIDE = 8
@@ -69,6 +70,7 @@ class GemmDesc(C.Structure):
         ("gna_out_sp", _vp), ("gna_gamma", _vp), ("gna_beta", _vp), ("gna_eps", _f), ("gna_flags", _i),
         ("cat_b", _vp), ("cat_cb", _i), ("cat_raw_sp", _vp),
         ("acc_scale_dev", _vp), ("pf_items", _vp), ("pf_n", _i),
+        ("tap_mode", _i), ("A2", _vp), ("lda2", _i), ("Cin2", _i),
     ]
 
 
@@ -227,11 +229,12 @@ def _req(t, dtype=torch.float32):
 class PackedWeight:
     """A weight in the MFMA operand image ([K/32][N/16][hi image | lo image], include/mvd_hip.h) plus its fp32 bias."""
 
-    __slots__ = ("data", "N", "K", "n_real", "bias", "geglu", "conv_cin", "acc_scale")
+    __slots__ = ("data", "N", "K", "n_real", "bias", "geglu", "conv_cin", "acc_scale", "tail_cin")
 
-    def __init__(self, data, N, K, n_real, bias, geglu=False, conv_cin=0, acc_scale=1.0):
+    def __init__(self, data, N, K, n_real, bias, geglu=False, conv_cin=0, acc_scale=1.0, tail_cin=0):
         self.data, self.N, self.K, self.n_real, self.bias, self.geglu, self.conv_cin = data, N, K, n_real, bias, geglu, conv_cin
         self.acc_scale = acc_scale
+        self.tail_cin = tail_cin          # channels (padded to 32) of the centre-tap tail behind the nine-tap blocks (pack_conv3x3_tail)
 
 
 class RowStats:
@@ -391,6 +394,45 @@ def pack_conv3x3(weight, bias=None, like=None):
     return PackedWeight(data, Np, 9 * cin_pad, Cout, b, conv_cin=cin_pad, acc_scale=1.0 / scale)
 
 
+def tap_schedule(cin, cin2=0):
+    """Host mirror of the conv k loop's schedule (csrc/gemm_device.hpp: conv_tail_start): the (operand, 32-channel block, tap) that
+    k-tile kt reads, in order -- operand 0 at the nine taps ky * 3 + kx of each of its cin / 32 blocks, then (centre-tap tail, cin2 > 0)
+    operand 1 at the centre tap 4 of each of its cin2 / 32 blocks.  The packed weight of pack_conv3x3_tail lists its k-tiles in this order."""
+    assert cin % 32 == 0 and cin2 % 32 == 0
+    return [(0, cb, tap) for cb in range(cin // 32) for tap in range(9)] + [(1, cb, 4) for cb in range(cin2 // 32)]
+
+
+def compose_conv_tail_bias(bias, tail_bias):
+    """b + bt of conv3x3(a) + conv1x1(x), added in fp64 and rounded once (weight preprocessing, like the other composed operands)."""
+    if bias is None and tail_bias is None:
+        return None
+    terms = [t.detach().double() for t in (bias, tail_bias) if t is not None]
+    return sum(terms[1:], terms[0]).float()
+
+
+def pack_conv3x3_tail(weight, bias, tail_weight, tail_bias):
+    """[W | Wt] in schedule order (tap_schedule): the 3x3 convolution `weight` (Cout, Cin, 3, 3) of one input and the 1x1 convolution
+    `tail_weight` (Cout, Cin2[, 1, 1]) of a second one as ONE packed operand, bias b + bt -- conv3x3(a) + conv1x1(x) is then one GEMM
+    (hip.gemm(a, W, a2=x planes): mvd_gemm_desc.tap_mode = MVD_TAPS_CENTRE_TAIL).  The image is [K / 32][N / 16] micro-tiles, k-tile
+    major, so it is the conv image followed by the linear image, both at one pack scale."""
+    w = weight.detach().contiguous().float()
+    wt = tail_weight.detach().reshape(tail_weight.shape[0], -1).contiguous().float()
+    Cout, Cin, Cin2 = w.shape[0], w.shape[1], wt.shape[1]
+    assert wt.shape[0] == Cout
+    cin_pad, cin2_pad, Np = (Cin + 31) // 32 * 32, (Cin2 + 31) // 32 * 32, (Cout + 15) // 16 * 16
+    n_main = Np * 9 * cin_pad * 4
+    data = torch.empty(n_main + Np * cin2_pad * 4, dtype=torch.uint8, device=w.device)
+    scale = min(_pack_scale(w, weight), _pack_scale(wt, tail_weight))        # = the scale of max|[W | Wt]|
+    check(lib().mvd_pack_conv3x3_weight(ptr(w), Cout, Cin, cin_pad, scale, ptr(data), stream()))
+    check(lib().mvd_pack_linear_weight(ptr(wt), Cout, Cin2, Cin2, 0, scale, ptr(data[n_main:]), stream()))
+    bsum = compose_conv_tail_bias(bias, tail_bias)
+    b = None
+    if bsum is not None:
+        b = torch.zeros(Np, dtype=torch.float32, device=w.device)
+        b[:Cout] = bsum
+    return PackedWeight(data, Np, 9 * cin_pad + cin2_pad, Cout, b, conv_cin=cin_pad, acc_scale=1.0 / scale, tail_cin=cin2_pad)
+
+
 # ---------------------------------------------------------------------------------------------
 # packed-weight cache invalidation
 # ---------------------------------------------------------------------------------------------
@@ -485,7 +527,7 @@ def split_planes(x, out=None, ldp=None, scale=None):
 def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_NONE, res=None, colscale=None,
          bias_b=None, rows_per_batch=0, epi=EPI_STORE, conv=None, qkv=None, workspace=None, splitk=0, ldo=None,
          out_planes=None, out_planes_col=0, cfg=None, gn_stats=None, gn_hw=0, gn_groups=32, row_stats=None, ln=None, gn_apply=None, cat=None,
-         acc_scale_dev=None):
+         acc_scale_dev=None, a2=None):
     """out = epilogue(A @ W^T).  A: split planes (M, 2*K) int16 (dense) or the NHWC image rows (B*H*W, 2*C) with
     conv=dict(B, Hin, Win, Cin, Hout, Wout, stride, upsample).  qkv = dict(planes=(qh,ql,kh,kl,vh,vl), heads, dhead, L).
     out: fp32 tensor or None; out_planes: split-planes tensor or None (feeds the next GEMM); out_planes_col: first column
@@ -499,6 +541,8 @@ def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_N
     receives act(GroupNorm(out)) -- fused with the split-K reduce when the GEMM splits (mvd_gemm_desc.gna_out_sp; flags GNA_*).
     cat = (skip (M, cb) fp32, raw planes (M, 2 * (N + cb)) or None): the GroupNorm of gn_apply runs over [out | skip] (mvd_gemm_desc.cat_b).
     acc_scale_dev: device scalar multiplied into the accumulator scale (mvd_gemm_desc.acc_scale_dev: the backward's 1 / gradient scale).
+    a2: split planes (M, 2 * lda2) of a second input that a weight of pack_conv3x3_tail reads at the centre tap behind the convolution's
+    own k-tiles: out = epilogue(conv3x3(A) + a2 @ Wt^T) (mvd_gemm_desc.tap_mode = MVD_TAPS_CENTRE_TAIL).
     """
     assert A.dtype == torch.int16, "A must be in split-planes format (see hip.split_planes)"
     d = GemmDesc()
@@ -517,11 +561,17 @@ def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_N
             setattr(d, k, int(conv[k]))
         d.no_pad_tl = int(conv.get("no_pad_tl", 0))
         d.M = conv["B"] * conv["Hout"] * conv["Wout"]
-        assert conv["Cin"] * 9 == W.K, (conv["Cin"], W.K)
+        tail_cin = getattr(W, "tail_cin", 0)
+        assert (a2 is not None) == bool(tail_cin), "a weight of pack_conv3x3_tail needs a2=, and only such a weight takes it"
+        if a2 is not None:
+            assert a2.dtype == torch.int16 and a2.numel() // a2.shape[-1] == d.M and a2.shape[-1] // 2 >= tail_cin
+            d.tap_mode, d.A2, d.lda2, d.Cin2 = TAPS_CENTRE_TAIL, a2.data_ptr(), int(a2.shape[-1] // 2), int(tail_cin)
+        assert conv["Cin"] * 9 + tail_cin == W.K, (conv["Cin"], tail_cin, W.K)
     else:
         d.a_mode = A_DENSE
         d.M = int(M if M is not None else A.numel() // A.shape[-1])
         d.lda = int(lda if lda is not None else A.shape[-1] // 2)
+        assert a2 is None, "a2= (centre-tap tail) belongs to a convolution"
         assert d.lda >= W.K, f"A has {d.lda} columns, packed K is {W.K} (pad A)"
     d.epi, d.act = epi, act
     if out is not None:
@@ -573,7 +623,8 @@ def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_N
         d.workspace = workspace.data_ptr()
         d.workspace_elems = workspace.numel()
     key = (d.M, d.N, d.K, d.a_mode, d.Cin, d.stride, d.upsample, d.no_pad_tl, d.epi, d.prec, res is not None, out is not None,
-           out_planes is not None, splitk, d.b_mode, row_stats is not None, ln is not None, gn_apply is not None, cat[0].shape[-1] if cat is not None else 0)
+           out_planes is not None, splitk, d.b_mode, row_stats is not None, ln is not None, gn_apply is not None, cat[0].shape[-1] if cat is not None else 0,
+           d.tap_mode, d.Cin2)
     if cfg is None:
         tuned = _TUNED.get(key)
         if tuned is None and AUTOTUNE and 2.0 * d.M * d.N * d.K >= AUTOTUNE_MIN_FLOPS:
@@ -695,7 +746,7 @@ class WeightPrefetcher:
 # mvd_gemm_desc.cfg = 1 + CFG_STRIDE * tile + 2 * loop + order (include/mvd_hip.h: MVD_GEMM_CFG_STRIDE)
 CFG_STRIDE = 32
 GNA_SILU, GNA_ROUND_F16, GNA_OUT_UNUSED = 1, 2, 4      # mvd_gemm_desc.gna_flags
-TUNE_CACHE_VERSION = 11            # bump when the cfg encoding or the tuner's problem key changes (save_tuned / load_tuned)
+TUNE_CACHE_VERSION = 12            # bump when the cfg encoding or the tuner's problem key changes (save_tuned / load_tuned)
 GEMM_TILES = ((64, 64, 2, 2), (128, 128, 2, 4), (128, 80, 4, 1), (64, 80, 4, 1), (128, 160, 4, 2))     # BM, BN, WM, WN
 GEMM_LOOPS = (2, 3, 4, None, 6, 7, "patch", "ws")  # template STAGES of gemm_kernel: 2 = plain, 3 = register-pipelined, 4 = staggered wave
                                  # groups (3 LDS buffers), 6 / 7 = register-pipelined over a ring of <= 4 / <= 8 LDS buffers; "patch" = conv_patch_kernel

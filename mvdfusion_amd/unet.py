@@ -87,19 +87,26 @@ class ResBlock(TimestepBlock):
             nn.Conv2d(channels, self.out_channels, 1)
         self._p = None
 
-    def packed(self):
+    def packed(self, fuse_skip=True):
+        """(conv1, conv2, skip) packed; fuse_skip: a 1x1 skip convolution rides in conv2's operand as its centre-tap tail
+        (hip.pack_conv3x3_tail: [W2 | Wsk], bias b2 + bsk) and `skip` is None -- one image per weight either way."""
+        c1, c2, sk = self.in_layers[2], self.out_layers[3], self.skip_connection
+        fuse = bool(fuse_skip) and not isinstance(sk, nn.Identity)
         if self._p is None:
-            c1, c2 = self.in_layers[2], self.out_layers[3]
-            sk = None if isinstance(self.skip_connection, nn.Identity) else \
-                hip.pack_linear(self.skip_connection.weight, self.skip_connection.bias)
-            self._p = (hip.pack_conv3x3(c1.weight, None), hip.pack_conv3x3(c2.weight, c2.bias), sk)
+            self._p = (hip.pack_conv3x3(c1.weight, None), None, None)
+        if self._p[1] is None or bool(self._p[1].tail_cin) != fuse:      # (the precision policy is a property of the model: packed once)
+            w2 = hip.pack_conv3x3_tail(c2.weight, c2.bias, sk.weight, sk.bias) if fuse else hip.pack_conv3x3(c2.weight, c2.bias)
+            wsk = None if fuse or isinstance(sk, nn.Identity) else hip.pack_linear(sk.weight, sk.bias)
+            self._p = (self._p[0], w2, wsk)
         return self._p
 
     def run(self, ctx, x, H, W, out=None, x_planes=None):
         """x: fp32 (M, Cin) residual stream; x_planes: its split-bf16 planes if the producer already wrote them."""
         B, Ci, Co = ctx.B, self.channels, self.out_channels
         M = B * H * W
-        w1, w2, wsk = self.packed()
+        # conv2(a2) + skip(x) is ONE GEMM over [im2col(a2) | x] when both run at one operand precision (the 1x1 skip as conv2's centre-tap
+        # tail); a policy that sets them apart keeps the skip's own GEMM and the residual read
+        w1, w2, wsk = self.packed(fuse_skip=ctx.prec_of("skip") == ctx.prec_of("conv"))
         geo = dict(B=B, Hin=H, Win=W, Hout=H, Wout=W, stride=1, upsample=0)
         a = ctx.ws.planes("res.a", M, Ci)
         ctx.groupnorm(x, a, self.in_layers[0], B, H * W, Ci, silu=True)
@@ -111,14 +118,17 @@ class ResBlock(TimestepBlock):
         ctx.gemm(a, w1, h, conv=dict(Cin=Ci, **geo), bias=False, bias_b=eb, rows_per_batch=M // eb.shape[0],
                  gn=(B, H * W), kind="conv",
                  gn_apply=(self.out_layers[0], a2, True, True))
-        skip = x
-        if wsk is not None:
-            if x_planes is None:
-                x_planes = hip.split_planes(x, ctx.ws.planes("res.xp", M, Ci))
-            skip = ctx.ws.get("res.skip", (M, Co))
-            ctx.gemm(x_planes, wsk, skip, kind="skip")
+        if (wsk is not None or w2.tail_cin) and x_planes is None:
+            x_planes = hip.split_planes(x, ctx.ws.planes("res.xp", M, Ci))
         if out is None:
             out = ctx.act((M, Co))
+        if w2.tail_cin:
+            ctx.gemm(a2, w2, out, conv=dict(Cin=Co, **geo), a2=x_planes, gn=(B, H * W), kind="conv")
+            return out
+        skip = x
+        if wsk is not None:
+            skip = ctx.ws.get("res.skip", (M, Co))
+            ctx.gemm(x_planes, wsk, skip, kind="skip")
         ctx.gemm(a2, w2, out, conv=dict(Cin=Co, **geo), res=skip, gn=(B, H * W), kind="conv")
         return out
 
