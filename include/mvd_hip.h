@@ -238,13 +238,26 @@ typedef struct mvd_gemm_desc {
    *                        in one launch -- a ResBlock's conv2 and its 1x1 skip convolution (openaimodel.py:241,274) without the skip's own
    *                        GEMM, its fp32 output and the residual read.  The packed weight is the k-tile concatenation of the conv image
    *                        and the linear image (same N padding and pack scale).  Stride 1, padded, no upsample, Hin == Hout, Win == Wout;
-   *                        served by every cfg except the input-patch kernel (loop 6). */
+   *                        served by every cfg except the input-patch kernel (loop 6).
+   *   MVD_TAPS_UP4         the four-tap form of a convolution behind a nearest-2x upsample (upsample == 1, stride 1, packed weight): the
+   *                        3x3 window of output pixel (2i + a, 2j + c) covers a 2x2 block of low-resolution pixels, rows i - 1 + a + dy and
+   *                        columns j - 1 + c + dx (dy, dx = 0, 1), so each of the four output parities (a, c) is a 2x2 convolution of the
+   *                        LOW-resolution image with its own weight, the 3x3 taps that land on one pixel summed at pack time (row weights
+   *                        a = 0: w[0], w[1] + w[2]; a = 1: w[0] + w[1], w[2]; columns alike): K = 4 * Cin, 4/9 of the multiply-accumulates.
+   *                        Wp = the four parity images (index 2a + c) one after the other, each [K / 32][N / 16] micro-tiles with k-tile
+   *                        order (32-channel block, tap dy * 2 + dx), all at one pack scale.  The launch walks its M rows as (parity,
+   *                        image, i, j) -- B * Hin * Win rows per parity, a block tile lies inside one parity -- and stores row (b, 2i + a,
+   *                        2j + c) of the ordinary (B, Hout, Wout, N) output / split-K slab, so everything behind the tile epilogue (split-K
+   *                        reduces, GroupNorm apply, concat) is unchanged.  MVD_EPI_STORE with bias, act, out, out_sp, n_store, split-K,
+   *                        gn_stats (then Hin * Win % 16 == 0), gna_out_sp and cat_b; REFUSED: res, bias_b, colscale, rs_out, the GEGLU /
+   *                        QKV epilogues, no_pad_tl.  Served by every cfg except the input-patch kernel (loop 6). */
   int tap_mode;
   const void* A2;
   int lda2, Cin2;
 } mvd_gemm_desc;
 #define MVD_TAPS_FULL 0
-#define MVD_TAPS_CENTRE_TAIL 2 /* (1 is reserved for the four-tap form of a convolution behind a nearest-2x upsample) */
+#define MVD_TAPS_UP4 1
+#define MVD_TAPS_CENTRE_TAIL 2
 #define MVD_GNA_SILU 1
 #define MVD_GNA_ROUND_F16 2
 #define MVD_GNA_OUT_UNUSED 4

@@ -430,6 +430,7 @@ static bool cfg_supported(const mvd_gemm_desc& d, int cfg) {
   const int tile = (cfg - 1) / MVD_GEMM_CFG_STRIDE, loop = ((cfg - 1) % MVD_GEMM_CFG_STRIDE) >> 1;
   if (loop >= MVD_GEMM_LOOPS) return false;
   if (tile >= 2 && d.epi != MVD_EPI_STORE) return false;
+  if (d.a_mode == MVD_A_CONV3X3 && d.tap_mode == MVD_TAPS_UP4 && (d.epi != MVD_EPI_STORE || !d.upsample)) return false;      // (the four-tap form)
   const int waves = kTiles[tile].waves;
   if ((loop == 2 || loop == 3) && waves != 8) return false;
   if (loop == 3 || loop >= 8) return false;                    // removed (never selected by the tuner): the four-buffer staggered loop, the two
@@ -449,6 +450,7 @@ extern "C" int mvd_gemm(const mvd_gemm_desc* dp, mvd_stream_t stream) {
   MVD_CHECK_ARG(dp != nullptr, "mvd_gemm: null descriptor");
   GemmParams p;
   p.d = *dp;
+  p.up4_tpp = p.up4_mq = 0;
   mvd_gemm_desc& d = p.d;
   MVD_CHECK_ARG(d.M > 0 && d.N > 0 && d.K > 0, "mvd_gemm: bad sizes M=%d N=%d K=%d", d.M, d.N, d.K);
   MVD_CHECK_ARG(d.K % 32 == 0, "mvd_gemm: K=%d must be a multiple of 32 (pad the packed weight)", d.K);
@@ -457,8 +459,19 @@ extern "C" int mvd_gemm(const mvd_gemm_desc* dp, mvd_stream_t stream) {
   MVD_CHECK_ARG(d.A && d.Wp, "mvd_gemm: null operand");
   MVD_CHECK_ARG(((uintptr_t)d.A & 127) == 0 && ((uintptr_t)d.Wp & 127) == 0, "mvd_gemm: operands must be 128-byte aligned");
   if (d.a_mode == MVD_A_CONV3X3) {
-    MVD_CHECK_ARG(d.tap_mode == MVD_TAPS_FULL || d.tap_mode == MVD_TAPS_CENTRE_TAIL, "mvd_gemm: tap_mode %d is not served", d.tap_mode);
-    const bool tail = d.tap_mode == MVD_TAPS_CENTRE_TAIL;
+    MVD_CHECK_ARG(d.tap_mode == MVD_TAPS_FULL || d.tap_mode == MVD_TAPS_CENTRE_TAIL || d.tap_mode == MVD_TAPS_UP4,
+                  "mvd_gemm: tap_mode %d is not served", d.tap_mode);
+    const bool tail = d.tap_mode == MVD_TAPS_CENTRE_TAIL, up4 = d.tap_mode == MVD_TAPS_UP4;
+    if (up4) {
+      MVD_CHECK_ARG(d.upsample == 1 && d.stride == 1 && !d.no_pad_tl && d.b_mode == MVD_B_PACKED,
+                    "mvd_gemm: tap_mode MVD_TAPS_UP4 (the four-tap form) serves stride-1 padded convolutions behind a nearest-2x upsample with a packed weight");
+      MVD_CHECK_ARG(d.epi == MVD_EPI_STORE, "mvd_gemm: tap_mode MVD_TAPS_UP4 (the four-tap form) serves MVD_EPI_STORE only (epi=%d)", d.epi);
+      MVD_CHECK_ARG(!d.res && !d.bias_b && !d.colscale && !d.rs_out,
+                    "mvd_gemm: tap_mode MVD_TAPS_UP4 (the four-tap form) takes no res, bias_b, colscale or rs_out (its tile rows are not output rows)");
+      if (d.gn_stats)
+        MVD_CHECK_ARG((d.Hin * d.Win) % 16 == 0, "mvd_gemm: tap_mode MVD_TAPS_UP4 (the four-tap form) with gn_stats needs Hin * Win %% 16 == 0 (Hin=%d Win=%d)", d.Hin,
+                      d.Win);
+    }
     if (tail) {
       MVD_CHECK_ARG(d.A2 != nullptr && ((uintptr_t)d.A2 & 127) == 0 && d.Cin2 > 0 && d.Cin2 % 32 == 0 && d.lda2 >= d.Cin2 && d.lda2 % 32 == 0,
                     "mvd_gemm: the centre-tap tail needs A2 (128-byte aligned), Cin2 %% 32 == 0 and lda2 >= Cin2, a multiple of 32 (Cin2=%d lda2=%d)",
@@ -467,9 +480,9 @@ extern "C" int mvd_gemm(const mvd_gemm_desc* dp, mvd_stream_t stream) {
                     "mvd_gemm: the centre-tap tail serves stride-1 padded convolutions with Hin == Hout, Win == Wout and a packed weight");
       MVD_CHECK_ARG((long long)d.M * 2 * d.lda2 < (1ll << 31), "mvd_gemm: A2 is addressed with 32-bit offsets (M=%d lda2=%d)", d.M, d.lda2);
     }
-    MVD_CHECK_ARG(d.Cin % 32 == 0 && d.K == 9 * d.Cin + (tail ? d.Cin2 : 0),
-                  "mvd_gemm: conv needs Cin %% 32 == 0 and K == 9*Cin (+ Cin2 with a centre-tap tail) (Cin=%d Cin2=%d K=%d)", d.Cin,
-                  tail ? d.Cin2 : 0, d.K);
+    MVD_CHECK_ARG(d.Cin % 32 == 0 && d.K == (up4 ? 4 : 9) * d.Cin + (tail ? d.Cin2 : 0),
+                  "mvd_gemm: conv needs Cin %% 32 == 0 and K == 9*Cin (+ Cin2 with a centre-tap tail; 4*Cin in the four-tap form) (Cin=%d Cin2=%d K=%d)",
+                  d.Cin, tail ? d.Cin2 : 0, d.K);
     MVD_CHECK_ARG(d.M == d.B * d.Hout * d.Wout, "mvd_gemm: conv M mismatch");
     MVD_CHECK_ARG(d.stride == 1 || d.stride == 2, "mvd_gemm: conv stride must be 1 or 2");
     if (d.upsample) MVD_CHECK_ARG(d.stride == 1 && d.Hout == 2 * d.Hin && d.Wout == 2 * d.Win, "mvd_gemm: upsample geometry");
@@ -552,11 +565,20 @@ extern "C" int mvd_gemm(const mvd_gemm_desc* dp, mvd_stream_t stream) {
   const TileInfo& ti = kTiles[tile];
   p.tiles_n = cdiv(d.N, ti.bn);
   p.tiles_m = cdiv(d.M, ti.bm);
+  const bool up4 = d.a_mode == MVD_A_CONV3X3 && d.tap_mode == MVD_TAPS_UP4;
+  if (up4) {      // rows = (parity, low-resolution pixel): a block tile lies inside one parity, rows past up4_mq are masked
+    p.up4_mq = d.B * d.Hin * d.Win;
+    p.up4_tpp = cdiv(p.up4_mq, ti.bm);
+    p.tiles_m = 4 * p.up4_tpp;
+  }
   if (order < 0) {
-    // bytes each XCD pulls through its L2 under the two tile orders (8 XCDs, operands are 4 B per element)
+    // bytes each XCD pulls through its L2 under the two tile orders (8 XCDs, operands are 4 B per element).  Four-tap form: parity is the
+    // outermost tile coordinate, so the estimate is that of ONE parity -- its weight image (N x K, a quarter of the packed operand) against
+    // its up4_mq rows, each pixel line read at four taps
+    const int est_tm = up4 ? p.up4_tpp : p.tiles_m;
     const double W = (double)d.N * d.K * 4.0;
-    const double A = (double)d.M * d.K * 4.0 / (d.a_mode == MVD_A_CONV3X3 ? 9.0 : 1.0);
-    const double rep_m = p.tiles_m < 8 ? p.tiles_m : 8, rep_n = p.tiles_n < 8 ? p.tiles_n : 8;
+    const double A = (double)(up4 ? p.up4_mq : d.M) * d.K * 4.0 / (d.a_mode == MVD_A_CONV3X3 ? (up4 ? 4.0 : 9.0) : 1.0);
+    const double rep_m = est_tm < 8 ? est_tm : 8, rep_n = p.tiles_n < 8 ? p.tiles_n : 8;
     order = (W + A * rep_n) < (W * rep_m + A) ? 1 : 0;
   }
   p.m_fastest = order;

@@ -12,6 +12,9 @@ struct GemmParams {
   int splits;
   int tiles_m, tiles_n;
   int m_fastest;
+  // four-tap form (mvd_gemm_desc.tap_mode == MVD_TAPS_UP4; 0 = off): the M axis of the launch is (parity, low-resolution pixel) --
+  // tiles_m = 4 * up4_tpp block tiles, up4_tpp = cdiv(up4_mq, BM) per parity, up4_mq = B * Hin * Win rows per parity
+  int up4_tpp, up4_mq;
 };
 
 // acc_scale of the descriptor times its optional device scalar (mvd_gemm_desc.acc_scale_dev)

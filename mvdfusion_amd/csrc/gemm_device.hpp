@@ -113,6 +113,71 @@ __device__ __forceinline__ int conv_tail_start(const mvd_gemm_desc& d) {
   return d.tap_mode == MVD_TAPS_CENTRE_TAIL ? 9 * (d.Cin >> 5) : 0x7fffffff;
 }
 
+// ... and the taps per channel block the walk wraps at: nine, or four in the four-tap form behind a nearest-2x upsample (MVD_TAPS_UP4).
+__device__ __forceinline__ int conv_taps_per_block(const mvd_gemm_desc& d) { return d.tap_mode == MVD_TAPS_UP4 ? 4 : 9; }
+
+// Block tile of a workgroup: first row m0, first column n0 and -- four-tap form -- the output parity `par` (2a + c; -1 otherwise) of the tile;
+// m0 then counts the low-resolution pixels of that parity (GemmParams.up4_mq of them).  Parity is the OUTERMOST coordinate under both tile
+// orders: the tiles that share a parity's weight image are neighbours in the walk over the XCDs.
+struct TileCoord {
+  int m0, n0, par;
+};
+template <int BM, int BN>
+__device__ __forceinline__ TileCoord tile_coord(const GemmParams& p, int tile) {
+  int par = -1, tpm = p.tiles_m;
+  if (p.up4_tpp) {
+    tpm = p.up4_tpp;
+    const int per = tpm * p.tiles_n;
+    par = tile / per;
+    tile -= par * per;
+  }
+  return {(p.m_fastest ? tile % tpm : tile / p.tiles_n) * BM, (p.m_fastest ? tile / tpm : tile % p.tiles_n) * BN, par};
+}
+
+// Source offset (u16 units from d.A, channel 0) of filter tap `tap` of tile row m, -1 in the zero padding: the per-row tap table of the
+// conv kernels.  par < 0: the nine taps ky * 3 + kx of output pixel m; par >= 0 (four-tap form): tap dy * 2 + dx of low-resolution pixel m
+// for output parity (a, c) = (par >> 1, par & 1) -- the padding of the upsampled image coincides with the padding of the low-resolution one.
+__device__ __forceinline__ int conv_tap_offset(const mvd_gemm_desc& d, int par, int m, int tap) {
+  int b, iy, ix;
+  bool ok;
+  if (par >= 0) {
+    const int hw = d.Hin * d.Win;
+    b = m / hw;
+    const int rem = m - b * hw;
+    const int i = rem / d.Win, j = rem - i * d.Win;
+    iy = i - 1 + (par >> 1) + (tap >> 1);
+    ix = j - 1 + (par & 1) + (tap & 1);
+    ok = tap < 4 && iy >= 0 && iy < d.Hin && ix >= 0 && ix < d.Win;
+  } else {
+    const int hw = d.Hout * d.Wout;
+    b = m / hw;
+    const int rem = m - b * hw;
+    const int oy = rem / d.Wout, ox = rem - oy * d.Wout;
+    const int ky = tap / 3, kx = tap - ky * 3;
+    if (d.upsample) {
+      const int uy = oy + ky - 1, ux = ox + kx - 1;
+      ok = uy >= 0 && uy < d.Hout && ux >= 0 && ux < d.Wout;
+      iy = uy >> 1;
+      ix = ux >> 1;
+    } else {
+      iy = oy * d.stride + ky - (d.no_pad_tl ? 0 : 1);
+      ix = ox * d.stride + kx - (d.no_pad_tl ? 0 : 1);
+      ok = iy >= 0 && iy < d.Hin && ix >= 0 && ix < d.Win;
+    }
+  }
+  return ok ? ((b * d.Hin + iy) * d.Win + ix) * 2 * d.Cin : -1;
+}
+
+// Four-tap form: row mq (image, i, j) of parity `par` of the launch is row (image, 2i + a, 2j + c) of the output.  The ONE place where a
+// tile row becomes a global row; par < 0: the identity.
+__device__ __forceinline__ int epi_out_row(const mvd_gemm_desc& d, int par, int m) {
+  if (par < 0) return m;
+  const int hw = d.Hin * d.Win;
+  const int b = m / hw, rem = m - b * hw;
+  const int i = rem / d.Win, j = rem - i * d.Win;
+  return (b * d.Hout + 2 * i + (par >> 1)) * d.Wout + 2 * j + (par & 1);
+}
+
 // conv_patch_kernel: slots of the input patch (128 B each) a workgroup may hold (BM = 128: 288 = 8 images of 4x4 with halo)
 #define MVD_PATCH_SLOTS_MAX 288
 // ... and the depth of its ring of weight stages, by tile width (two patch buffers of 37 KiB + the ring fit the CU's 160 KiB)
@@ -162,13 +227,16 @@ __device__ __forceinline__ float2 ln_row_stats(const mvd_gemm_desc& d, int m) {
 // caller has passed a workgroup barrier after its last fragment read) so that global traffic is row-contiguous 16-byte accesses.
 template <int BM, int BN, int WM, int WN>
 __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[BM / WM / 16][BN / WN / 16], unsigned char* smem, int m0,
-                                              int n0, int lane, int wave, const float* s_rows = nullptr) {
+                                              int n0, int lane, int wave, const float* s_rows = nullptr, int par = -1) {
   constexpr int WTM = BM / WM, WTN = BN / WN;
   constexpr int TM = WTM / 16, TN = WTN / 16;
   constexpr int LDW = WTN + 4;                        // fp32 pitch of the epilogue staging tile
   constexpr int C4 = WTN / 4;                         // float4 columns of a wave tile row
   const mvd_gemm_desc& d = p.d;
   const int wm = wave / WN, wn = wave % WN;
+  // four-tap form (par >= 0): the tile's rows are low-resolution pixels of one output parity -- Mlim of them -- and reach the output through
+  // epi_out_row; every 16-row slab lies in one image (Hin * Win % 16 == 0 with gn_stats)
+  const int Mlim = par >= 0 ? p.up4_mq : d.M;
   //      (the final barrier above guarantees nobody still reads the stage buffers; each wave owns a private region)
   float* sC = (float*)smem + wave * (WTM * LDW);
   MVD_STAMP_AT(d, wave, 4);
@@ -202,7 +270,8 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
       const int idx = ps * 64 + lane;
       const int row = idx / C4, col = (idx - row * C4) * 4;
       const int m = wm0 + row, n = wn0 + col;
-      if (idx < WTM * C4 && m < d.M && n < d.N) *(float4*)(ws + (size_t)m * d.N + n) = *(const float4*)(sC + row * LDW + col);
+      if (idx < WTM * C4 && m < Mlim && n < d.N)
+        *(float4*)(ws + (size_t)epi_out_row(d, par, m) * d.N + n) = *(const float4*)(sC + row * LDW + col);
     }
     return;
   }
@@ -380,7 +449,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
   const int mrow0 = wm0 + lrow;
   const bool lane_ok = lane < RPC * C4 && n + 3 < d.n_store;
   float* const sL = sC + lrow * LDW + lcol;                  // the lane's four values of chunk 0; chunk ps: + ps * RPC * LDW
-  const int rows_ok = min(WTM - lrow, d.M - mrow0);          // chunk ps is valid for this lane iff ps * RPC < rows_ok
+  const int rows_ok = min(WTM - lrow, Mlim - mrow0);          // chunk ps is valid for this lane iff ps * RPC < rows_ok
   auto pass1 = [&](auto act_c, auto res_c, auto bb_c) {
     constexpr int ACT = decltype(act_c)::value;
     constexpr bool HAS_RES = decltype(res_c)::value, HAS_BB = decltype(bb_c)::value;
@@ -464,11 +533,23 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
 #pragma unroll 1
       for (int ps = 0; ps * RPC < rows_ok; ++ps)
 #pragma unroll 1
-        for (int e = 0; e < 4; ++e) epi_store_elem(d, mrow0 + ps * RPC, n + e, sL[ps * (RPC * LDW) + e]);
+        for (int e = 0; e < 4; ++e) epi_store_elem(d, epi_out_row(d, par, mrow0 + ps * RPC), n + e, sL[ps * (RPC * LDW) + e]);
     }
   }
   MVD_STAMP_AT(d, wave, 9);
-  if (lane_ok) {
+  if (lane_ok && par >= 0) {      // four-tap form: every row has its own output row (no running pointer)
+#pragma unroll 1
+    for (int p0 = 0; p0 * RPC < rows_ok; p0 += 4) {
+      float4 f[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) f[j] = *(const float4*)(sL + ((p0 + j) * RPC < rows_ok ? p0 + j : 0) * (RPC * LDW));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if ((p0 + j) * RPC >= rows_ok) break;
+        epi_put4(d, epi_out_row(d, par, mrow0 + (p0 + j) * RPC), n, f[j]);
+      }
+    }
+  } else if (lane_ok) {
     float* po = d.out ? d.out + (size_t)mrow0 * d.ldo + n : nullptr;
     u16* psp = d.out_sp ? (u16*)d.out_sp + sp_index((size_t)mrow0, d.ldp, n) : nullptr;
     const size_t ostep = (size_t)RPC * d.ldo, sstep = (size_t)RPC * 2 * d.ldp;
@@ -540,12 +621,13 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
       }
       // images at least as tall as the wave tile (gn_hw % WTM == 0): one pair of atomics per wave tile and group fragment -- the
       // 16-row slabs are summed in row order first; shorter images: one pair per slab
-      const bool whole = d.gn_hw % WTM == 0;
+      const int img_rows = par >= 0 ? d.Hin * d.Win : d.gn_hw;      // tile rows per image
+      const bool whole = img_rows % WTM == 0;
       float s1 = 0.f, q1 = 0.f;
 #pragma unroll 1
       for (int sl = 0; sl < WTM / 16; ++sl) {
         const int ms = wm0 + sl * 16;
-        if (ms >= d.M) break;
+        if (ms >= Mlim) break;
         if (!whole) s1 = q1 = 0.f;
         if (okc) {
 #pragma unroll
@@ -555,7 +637,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
             q1 += v * v;
           }
         }
-        if (whole && sl + 1 < WTM / 16 && ms + 16 < d.M) continue;
+        if (whole && sl + 1 < WTM / 16 && ms + 16 < Mlim) continue;
         float ss = s1, qq = q1;
         for (int j = 1; j < jmax; ++j) {
           const float ts = __shfl_down(s1, j, 64), tq = __shfl_down(q1, j, 64);
@@ -564,7 +646,7 @@ __device__ __forceinline__ void tile_epilogue(const GemmParams& p, f32x4 (&acc)[
             qq += tq;
           }
         }
-        if (leader) gn_stats_add(d.gn_stats, ms / d.gn_hw, gidx, d.gn_groups, ss, qq);
+        if (leader) gn_stats_add(d.gn_stats, ms / img_rows, gidx, d.gn_groups, ss, qq);
       }
     }
   }

@@ -93,8 +93,13 @@ void gemm_kernel(GemmParams p) {
   }
   // n-fastest: an XCD re-uses one A row panel across its n-tiles (and streams all of W);
   // m-fastest: an XCD keeps a W column panel resident and streams A -- chosen per problem by bytes moved.
-  const int m0 = (p.m_fastest ? tile % p.tiles_m : tile / p.tiles_n) * BM;
-  const int n0 = (p.m_fastest ? tile / p.tiles_m : tile % p.tiles_n) * BN;
+  const TileCoord tc = tile_coord<BM, BN>(p, tile);
+  const int m0 = tc.m0, n0 = tc.n0;
+  // four-tap form (MVD_TAPS_UP4): par = the tile's output parity, its rows are the mlim low-resolution pixels of that parity and its weight
+  // is image `par` of the four; otherwise par = -1 and the rows are the M rows of the output
+  const int par = AMODE != MVD_A_DENSE ? tc.par : -1;
+  const int mlim = par >= 0 ? p.up4_mq : d.M;
+  const u16* const wp = (const u16*)d.Wp + (par > 0 ? (size_t)par * p.nk * p.nt16 * 1024 : (size_t)0);
   const int kt0 = blockIdx.z * p.kt_per_split;
   const int kt1 = min(p.nk, kt0 + p.kt_per_split);
   const int nkt = kt1 - kt0;
@@ -125,7 +130,7 @@ void gemm_kernel(GemmParams p) {
     const int R = (gi & 1) * 8 + gr;
     const int gc = (lane & 7) ^ ((R >> 1) & 7);
     const int m = m0 + gi * 8 + gr;
-    a_ok[i] = m < d.M;
+    a_ok[i] = m < mlim;
     a_src[i] = (const u16*)d.A + (size_t)(a_ok[i] ? m : 0) * 2 * d.lda + gc * 8;
     a_tab[i] = (gi * 8 + gr) * 9;
     a_chunk[i] = gc * 8;
@@ -134,32 +139,11 @@ void gemm_kernel(GemmParams p) {
   // conv: source offset (u16 units from d.A, channel 0) of every (tile row, filter tap), -1 where the tap falls into
   // the zero padding or the row is outside M.  Filled once per workgroup; the k loop reads one entry per granule.
   int* s_tab = (int*)(smem + SMEM);
-  if (AMODE != MVD_A_DENSE) {
-    const int hw = d.Hout * d.Wout;
+  if (AMODE != MVD_A_DENSE) {      // (nine entries per row in both forms; the four-tap form reads the first four)
     for (int e = tid; e < BM * 9; e += NW * 64) {
       const int row = e / 9, tap = e - row * 9;
       const int m = m0 + row;
-      int off = -1;
-      if (m < d.M) {
-        const int b = m / hw;
-        const int rem = m - b * hw;
-        const int oy = rem / d.Wout, ox = rem - oy * d.Wout;
-        const int ky = tap / 3, kx = tap - ky * 3;
-        int iy, ix;
-        bool ok;
-        if (d.upsample) {
-          const int uy = oy + ky - 1, ux = ox + kx - 1;
-          ok = uy >= 0 && uy < d.Hout && ux >= 0 && ux < d.Wout;
-          iy = uy >> 1;
-          ix = ux >> 1;
-        } else {
-          iy = oy * d.stride + ky - (d.no_pad_tl ? 0 : 1);
-          ix = ox * d.stride + kx - (d.no_pad_tl ? 0 : 1);
-          ok = iy >= 0 && iy < d.Hin && ix >= 0 && ix < d.Win;
-        }
-        if (ok) off = ((b * d.Hin + iy) * d.Win + ix) * 2 * d.Cin;
-      }
-      s_tab[e] = off;
+      s_tab[e] = m < mlim ? conv_tap_offset(d, par, m, tap) : -1;
     }
     __syncthreads();
   }
@@ -174,7 +158,7 @@ void gemm_kernel(GemmParams p) {
       const int n = n0 + gi * 8 + gr;
       b_src[i] = (gi < B_GRAN && n < d.N) ? (const u16*)d.Wp + (size_t)n * 2 * d.ldb + gc * 8 : nullptr;
     } else {
-      b_src[i] = (gi < B_GRAN && nt < p.nt16) ? (const u16*)d.Wp + (size_t)nt * 1024 + (gi & 1) * 512 + lane * 8 : nullptr;
+      b_src[i] = (gi < B_GRAN && nt < p.nt16) ? wp + (size_t)nt * 1024 + (gi & 1) * 512 + lane * 8 : nullptr;
     }
   }
   // elements between consecutive k-tiles: packed weight = one row of micro-tiles; planes = the next 128-byte line of the row
@@ -191,6 +175,7 @@ void gemm_kernel(GemmParams p) {
   int c_tap = 0, c_cb = 0;                    // conv: tap and channel block of the k-tile staged next (uniform)
   int c_kt = kt0;                             // ... and its index: k-tiles >= c_main are the centre-tap tail over A2 (conv_tail_start)
   const int c_main = conv_tail_start(d);
+  const int c_ntap = conv_taps_per_block(d);   // taps per channel block of the walk: 9, or 4 in the four-tap form (uniform)
   if (AMODE == MVD_A_DENSE) {
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
@@ -198,8 +183,8 @@ void gemm_kernel(GemmParams p) {
       a_step[i] = a_ok[i] ? 64 : 0;
     }
   } else {
-    c_cb = kt0 / 9;
-    c_tap = kt0 - c_cb * 9;
+    c_cb = kt0 / c_ntap;
+    c_tap = kt0 - c_cb * c_ntap;
 #pragma unroll
     for (int i = 0; i < AI; ++i) a_off[i] = s_tab[a_tab[i] + c_tap];
   }
@@ -240,7 +225,7 @@ void gemm_kernel(GemmParams p) {
   auto advance_tap = [&]() {                  // conv bookkeeping after each stage(): next tap, prefetch its table entries
     if (AMODE != MVD_A_DENSE) {
       ++c_kt;
-      if (++c_tap == 9) {
+      if (++c_tap == c_ntap) {
         c_tap = 0;
         ++c_cb;
       }
@@ -431,7 +416,7 @@ void gemm_kernel(GemmParams p) {
 
   // ---- epilogue (the final barrier above guarantees nobody still reads the stage buffers; each wave owns a private region)
   MVD_STAMP_AT(d, wave, 3);
-  tile_epilogue<BM, BN, WM, WN>(p, acc, smem, m0, n0, lane, wave, AMODE == MVD_A_DENSE && d.ln_stats != nullptr ? s_rows : nullptr);
+  tile_epilogue<BM, BN, WM, WN>(p, acc, smem, m0, n0, lane, wave, AMODE == MVD_A_DENSE && d.ln_stats != nullptr ? s_rows : nullptr, par);
   MVD_STAMP_AT(d, wave, 8);
 }
 

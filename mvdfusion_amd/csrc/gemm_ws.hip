@@ -46,38 +46,19 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
     const int q = nb >> 3, r = nb & 7, xcd = bid & 7, idx = bid >> 3;
     tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
-  const int m0 = (p.m_fastest ? tile % p.tiles_m : tile / p.tiles_n) * BM;
-  const int n0 = (p.m_fastest ? tile / p.tiles_m : tile % p.tiles_n) * BN;
+  const TileCoord tc = tile_coord<BM, BN>(p, tile);
+  const int m0 = tc.m0, n0 = tc.n0;
+  const int par = AMODE != MVD_A_DENSE ? tc.par : -1;       // four-tap form: output parity of the tile, rows = low-resolution pixels (as gemm_kernel)
+  const int mlim = par >= 0 ? p.up4_mq : d.M;
   const int kt0 = blockIdx.z * p.kt_per_split;
   const int nkt = min(p.nk, kt0 + p.kt_per_split) - kt0;
   float* s_rows = (float*)(smem + SMEM + TAB_BYTES);
   int* s_tab = (int*)(smem + SMEM);
-  if (AMODE != MVD_A_DENSE) {      // conv: source offset of every (tile row, filter tap), -1 in the zero padding / past M (as gemm_kernel)
-    const int hw = d.Hout * d.Wout;
+  if (AMODE != MVD_A_DENSE) {      // conv: source offset of every (tile row, filter tap), -1 in the zero padding / past the rows (as gemm_kernel)
     for (int e = tid; e < BM * 9; e += 512) {
       const int row = e / 9, tap = e - row * 9;
       const int m = m0 + row;
-      int off = -1;
-      if (m < d.M) {
-        const int b = m / hw;
-        const int rem = m - b * hw;
-        const int oy = rem / d.Wout, ox = rem - oy * d.Wout;
-        const int ky = tap / 3, kx = tap - ky * 3;
-        int iy, ix;
-        bool ok;
-        if (d.upsample) {
-          const int uy = oy + ky - 1, ux = ox + kx - 1;
-          ok = uy >= 0 && uy < d.Hout && ux >= 0 && ux < d.Wout;
-          iy = uy >> 1;
-          ix = ux >> 1;
-        } else {
-          iy = oy * d.stride + ky - (d.no_pad_tl ? 0 : 1);
-          ix = ox * d.stride + kx - (d.no_pad_tl ? 0 : 1);
-          ok = iy >= 0 && iy < d.Hin && ix >= 0 && ix < d.Win;
-        }
-        if (ok) off = ((b * d.Hin + iy) * d.Win + ix) * 2 * d.Cin;
-      }
-      s_tab[e] = off;
+      s_tab[e] = m < mlim ? conv_tap_offset(d, par, m, tap) : -1;
     }
     __syncthreads();
   }
@@ -91,13 +72,15 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
     int a_step[AI], a_tab[AI], a_chunk[AI], a_off[AI], a_tail[AI];
     int c_tap = 0, c_cb = 0, c_kt = kt0;       // (c_kt >= c_main: the centre-tap tail over A2, as gemm_kernel)
     const int c_main = conv_tail_start(d);
+    const int c_ntap = conv_taps_per_block(d);
+    const u16* const wp = (const u16*)d.Wp + (par > 0 ? (size_t)par * p.nk * p.nt16 * 1024 : (size_t)0);      // four-tap form: the parity's image
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
       const int gi = lw + i * NL;
       const int R = (gi & 1) * 8 + gr;
       const int gc = (lane & 7) ^ ((R >> 1) & 7);
       const int m = m0 + gi * 8 + gr;
-      const bool ok = m < d.M;
+      const bool ok = m < mlim;
       a_cur[i] = ok ? (const u16*)d.A + (size_t)m * 2 * d.lda + gc * 8 + (size_t)kt0 * 64 : zero;
       a_step[i] = ok ? 64 : 0;
       a_tab[i] = (gi * 8 + gr) * 9;
@@ -105,8 +88,8 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
       a_tail[i] = ok ? m * 2 * d.lda2 : -1;
     }
     if (AMODE != MVD_A_DENSE) {
-      c_cb = kt0 / 9;
-      c_tap = kt0 - c_cb * 9;
+      c_cb = kt0 / c_ntap;
+      c_tap = kt0 - c_cb * c_ntap;
 #pragma unroll
       for (int i = 0; i < AI; ++i) a_off[i] = s_tab[a_tab[i] + c_tap];
     }
@@ -125,7 +108,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
           const int n = n0 + gi * 8 + gr;
           src = (gi < B_GRAN && n < d.N) ? (const u16*)d.Wp + (size_t)n * 2 * d.ldb + gc * 8 : nullptr;
         } else {
-          src = (gi < B_GRAN && nt < p.nt16) ? (const u16*)d.Wp + (size_t)nt * 1024 + (gi & 1) * 512 + lane * 8 : nullptr;
+          src = (gi < B_GRAN && nt < p.nt16) ? wp + (size_t)nt * 1024 + (gi & 1) * 512 + lane * 8 : nullptr;
         }
         b_cur[i] = src ? src + (size_t)kt0 * b_kstride : zero;
         b_step[i] = src ? b_kstride : 0;
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
       }
       if (AMODE != MVD_A_DENSE) {
         ++c_kt;
-        if (++c_tap == 9) {
+        if (++c_tap == c_ntap) {
           c_tap = 0;
           ++c_cb;
         }
@@ -297,7 +280,7 @@ __global__ __launch_bounds__(512) void gemm_ws_kernel(GemmParams p) {
   // register is still reserved -- a late return must not land in a VGPR the epilogue has re-used (free after a k-loop of tens of us)
   asm volatile("s_waitcnt vmcnt(0)" ::"v"(pf_sink) : "memory");
   __syncthreads();
-  tile_epilogue<BM, BN, CM, CN>(p, acc, smem, m0, n0, lane, wave, AMODE == MVD_A_DENSE && d.ln_stats != nullptr ? s_rows : nullptr);
+  tile_epilogue<BM, BN, CM, CN>(p, acc, smem, m0, n0, lane, wave, AMODE == MVD_A_DENSE && d.ln_stats != nullptr ? s_rows : nullptr, par);
   MVD_STAMP_AT(d, wave, 8);
 }
 

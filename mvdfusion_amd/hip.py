@@ -41,6 +41,7 @@ def parse_precision(name):
     return fmt, default, policy
 A_DENSE, A_CONV3X3 = 0, 1
 TAPS_FULL, TAPS_CENTRE_TAIL = 0, 2      # mvd_gemm_desc.tap_mode
+TAPS_UP4 = 1                            # ... the four-tap form of a convolution behind a nearest-2x upsample (pack_conv3x3_up4)
 EPI_STORE, EPI_GEGLU, EPI_QKV = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SILU, ACT_QUICKGELU = 0, 1, 2, 3
 STEP_STRIDE = 8
@@ -229,12 +230,13 @@ def _req(t, dtype=torch.float32):
 class PackedWeight:
     """A weight in the MFMA operand image ([K/32][N/16][hi image | lo image], include/mvd_hip.h) plus its fp32 bias."""
 
-    __slots__ = ("data", "N", "K", "n_real", "bias", "geglu", "conv_cin", "acc_scale", "tail_cin")
+    __slots__ = ("data", "N", "K", "n_real", "bias", "geglu", "conv_cin", "acc_scale", "tail_cin", "up4")
 
-    def __init__(self, data, N, K, n_real, bias, geglu=False, conv_cin=0, acc_scale=1.0, tail_cin=0):
+    def __init__(self, data, N, K, n_real, bias, geglu=False, conv_cin=0, acc_scale=1.0, tail_cin=0, up4=False):
         self.data, self.N, self.K, self.n_real, self.bias, self.geglu, self.conv_cin = data, N, K, n_real, bias, geglu, conv_cin
         self.acc_scale = acc_scale
         self.tail_cin = tail_cin          # channels (padded to 32) of the centre-tap tail behind the nine-tap blocks (pack_conv3x3_tail)
+        self.up4 = up4                    # four parity images of K = 4 * conv_cin each (pack_conv3x3_up4): `data` holds 4 * N * K operands
 
 
 class RowStats:
@@ -402,6 +404,56 @@ def tap_schedule(cin, cin2=0):
     return [(0, cb, tap) for cb in range(cin // 32) for tap in range(9)] + [(1, cb, 4) for cb in range(cin2 // 32)]
 
 
+def up4_schedule(weight):
+    """Host mirror of the four-tap form of conv3x3(nearest2x(x)) (mvd_gemm_desc.tap_mode = MVD_TAPS_UP4).  Output pixel (2i + a, 2j + c)
+    reads the low-resolution rows i - 1 + a + dy and columns j - 1 + c + dx (dy, dx = 0, 1); the 3x3 taps that land on one low-resolution
+    pixel are summed: row weights a = 0: w[0], w[1] + w[2]; a = 1: w[0] + w[1], w[2]; columns alike.  Returns (wq, order):
+    wq (4, Cout, Cin, 2, 2) = the composed 2x2 weight of parity 2a + c, formed in float64 and rounded once to the dtype of `weight`;
+    order = the (parity, 32-channel block, tap dy * 2 + dx) of every k-tile of the packed operand, parity image after parity image."""
+    w = weight.detach()
+    assert w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)
+    rows = torch.tensor([[[1, 0, 0], [0, 1, 1]], [[1, 1, 0], [0, 0, 1]]], dtype=torch.float64, device=w.device)      # [a][dy][ky]
+    wq = torch.einsum("ayk,cxl,oikl->acoiyx", rows, rows, w.double()).reshape(4, w.shape[0], w.shape[1], 2, 2).to(w.dtype)
+    nb = (w.shape[1] + 31) // 32
+    return wq, [(par, cb, tap) for par in range(4) for cb in range(nb) for tap in range(4)]
+
+
+def pack_conv3x3_up4(weight, bias=None):
+    """The weight of conv3x3(nearest2x(x)) as the four composed parity images of up4_schedule, one after the other, each [K / 32][N / 16]
+    micro-tiles with K = 4 * cin_pad in k-tile order (32-channel block, tap), all at ONE pack scale taken from the composed weights (a sum
+    of up to four taps can exceed max|w|).  hip.gemm runs it with tap_mode = MVD_TAPS_UP4 on the LOW-resolution planes."""
+    wq, _ = up4_schedule(weight.detach().float())
+    Cout, Cin = wq.shape[1], wq.shape[2]
+    cin_pad, Np = (Cin + 31) // 32 * 32, (Cout + 15) // 16 * 16
+    K = 4 * cin_pad
+    m = torch.zeros(4, Cout, cin_pad, 4, dtype=torch.float32, device=wq.device)
+    m[:, :, :Cin] = wq.reshape(4, Cout, Cin, 4)
+    m = m.reshape(4, Cout, cin_pad // 32, 32, 4).permute(0, 1, 2, 4, 3).reshape(4, Cout, K).contiguous()      # k = (block * 4 + tap) * 32 + channel
+    img = Np * K * 4
+    data = torch.empty(4 * img, dtype=torch.uint8, device=wq.device)
+    scale = _pack_scale(m)
+    for par in range(4):
+        check(lib().mvd_pack_linear_weight(ptr(m[par]), Cout, K, K, 0, scale, ptr(data[par * img:]), stream()))
+    b = None
+    if bias is not None:
+        b = torch.zeros(Np, dtype=torch.float32, device=wq.device)
+        b[:Cout] = bias.detach().float()
+    return PackedWeight(data, Np, K, Cout, b, conv_cin=cin_pad, acc_scale=1.0 / scale, up4=True)
+
+
+# Which form an Upsample layer's convolution takes (unet.py: Upsample.run; the VAE decoder stays nine-tap).  The four-tap form does 4/9 of
+# the multiply-accumulates over 16/9 of the weight bytes: four-tap from UP4_MIN_ROWS low-resolution rows (B * Hin * Win) upward.  128 rows
+# (the 4^2 -> 8^2 layer of a V = 4 step) is the smallest launch measured, and it still gains (DESIGN.md section 6.00000000); fewer rows are
+# more weight-bound and stay nine-tap.  MVD_UP4_MIN_ROWS=0 forces nine-tap everywhere (A/B runs inside one tree).
+UP4_MIN_ROWS = int(os.environ.get("MVD_UP4_MIN_ROWS", "128"))
+
+
+def use_up4(B, Hin, Win, training=False):
+    """The per-layer rule.  Training forwards stay nine-tap (their weights change every step: composing and packing 16/9 of the bytes per
+    step is not a gain); Hin * Win % 16 == 0 is what the producer GroupNorm statistics of the four-tap launch need."""
+    return UP4_MIN_ROWS > 0 and not training and (Hin * Win) % 16 == 0 and B * Hin * Win >= UP4_MIN_ROWS
+
+
 def compose_conv_tail_bias(bias, tail_bias):
     """b + bt of conv3x3(a) + conv1x1(x), added in fp64 and rounded once (weight preprocessing, like the other composed operands)."""
     if bias is None and tail_bias is None:
@@ -436,7 +488,7 @@ def pack_conv3x3_tail(weight, bias, tail_weight, tail_bias):
 # ---------------------------------------------------------------------------------------------
 # packed-weight cache invalidation
 # ---------------------------------------------------------------------------------------------
-_CACHE_ATTRS = ("_p", "_pg", "_temb", "_xattn", "_head", "_pq", "_q", "_fused", "_lnf")
+_CACHE_ATTRS = ("_p", "_p4", "_pg", "_temb", "_xattn", "_head", "_pq", "_q", "_fused", "_lnf")
 
 
 def params_signature(module):
@@ -566,7 +618,11 @@ def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_N
         if a2 is not None:
             assert a2.dtype == torch.int16 and a2.numel() // a2.shape[-1] == d.M and a2.shape[-1] // 2 >= tail_cin
             d.tap_mode, d.A2, d.lda2, d.Cin2 = TAPS_CENTRE_TAIL, a2.data_ptr(), int(a2.shape[-1] // 2), int(tail_cin)
-        assert conv["Cin"] * 9 + tail_cin == W.K, (conv["Cin"], tail_cin, W.K)
+        if getattr(W, "up4", False):
+            assert a2 is None and conv["Cin"] * 4 == W.K, (conv["Cin"], W.K)          # (the library checks the geometry)
+            d.tap_mode = TAPS_UP4
+        else:
+            assert conv["Cin"] * 9 + tail_cin == W.K, (conv["Cin"], tail_cin, W.K)
     else:
         d.a_mode = A_DENSE
         d.M = int(M if M is not None else A.numel() // A.shape[-1])

@@ -38,15 +38,22 @@ class Upsample(nn.Module):
         super().__init__()
         self.channels, self.out_channels = channels, out_channels or channels
         self.conv = nn.Conv2d(self.channels, self.out_channels, 3, padding=padding)
-        self._p = None
+        self._p = self._p4 = None
 
     def run(self, ctx, x, H, W, out=None):
-        if self._p is None:
-            self._p = hip.pack_conv3x3(self.conv.weight, self.conv.bias)
+        # nine taps over the upsampled image, or four composed taps per output parity over the low-resolution one (hip.use_up4: per layer)
+        if hip.use_up4(ctx.B, H, W, training=ctx.keep_fp32):
+            if self._p4 is None:
+                self._p4 = hip.pack_conv3x3_up4(self.conv.weight, self.conv.bias)
+            wp = self._p4
+        else:
+            if self._p is None:
+                self._p = hip.pack_conv3x3(self.conv.weight, self.conv.bias)
+            wp = self._p
         if out is None:
             out = ctx.act((ctx.B * 4 * H * W, self.out_channels))
         xp = hip.split_planes(x, ctx.ws.planes("updown.x", ctx.B * H * W, self.channels))   # raw residual stream -> planes
-        ctx.gemm(xp, self._p, out, conv=dict(B=ctx.B, Hin=H, Win=W, Cin=self.channels, Hout=2 * H, Wout=2 * W,
+        ctx.gemm(xp, wp, out, conv=dict(B=ctx.B, Hin=H, Win=W, Cin=self.channels, Hout=2 * H, Wout=2 * W,
                                             stride=1, upsample=1), gn=(ctx.B, 4 * H * W), kind="conv")
         return out, 2 * H, 2 * W
 
