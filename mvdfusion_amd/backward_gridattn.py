@@ -94,6 +94,17 @@ def _dit_block_backward(tape, blk, h, c, dh2, T, V):
     return dh, g, dc
 
 
+def fixed_point_scale(mx):
+    """The power of two mvd_gridattn_tokens_backward* multiplies by before it rounds to its 64-bit fixed-point accumulators, for token
+    gradients of largest magnitude mx: the largest gradient lands in [2^40, 2^41), which leaves 40 fractional bits below it and 22 bits
+    of headroom above it for the sum over the rows that reach one texel.  The kernels take the scale as a C float, so the exponent stops
+    at 127: for mx < 2^-87 the largest gradient lands lower (at 2^27 for mx = 2^-100, still past the 24 bits of an fp32 gradient).
+    mx = 0 or not finite: 1."""
+    if not (mx > 0 and math.isfinite(mx)):
+        return 1.0
+    return 2.0 ** min(40 - math.floor(math.log2(mx)), 127)
+
+
 def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     """ga: GridAttn; eng: the StepEngine whose buffers hold this step's inputs (x, depth noise, step table, cameras, input latents);
     c (R, 256) conditioning (eng.t_rows: N rows with per-scene timesteps, else 1); dvol (N*V*S*S*D, 768) gradient of the frustum of the
@@ -152,8 +163,7 @@ def gridattn_backward(ga, tape, eng, c, dvol, V, S, D):
     dtok = dtok.contiguous() if dtok.is_contiguous() else dtok
     base = dtok if dtok.storage_offset() == 0 else dtok.contiguous()
     ldt = base.stride(0)
-    mx = float(dtok[:, :512].abs().max())
-    scale = 2.0 ** (40 - math.floor(math.log2(mx))) if mx > 0 and math.isfinite(mx) else 1.0
+    scale = fixed_point_scale(float(dtok[:, :512].abs().max()))
     dfeat_acc = torch.zeros(N * V, S, S, 256, dtype=torch.int64, device=dev)
     din_acc = torch.zeros(N, S, S, 256, dtype=torch.int64, device=dev)
     hip.check(L.mvd_gridattn_tokens_backward_window(*geo, hip.ptr(eng.cams), hip.ptr(eng.in_cam), hip.ptr(base), ldt, hip.ptr(dfeat_acc),
