@@ -489,6 +489,15 @@ int mvd_cfg_ddim_update(const float* eps_nhwc, int ldc, float* x, float* x0, flo
                         const float* steps, const int* iter, int V, int S, int cfg, float cfg_scale, int do_update,
                         mvd_stream_t stream);
 
+/* Pinned views (sampler.py:109-110,123-124 `overwrite_x_noisy`, generalised): rewrite the first K view rows of every group of
+ * group_views rows of x (groups*group_views, 5, S, S) from known (groups*K, 5, S, S); every other row of x / x0 is left alone.
+ *   mode 0 (clean) : x[g*group_views + k] = known[g*K + k]; x0 untouched; noise / steps / iter may be NULL
+ *   mode 1 (noised): x[row] = steps[*iter][1] * known + steps[*iter][6] * noise[*iter][g*K + k] (sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t)
+ *                    of the step the device counter points at) and x0[row] = known; noise (nsteps, groups*K, 5, S, S)
+ * 0 < K <= group_views.  With S*S % 4 == 0 the rows move as float4: every pointer 16-byte aligned, noise_stride % 4 == 0. */
+int mvd_pin_views(float* x, float* x0, const float* known, const float* noise, size_t noise_stride /* floats between consecutive steps */,
+                  const float* steps, const int* iter, int groups, int group_views, int K, int S, int mode, mvd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);

@@ -361,6 +361,47 @@ __global__ __launch_bounds__(256) void cfg_ddim_kernel(const float* __restrict__
   }
 }
 
+// pin_views: T = float4 when a view row (5*S*S floats) is a whole number of them, else float.  One element of the groups*K pinned rows per
+// thread and pass; rows outside the pinned set are never addressed.  rowlen = elements of T per view row, nstride = per step of noise.
+template <typename T>
+__device__ __forceinline__ T pin_axpy(float sa, const T& k, float s1, const T& n);
+template <>
+__device__ __forceinline__ float pin_axpy<float>(float sa, const float& k, float s1, const float& n) {
+  return sa * k + s1 * n;
+}
+template <>
+__device__ __forceinline__ float4 pin_axpy<float4>(float sa, const float4& k, float s1, const float4& n) {
+  return make_float4(sa * k.x + s1 * n.x, sa * k.y + s1 * n.y, sa * k.z + s1 * n.z, sa * k.w + s1 * n.w);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void pin_views_kernel(T* __restrict__ x, T* __restrict__ x0, const T* __restrict__ known,
+                                                        const T* __restrict__ noise, size_t nstride, const float* __restrict__ steps,
+                                                        const int* __restrict__ iter, int group_views, int K, size_t rowlen, size_t total,
+                                                        int mode) {
+  float sa = 1.f, s1 = 0.f;
+  size_t nbase = 0;
+  if (mode == 1) {
+    const int it = iter[0];
+    const float* st = steps + (size_t)it * MVD_STEP_STRIDE;
+    sa = st[1];
+    s1 = st[6];
+    nbase = (size_t)it * nstride;
+  }
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+    const size_t p = e / rowlen;                 // pinned row g * K + k
+    const size_t off = e - p * rowlen;
+    const size_t dst = ((p / K) * group_views + p % K) * rowlen + off;
+    const T kv = known[e];
+    if (mode == 1) {
+      x[dst] = pin_axpy<T>(sa, kv, s1, noise[nbase + e]);
+      x0[dst] = kv;
+    } else {
+      x[dst] = kv;
+    }
+  }
+}
+
 inline int grid_for(size_t total, int cap = 2048) {
   size_t b = (total + 255) / 256;
   if (b > (size_t)cap) b = cap;
@@ -510,5 +551,32 @@ extern "C" int mvd_cfg_ddim_update(const float* eps_nhwc, int ldc, float* x, flo
   hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, eps_nhwc, ldc, x, x0, eps_out,
                      ddim_noise, steps, iter, V, S, cfg, cfg_scale, do_update, noise_stride);
   MVD_CHECK_LAUNCH("mvd_cfg_ddim_update");
+  return 0;
+}
+
+extern "C" int mvd_pin_views(float* x, float* x0, const float* known, const float* noise, size_t noise_stride, const float* steps,
+                             const int* iter, int groups, int group_views, int K, int S, int mode, mvd_stream_t stream) {
+  MVD_CHECK_ARG(x && known && groups > 0 && group_views > 0 && S > 0 && (mode == 0 || mode == 1),
+                "mvd_pin_views: bad arguments (null x / known, groups=%d, group_views=%d, S=%d, mode=%d)", groups, group_views, S, mode);
+  MVD_CHECK_ARG(K > 0 && K <= group_views, "mvd_pin_views: K=%d pinned views of a %d-view group (0 < K <= group_views)", K, group_views);
+  MVD_CHECK_ARG((long long)groups * group_views <= 0x3fffffff, "mvd_pin_views: groups * group_views too large");
+  const size_t row = (size_t)5 * S * S;
+  if (mode == 1)
+    MVD_CHECK_ARG(x0 && noise && steps && iter && noise_stride >= (size_t)groups * K * row,
+                  "mvd_pin_views: mode 1 needs x0, noise, steps, iter and noise_stride >= groups * K * 5 * S * S");
+  const size_t total = (size_t)groups * K * row;
+  hipStream_t s = (hipStream_t)stream;
+  if (((size_t)S * S) % 4 == 0) {
+    MVD_CHECK_ARG(((uintptr_t)x & 15) == 0 && ((uintptr_t)known & 15) == 0, "mvd_pin_views: x / known must be 16-byte aligned");
+    if (mode == 1)
+      MVD_CHECK_ARG(((uintptr_t)x0 & 15) == 0 && ((uintptr_t)noise & 15) == 0 && noise_stride % 4 == 0,
+                    "mvd_pin_views: x0 / noise must be 16-byte aligned and noise_stride a multiple of 4");
+    hipLaunchKernelGGL(pin_views_kernel<float4>, dim3(grid_for(total / 4)), dim3(256), 0, s, (float4*)x, (float4*)x0, (const float4*)known,
+                       (const float4*)noise, noise_stride / 4, steps, iter, group_views, K, row / 4, total / 4, mode);
+  } else {
+    hipLaunchKernelGGL(pin_views_kernel<float>, dim3(grid_for(total)), dim3(256), 0, s, x, x0, known, noise, noise_stride, steps, iter,
+                       group_views, K, row, total, mode);
+  }
+  MVD_CHECK_LAUNCH("mvd_pin_views");
   return 0;
 }

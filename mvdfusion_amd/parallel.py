@@ -76,10 +76,16 @@ def run_view_parallel(x_T, n_steps, local_step, exchange, force_collective=False
 
 @torch.no_grad()
 def sample_view_parallel(model, batch_cameras, input_latents, input_cameras, clip_embed, cfg_scale, x_T, depth_noise,
-                         ddim_noise, num_steps=None, use_graph=True, group=None, force_collective=False):
-    """DDIMSampler.sample with the views sharded over the ranks of `group` (one process per GPU, RCCL)."""
+                         ddim_noise, num_steps=None, use_graph=True, group=None, force_collective=False, known_latents=None):
+    """DDIMSampler.sample with the views sharded over the ranks of `group` (one process per GPU, RCCL).  Pinned views are refused:
+    ``known_latents`` and DDIMSampler(overwrite_x_noisy=True) belong to DDIMSampler.sample, which owns the query range itself."""
     from .engine import ddim_step_table
     samp = model.ddim
+    if known_latents is not None:
+        raise ValueError("sample_view_parallel: known_latents is not supported (a pinned run uses the query range the ranks shard); "
+                         "use DDIMSampler.sample")
+    if samp.overwrite_x_noisy:
+        raise ValueError("sample_view_parallel: DDIMSampler(overwrite_x_noisy=True) is not supported; use DDIMSampler.sample")
     dev = model._device.device
     V, S, D = clip_embed.shape[0], samp.latent_size, model.view_attn.n_pts_per_ray
     ex = ViewExchange(V, group)

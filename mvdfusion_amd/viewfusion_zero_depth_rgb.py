@@ -81,6 +81,11 @@ class StepEngine:
         self.depth_mode = 0                    # GridAttn samples depth around 0: x[:,4] / sqrt(alpha_bar) (the x0-style estimate);
                                                # 1: the previous step's x0 estimate self.x0[:,4] (DDIMSampler feed_prev_depth);
                                                # 2: self.prev[:,4] (view_attn_efficient2.py:418-426)
+        self.pin = None                        # pinned views: None, or (mode, K) -- the first K view rows of every scene are rewritten from
+                                               # self.known at the start of each step (set_pin; include/mvd_hip.h: mvd_pin_views).
+                                               # mode 0: the clean rows (DDIMSampler overwrite_x_noisy); 1: re-noised to the step's timestep
+        self.known = z(1, 5, S, S)             # (N*K, 5, S, S) clean latents of the pinned views, scene-major
+        self.pin_noise = None                  # mode 1: (rows of the step table, N*K, 5, S, S) standard normal
         self.depth_noise = z(1, NV, D, S, S)
         self.ddim_noise = z(1, NV, 5, S, S)
         self.f256 = _sinusoid_freqs(256).to(dev)
@@ -143,6 +148,37 @@ class StepEngine:
         self.n_rows = int(steps_table.shape[0]) - (self.N - 1) * scene_stride      # the kernels index steps[iter + n * stride] unchecked
         self.rewind()
 
+    def set_pin(self, mode, known, noise=None):
+        """Pin the first K = len(known) / N views of every scene (after set_schedule: the noise has one row per step-table row).  The
+        buffers are static inputs of the captured graphs: a change of shape re-allocates them and clears the graphs, like _set_tables.
+        Engines are cached per signature, so callers reset with clear_pin() in a `finally`."""
+        dev = self.ctx.device
+        nk = int(known.shape[0])
+        K = nk // self.N
+        if mode not in (0, 1) or K < 1 or K * self.N != nk or K > self.V or tuple(known.shape[1:]) != (5, self.S, self.S):
+            raise ValueError(f"StepEngine.set_pin: mode {mode}, known {tuple(known.shape)} for {self.N} scene(s) of {self.V} views at "
+                             f"S = {self.S} (expected (N*K, 5, S, S), 1 <= K <= V)")
+        if mode == 1 and (noise is None or tuple(noise.shape) != (int(self.steps.shape[0]), nk, 5, self.S, self.S)):
+            raise ValueError(f"StepEngine.set_pin: mode 1 needs noise ({int(self.steps.shape[0])}, {nk}, 5, {self.S}, {self.S}), got "
+                             f"{None if noise is None else tuple(noise.shape)}")
+        if self.known.shape != known.shape:
+            self.graphs.clear()
+            self.prefetchers.clear()
+            self.known = known.to(dev, torch.float32).contiguous().clone()
+        else:
+            self.known.copy_(known)
+        if mode == 1:
+            if self.pin_noise is None or self.pin_noise.shape != noise.shape:
+                self.graphs.clear()
+                self.prefetchers.clear()
+                self.pin_noise = noise.to(dev, torch.float32).contiguous().clone()
+            else:
+                self.pin_noise.copy_(noise)
+        self.pin = (int(mode), K)
+
+    def clear_pin(self):
+        self.pin = None
+
     def rewind(self, it=0):
         """Reset the device iteration counter (and its host mirror) to row `it` of the step table."""
         assert 0 <= it < self.n_rows
@@ -166,6 +202,11 @@ class StepEngine:
         sst, R = self.steps_scene_stride, self.t_rows
         if sst and do_update:
             raise ValueError("StepEngine: per-scene timesteps (set_schedule_scenes) are a training step: no DDIM update")
+        if self.pin is not None:   # pinned views first: GridAttn and the UNet input below read the rewritten rows
+            mode, K = self.pin
+            pn = self.pin_noise if mode == 1 else None
+            hip.check(L.mvd_pin_views(hip.ptr(self.x), hip.ptr(self.x0), hip.ptr(self.known), hip.ptr(pn), N * K * 5 * S * S,
+                                      hip.ptr(self.steps), hip.ptr(self.iter), N, V, K, S, mode, st()))
         # embed_time (:276-279): sinusoid(256) -> Linear -> SiLU -> Linear; only row 0 is used downstream (t[:1]) -- one row per scene
         # when every scene has its own timestep
         ts = ctx.ws.get("vf.tsin", (R, 256))
@@ -222,7 +263,7 @@ class StepEngine:
         return self.N if self.steps_scene_stride else 1
 
     def step(self, cfg_scale, do_update, use_graph=True):
-        key = (float(cfg_scale), bool(do_update), int(self.depth_mode), self.steps_scene_stride)
+        key = (float(cfg_scale), bool(do_update), int(self.depth_mode), self.steps_scene_stride, self.pin)
         if self.done >= self.n_rows:
             raise IndexError(f"StepEngine.step: iteration {self.done} is past the {self.n_rows}-row step table "
                              "(set_schedule() / rewind() before stepping again)")
@@ -234,7 +275,8 @@ class StepEngine:
         if g is None:
             # first call runs eagerly (allocates every workspace buffer, packs weights), then capture
             it0 = self.iter.clone()
-            x_keep, x0_keep = self.x.clone(), self.x0.clone()      # (x0: the previous step's estimate is an INPUT under feed_prev_depth)
+            x_keep, x0_keep = self.x.clone(), self.x0.clone()      # (x0: the previous step's estimate is an INPUT under feed_prev_depth;
+                                                                   #  pinned rows need nothing more: every pass rewrites them from static inputs)
             hip.AUTOTUNE = True            # pick the GEMM kernel configuration per problem shape (cached)
             try:
                 self.enqueue(cfg_scale, do_update)
@@ -322,7 +364,7 @@ class ViewFusion(nn.Module):
                  clip_path="", unet_cc_path="", z_scale_factor=0.18215, vae_max_batch=8, objective="noise",
                  loss_type="l2", embed_camera_pose=True, finetune_projection=False, finetune_unet=False,
                  finetune_cross_attn=True, finetune_view_attn=True, feed_prev_depth=False, drop_conditions=False,
-                 vae=None, clip_image_encoder=None, precision=None, reference_eval_dropout=False, **kwargs):
+                 vae=None, clip_image_encoder=None, precision=None, reference_eval_dropout=False, overwrite_x_noisy=False, **kwargs):
         super().__init__()
         assert embed_camera_pose, "this build implements the embed_camera_pose=True configuration of configs/*.yaml"
         self.finetune_projection, self.finetune_unet, self.z_scale_factor = finetune_projection, finetune_unet, z_scale_factor
@@ -385,7 +427,8 @@ class ViewFusion(nn.Module):
         self.register_buffer("_device", torch.tensor([0.0]), persistent=False)
         self.latent_size = int(self.view_attn.input_size)
         self.ddim = DDIMSampler(self, ddim_num_steps=50, ddim_discretize="uniform", ddim_eta=1.0,
-                                latent_size=self.latent_size, z_dim=4, feed_prev_depth=feed_prev_depth)
+                                latent_size=self.latent_size, z_dim=4, feed_prev_depth=feed_prev_depth,
+                                overwrite_x_noisy=overwrite_x_noisy)      # (the sampler's switch, sampler.py:14; reachable from a config here)
         self._engines = {}
         self._packed_sig = None
         assert self.finetune_view_attn is True, "must finetune new view attention layers"
@@ -600,6 +643,16 @@ class ViewFusion(nn.Module):
             its = [{"t": it["t"], "xt": it["xt"][n], "x0": it["x0"][n]} for it in inter]
             out.append((x[n], batch_latents, input_latents, batch_cameras, its))
         return out
+
+    def sample_rig(self, batch, trainer_config, cfg_scale, chunk_views, anchors_per_chunk=1, anchors=None, return_input=False, depth=False,
+                   verbose=True):
+        """``sample`` for a rig of M = trainer_config["train_batch_size"] views, more than one step holds: prepare_batch once for the
+        whole rig, then DDIMSampler.sample_rig generates it in chunks of ``chunk_views`` views, each later chunk with ``anchors_per_chunk``
+        already-generated views held fixed.  Returns what ``sample`` returns (no intermediates: the chunks have their own loops)."""
+        batch_latents, batch_cameras, input_latents, input_cameras, clip_v_embed = self.prepare_batch(batch, trainer_config)
+        x = self.ddim.sample_rig(batch_cameras, input_latents, input_cameras, clip_v_embed, unconditional_scale=cfg_scale,
+                                 chunk_views=chunk_views, anchors_per_chunk=anchors_per_chunk, anchors=anchors, depth=depth, verbose=verbose)
+        return (x, batch_latents, input_latents, batch_cameras, []) if return_input else x
 
     @torch.no_grad()
     def p_losses(self, batch, trainer_config, noise_source=None, _aux=None):
