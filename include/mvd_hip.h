@@ -499,6 +499,47 @@ int mvd_pin_views(float* x, float* x0, const float* known, const float* noise, s
                   const float* steps, const int* iter, int groups, int group_views, int K, int S, int mode, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fusion of the sampled RGB-D views into one depth-consistent coloured point cloud (csrc/fusion.hip; host: mvdfusion_amd/fusion.py).
+ * Not in the reference, whose driver stops at decoded images and a depth PNG; the cameras, NDC convention and depth map are GridAttn's.
+ *
+ * mvd_fuse_points: one output point per pixel of a P x P grid per view, P = S * up (integer up >= 1), ordered
+ *   pt = ((scene*V + b)*P + Y)*P + X.  Fine pixel (Y, X) takes the depth of latent pixel (Y / up, X / up) (nearest replication) and its ray
+ *   goes through its own centre: NDC (ndc_lin[X], ndc_lin[Y]) with ndc_lin (P) = linspace(1 - 1/P, -1 + 1/P, P) in fp32 from the host.
+ *   lat (nscene*V, 5, S, S) NCHW, channel 4 = depth; rgb (nscene*V, 3, P, P) or NULL; cams (nscene*V, MVD_CAM_RECORD).
+ *   Own point : dn = clamp((lat + 1) / 2, 0, 1); foreground iff lo < dn < hi; z = dn * depth_scale + depth_shift (GridAttn's map of a
+ *               depth sample); xyz[pt] = unproject(cam_b, ndc, z) for EVERY point; color[pt] = rgb[.., Y, X] bit for bit (rgb NULL: color
+ *               is not touched and may be NULL); flags[pt] = MVD_FUSE_FOREGROUND or 0.
+ *   Pair rule : for every other view v of the scene's rig, camera-space (xc, yc, zc) and NDC (u, w) of the point.  Seen iff zc > 0,
+ *               |u| <= 1 and |w| <= 1 (NaN: unseen).  Continuous latent pixel ix = clamp((1 - u) * S / 2 - 0.5, 0, S - 1), iy alike --
+ *               geometric pixel centres with a border clamp, NOT GridAttn's align_corners lookup (half a pixel off at the image edge:
+ *               harmless for features, wrong for a depth comparison).  Taps x0 = floor(ix), x1 = min(x0 + 1, S - 1), y alike; if any of
+ *               the four is not foreground the pair casts no vote.  Else zs = bilinear of the four metric depths, dz = zc - zs:
+ *               |dz| <= tau supports, dz < -tau conflicts (the point floats in front of the surface v sees), dz > tau is occlusion.
+ *   support[pt], conflict[pt]: uint8 counts over the other views (1 <= V <= 255; V = 1: all zero).
+ *   stage     : the two forms of the kernel give the same bits.  MVD_FUSE_STAGE_GLOBAL reads the depth maps from global memory;
+ *               MVD_FUSE_STAGE_LDS stages the scene's V depth planes and camera records in LDS per workgroup (refused beyond 128 KiB) and
+ *               walks the scene's points in a grid-stride loop.  MVD_FUSE_STAGE_AUTO is the global form: measured on an MI355X the staged
+ *               one is nowhere faster by more than 1 % and up to 3x slower.
+ *   All fp32, compiled without contraction.  nscene * V * P * P < 2^31.
+ *
+ * mvd_compact_points: stable stream compaction of those arrays.  keep = foreground && support >= min_support && conflict <= max_conflicts;
+ *   kept points go, in point order, to out_xyz (n, 3), out_color (n, 3; with color, both or neither), out_support (n), out_index (n) = pt;
+ *   *count = n (device).  Rows >= n are not touched.  No atomics: wavefront ballots, block counts, one scan, scatter -- deterministic.
+ *   The foreground bit travels in the flags byte written by the fuse kernel (not recomputed from lat: the compaction needs no geometry
+ *   arguments and any caller-made mask can be compacted).  scratch: mvd_compact_points_scratch bytes for npts, 4-byte aligned. */
+#define MVD_FUSE_FOREGROUND 1
+#define MVD_FUSE_STAGE_AUTO 0
+#define MVD_FUSE_STAGE_GLOBAL 1
+#define MVD_FUSE_STAGE_LDS 2
+int mvd_fuse_points(const float* lat, const float* rgb, const float* cams, const float* ndc_lin, float* xyz, float* color,
+                    uint8_t* support, uint8_t* conflict, uint8_t* flags, int nscene, int V, int S, int up, float depth_scale,
+                    float depth_shift, float lo, float hi, float tau, int stage, mvd_stream_t stream);
+size_t mvd_compact_points_scratch(size_t npts);
+int mvd_compact_points(const float* xyz, const float* color, const uint8_t* support, const uint8_t* conflict, const uint8_t* flags,
+                       size_t npts, int min_support, int max_conflicts, float* out_xyz, float* out_color, uint8_t* out_support,
+                       int* out_index, unsigned* count, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

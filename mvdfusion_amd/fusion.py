@@ -1,0 +1,160 @@
+"""Sampled RGB-D views -> one depth-consistent coloured point cloud (include/mvd_hip.h: mvd_fuse_points, mvd_compact_points).
+
+The sampler returns (V, 5, S, S) latents whose channel 4 is a depth map per view.  ``fuse_views`` unprojects every view's depth through its
+camera, lets every other view of the rig vote on each point (support: that view's depth map agrees within tau; conflict: the point floats
+in front of the surface that view sees), keeps the foreground points with enough support and few enough conflicts and returns them as one
+cloud, coloured from the decoded images when given.  ``ViewFusion.fuse`` is the same call with the model's own depth map and decoder;
+``write_ply`` saves a cloud.  Both kernels run on torch's current stream; the only host synchronisation is the read of the point count.
+"""
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from . import hip
+from .cameras import Cameras, _as_cameras, pack_cameras
+
+DEPTH_SCALE, DEPTH_SHIFT = 2.0, 0.5          # GridAttn's defaults (view_attn_efficient2.py): metric depth = dn * scale + shift
+TAU_FRACTION = 0.025                         # default tau = TAU_FRACTION * depth_scale
+
+
+@dataclass
+class PointCloud:
+    """The kept points, in point order (scene, view, Y, X); every field is a tensor on the latents' device."""
+    xyz: torch.Tensor                        # (n, 3) fp32 world coordinates
+    rgb: Optional[torch.Tensor]              # (n, 3) fp32 in [0, 1], or None without colour
+    support: torch.Tensor                    # (n,) uint8: other views whose depth map agrees with the point
+    scene: torch.Tensor                      # (n,) int64
+    view: torch.Tensor                       # (n,) int64: the view the point was unprojected from
+    pixel: torch.Tensor                      # (n, 2) int64: (Y, X) on that view's P x P grid
+    index: torch.Tensor                      # (n,) int32: ((scene * V + view) * P + Y) * P + X, as the kernel wrote it
+
+    def __len__(self):
+        return int(self.xyz.shape[0])
+
+
+def _ndc_lin(P, device):
+    return torch.linspace(1.0 - 1.0 / P, -1.0 + 1.0 / P, P, dtype=torch.float32).to(device)
+
+
+def _run(lat, rgb, cams, N, V, S, up, depth_scale, depth_shift, lo, hi, tau, min_support, max_conflicts):
+    """The two launches.  lat (N*V, 5, S, S), rgb (N*V, 3, P, P) or None, cams (N*V, CAM_RECORD), all fp32 on one GPU.  Returns
+    (xyz, rgb or None, support, index) cut to the kept points -- one host read, of the count."""
+    L = hip.lib()
+    dev, P = lat.device, S * up
+    npts = N * V * P * P
+    hip._req(lat), hip._req(cams)
+    if rgb is not None:
+        hip._req(rgb)
+    u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    xyz, support, conflict, flags = f32(npts, 3), u8(npts), u8(npts), u8(npts)
+    color = f32(npts, 3) if rgb is not None else None
+    lin = _ndc_lin(P, dev)
+    hip.check(L.mvd_fuse_points(hip.ptr(lat), hip.ptr(rgb), hip.ptr(cams), hip.ptr(lin), hip.ptr(xyz), hip.ptr(color), hip.ptr(support),
+                                hip.ptr(conflict), hip.ptr(flags), N, V, S, up, float(depth_scale), float(depth_shift), float(lo),
+                                float(hi), float(tau), hip.FUSE_STAGE_AUTO, hip.stream()))
+    out_xyz, out_support = f32(npts, 3), u8(npts)
+    out_color = f32(npts, 3) if rgb is not None else None
+    out_index = torch.empty(npts, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    nbytes = int(L.mvd_compact_points_scratch(npts))
+    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    hip.check(L.mvd_compact_points(hip.ptr(xyz), hip.ptr(color), hip.ptr(support), hip.ptr(conflict), hip.ptr(flags), npts,
+                                   int(min_support), int(max_conflicts), hip.ptr(out_xyz), hip.ptr(out_color), hip.ptr(out_support),
+                                   hip.ptr(out_index), hip.ptr(count), hip.ptr(scratch), nbytes, hip.stream()))
+    n = int(count.item())
+    return out_xyz[:n], None if out_color is None else out_color[:n], out_support[:n], out_index[:n]
+
+
+def _cat_cameras(cs):
+    cs = [_as_cameras(c) for c in cs]
+    return Cameras(*(torch.cat([getattr(c, k) for c in cs]) for k in ("R", "T", "focal_length", "principal_point")))
+
+
+def fuse_views(latents, cameras, rgb=None, up=1, tau=None, min_support=1, max_conflicts=0, foreground=(0.02, 0.98),
+               depth_scale=DEPTH_SCALE, depth_shift=DEPTH_SHIFT):
+    """Fuse sampled views into a PointCloud.
+
+    latents : (V, 5, S, S) with ``cameras`` the V batch cameras, or (N, V, 5, S, S) with a list of N camera sets (what ``sample_scenes``
+              returns); channel 4 is the depth map in [-1, 1].
+    rgb     : (.., 3, H, H) in [0, 1] with the latents' leading dimensions, or None.  The output grid has P = S * up pixels per side; an
+              image with H > P is resized to P with F.interpolate(mode="area"), H < P is refused (choose a smaller ``up``).
+    up      : integer >= 1.  A fine pixel takes the depth of the latent pixel it lies in and its own ray.
+    tau     : depth agreement in the units of depth_scale; default 0.025 * depth_scale.
+    A point is kept when it is foreground (foreground[0] < normalised depth < foreground[1]), at least ``min_support`` other views agree
+    with it and at most ``max_conflicts`` see their own surface behind it.
+
+    The defaults (tau, min_support, max_conflicts, foreground) are INTERFACE defaults: no trained checkpoint was available when this
+    was written, so nobody has tuned them on real samples -- expect to.  depth_scale / depth_shift must be those of the model that made
+    the latents (``ViewFusion.fuse`` passes its own)."""
+    if not torch.is_tensor(latents) or latents.dim() not in (4, 5):
+        raise ValueError("latents must be a (V, 5, S, S) or (N, V, 5, S, S) tensor")
+    single = latents.dim() == 4
+    if single:
+        if isinstance(cameras, (list, tuple)):
+            raise ValueError("(V, 5, S, S) latents take one camera set, not a list")
+        latents, cameras = latents[None], [cameras]
+        rgb = None if rgb is None else rgb[None]
+    elif not isinstance(cameras, (list, tuple)) or len(cameras) != latents.shape[0]:
+        raise ValueError(f"(N, V, 5, S, S) latents take a list of N = {latents.shape[0]} camera sets")
+    N, V, C, S, S2 = latents.shape
+    if C != 5 or S != S2 or S < 2:
+        raise ValueError(f"latents of shape {tuple(latents.shape)}: need 5 channels and a square map of at least 2 x 2")
+    if not 1 <= V <= 255:
+        raise ValueError(f"V = {V} views outside [1, 255]")
+    if int(up) != up or up < 1:
+        raise ValueError(f"up = {up}: an integer >= 1")
+    up = int(up)
+    P = S * up
+    if N * V * P * P >= 2 ** 31:
+        raise ValueError(f"{N * V * P * P} points: the point index is 31 bits")
+    lo, hi = (float(v) for v in foreground)
+    if not lo < hi:
+        raise ValueError(f"foreground = {foreground}: need lo < hi")
+    tau = TAU_FRACTION * float(depth_scale) if tau is None else float(tau)
+    if not tau >= 0:
+        raise ValueError(f"tau = {tau}: >= 0")
+    if not (0 <= int(min_support) <= 255 and 0 <= int(max_conflicts) <= 255):
+        raise ValueError("min_support and max_conflicts are counts in [0, 255]")
+    cams = _cat_cameras(cameras)
+    if len(cams) != N * V:
+        raise ValueError(f"{len(cams)} cameras for {N} x {V} views")
+    dev = latents.device
+    if rgb is not None:
+        if rgb.dim() != 5 or tuple(rgb.shape[:3]) != (N, V, 3) or rgb.shape[3] != rgb.shape[4]:
+            raise ValueError(f"rgb of shape {tuple(rgb.shape)} does not go with latents of shape {tuple(latents.shape)}")
+        H = rgb.shape[-1]
+        if H < P:
+            raise ValueError(f"rgb is {H} pixels wide, the output grid {P} (S = {S}, up = {up}): choose up <= {H // S}")
+        rgb = rgb.reshape(N * V, 3, H, H).to(dev, torch.float32)
+        if H > P:
+            rgb = torch.nn.functional.interpolate(rgb, size=(P, P), mode="area")
+        rgb = rgb.contiguous()
+    lat = latents.reshape(N * V, 5, S, S).float().contiguous()
+    xyz, color, support, index = _run(lat, rgb, pack_cameras(cams).to(dev), N, V, S, up, depth_scale, depth_shift, lo, hi, tau, min_support,
+                                      max_conflicts)
+    i = index.long()
+    return PointCloud(xyz=xyz, rgb=color, support=support, scene=i // (V * P * P), view=(i // (P * P)) % V,
+                      pixel=torch.stack([(i // P) % P, i % P], dim=1), index=index)
+
+
+def write_ply(path, cloud):
+    """Binary little-endian PLY: float x y z per vertex, and uchar red green blue (round(255 rgb)) when the cloud has colour."""
+    import numpy as np
+    n = len(cloud)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if cloud.rgb is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    v = np.zeros(n, dtype=np.dtype(fields))
+    xyz = cloud.xyz.detach().cpu().numpy().astype("<f4")
+    v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if cloud.rgb is not None:
+        c = np.rint(np.clip(cloud.rgb.detach().cpu().numpy(), 0.0, 1.0) * 255.0).astype("u1")
+        v["red"], v["green"], v["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    names = {"<f4": "float", "u1": "uchar"}
+    header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {n}\n" + \
+        "".join(f"property {names[t]} {k}\n" for k, t in fields) + "end_header\n"
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(v.tobytes())

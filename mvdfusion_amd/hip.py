@@ -47,6 +47,8 @@ ACT_NONE, ACT_GELU, ACT_SILU, ACT_QUICKGELU = 0, 1, 2, 3
 STEP_STRIDE = 8
 CAM_RECORD = 20
 TOKEN_DIM, TOKEN_LD = 723, 736
+FUSE_FOREGROUND = 1                                        # flags byte of mvd_fuse_points
+FUSE_STAGE_AUTO, FUSE_STAGE_GLOBAL, FUSE_STAGE_LDS = 0, 1, 2
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -154,6 +156,9 @@ SIGNATURES = {
     "mvd_view_pool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvd_cfg_ddim_update": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     "mvd_pin_views": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mvd_fuse_points": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp]),
+    "mvd_compact_points_scratch": (_sz, [_sz]),
+    "mvd_compact_points": (_i, [_vp] * 5 + [_sz, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),

@@ -655,6 +655,21 @@ class ViewFusion(nn.Module):
         return (x, batch_latents, input_latents, batch_cameras, []) if return_input else x
 
     @torch.no_grad()
+    def fuse(self, latents, batch_cameras, up=8, decode=True, **kw):
+        """The call after ``sample`` / ``sample_scenes`` / ``sample_rig``: the sampled views as one depth-consistent point cloud
+        (fusion.fuse_views with this model's depth_scale / depth_shift).  latents (V, 5, S, S) with the batch cameras, or (N, V, 5, S, S)
+        with a list of N camera sets.  decode: colour the points from ``self.decode(latents[:, :4])`` (8 S pixels per side, so up <= 8);
+        otherwise pass ``rgb=`` or get an uncoloured cloud.  Other keywords: tau, min_support, max_conflicts, foreground."""
+        from .fusion import fuse_views
+        if decode:
+            S = latents.shape[-1]
+            flat = latents.reshape(-1, 5, S, S)[:, :4]
+            img = torch.cat([self.decode(c) for c in flat.split(self.vae_max_batch)]).float()
+            kw["rgb"] = img.reshape(*latents.shape[:-3], 3, img.shape[-2], img.shape[-1])
+        return fuse_views(latents, batch_cameras, up=up, depth_scale=self.view_attn.depth_scale, depth_shift=self.view_attn.depth_shift,
+                          **kw)
+
+    @torch.no_grad()
     def p_losses(self, batch, trainer_config, noise_source=None, _aux=None):
         """viewfusion_zero_depth_rgb.py:362-392 -- the training objective's FORWARD pass on the HIP path: prepare_batch, shared
         random timestep, q_sample, apply_model (cfg 1, condition dropout when self.training), MSE against the noise.
