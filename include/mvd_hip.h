@@ -540,6 +540,52 @@ int mvd_compact_points(const float* xyz, const float* color, const uint8_t* supp
                        int* out_index, unsigned* count, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rendering a point cloud into cameras: z-buffered point splatting (csrc/fusion.hip; host: mvdfusion_amd/fusion.py render_points).
+ * Not in the reference either.  One primitive gives a novel view, the depth map the rig as a whole implies for a view, and the map of
+ * which source point each pixel shows: project every point into a camera and keep, per pixel, the nearest one.
+ *
+ * mvd_render_points:
+ *   xyz (n, 3) fp32 world points; color (n, 3) fp32 or NULL; scene_start: nscene + 1 int32 DEVICE values, points
+ *   [scene_start[s], scene_start[s + 1]) belong to scene s (the arrays are sorted by scene; values are clamped to [0, n]);
+ *   cams (nscene*M, MVD_CAM_RECORD): M target cameras per scene, camera c = s*M + j; P: output side in pixels;
+ *   radius r: integer, 0 <= r <= MVD_SPLAT_MAX_RADIUS; znear >= 0; empty_depth; background: 3 floats on the HOST (read at the call;
+ *   may be NULL when color is NULL).
+ *   Projection: for point i of scene s and camera j of that scene, (u, w, zc) = NDC and camera-space z exactly as mvd_fuse_points'
+ *               pair rule computes them (one function in the source).  cx = (1 - u) * P / 2 - 0.5, cy alike from w: geometric pixel
+ *               centres, the expression and operation order of the fuse kernel's depth lookup with P for S and no clamp.
+ *               Centre pixel px = floor(cx + 0.5), py = floor(cy + 0.5).
+ *   Dropped   : the pair draws nothing unless zc > znear and cx, cy are finite (a NaN anywhere drops it; the float-to-int conversion
+ *               happens only for centres within r + 2 pixels of the image -- any other covers no pixel).
+ *   Footprint : the pixels (py + dy, px + dx), |dx|, |dy| <= r, clipped to the image; a centre outside the image still draws the part of
+ *               its footprint that is inside.
+ *   Depth rule: every covered pixel takes the minimum of key = (uint64(bits(zc)) << 32) | i.  zc > 0, so the bit pattern orders like the
+ *               value: the nearest point wins, between points with identical zc bits the one that comes first in the input.  The result
+ *               is a pure function of the inputs, bit-identical run to run whatever order the atomics arrive in.  An empty pixel holds
+ *               all ones (no key equals it: i <= 2^31 - 2, and bits of all ones are a NaN, which is dropped).
+ *   Outputs per (camera, pixel): index (nscene*M, P, P) int32 = the winner's position i in the input arrays, or -1;
+ *               depth (nscene*M, P, P) fp32 = the winner's zc bit for bit, or empty_depth; rgb (nscene*M, 3, P, P) fp32 planar =
+ *               color[index] bit for bit, or background -- with color NULL rgb is not touched and may be NULL.
+ *   All fp32, compiled without contraction.  n <= 2^31 - 1; nscene * M * P * P < 2^31; nscene * M <= 65535.
+ *   scratch   : the 64-bit z-buffer, mvd_render_points_scratch(nscene*M, P) bytes, 8-byte aligned.
+ *   Three enqueues on the caller's stream: fill the z-buffer with ones, the splat kernel (one 64-bit unsigned atomicMin per covered
+ *   pixel, device scope; workgroups never straddle scenes or cameras), the resolve kernel (one thread per output pixel).  Every argument
+ *   is checked before anything is enqueued.
+ * mvd_render_points_stages: the same call restricted to the stages in `stages` (an OR of MVD_RENDER_FILL / _SPLAT / _RESOLVE;
+ *   MVD_RENDER_ALL is mvd_render_points) -- for timing one stage (tools/bench_render.py) or re-resolving a z-buffer. */
+#define MVD_SPLAT_MAX_RADIUS 4
+#define MVD_RENDER_FILL 1
+#define MVD_RENDER_SPLAT 2
+#define MVD_RENDER_RESOLVE 4
+#define MVD_RENDER_ALL 7
+size_t mvd_render_points_scratch(int ncam, int P);
+int mvd_render_points(const float* xyz, const float* color, const int* scene_start, const float* cams, size_t n, int nscene, int M, int P,
+                      int radius, float znear, float empty_depth, const float* background, int* index, float* depth, float* rgb,
+                      void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+int mvd_render_points_stages(const float* xyz, const float* color, const int* scene_start, const float* cams, size_t n, int nscene, int M,
+                             int P, int radius, float znear, float empty_depth, const float* background, int* index, float* depth,
+                             float* rgb, void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

@@ -16,6 +16,11 @@
 // compact: count_kernel (per-wavefront 64-bit ballot + popcount, per-block count) -> scan_kernel (one workgroup loops over the block
 // counts: exclusive offsets in place, total to *count) -> scatter_kernel (same ballots; rank = block offset + earlier wavefronts + popcount
 // of the lower lanes).  No atomic decides an order: the output is the masked selection in point order, run to run.
+//
+// render (mvd_render_points): z-buffered point splatting of a cloud into M cameras per scene.  The z-buffer is filled with ones -> splat_kernel:
+// one thread per (point, camera), project_z above, the centre pixel by the fuse kernel's pixel-centre convention, one 64-bit unsigned
+// atomicMin of (depth bits << 32 | point position) per covered pixel -> resolve_kernel: one thread per pixel unpacks the winner.  The minimum
+// of a set does not depend on the order its members arrive in: the outputs are the same bits run to run.
 #include "gridattn_common.hpp"
 
 namespace {
@@ -195,6 +200,68 @@ __global__ __launch_bounds__(kCompactThreads) void scatter_kernel(CompactArgs a)
   a.out_index[o] = (int)pt;
 }
 
+// ------------------------------------------------------------------------------------------------ point splatting
+constexpr int kSplatThreads = 256;
+constexpr unsigned long long kEmptyKey = ~0ull;
+// A plain load of the cell in front of each atomic skips it when the stored key is already smaller.  Keys only decrease, so a stale read
+// costs an unnecessary atomic and never a wrong result.  Measured (tools/bench_render.py); -DMVD_SPLAT_EARLY_OUT=0
+// builds the other form for the comparison.
+#ifndef MVD_SPLAT_EARLY_OUT
+#define MVD_SPLAT_EARLY_OUT 1
+#endif
+
+struct RenderArgs {
+  const float *xyz, *color, *cams;
+  const int* scene_start;
+  unsigned long long* zbuf;
+  int* index;
+  float *depth, *rgb;
+  int n, M, P, radius;
+  float znear, empty_depth, bg[3];
+};
+
+// blockIdx.y = scene * M + camera: the camera record and the scene's point range are uniform; blockIdx.x walks the range, blocks past it exit
+__global__ __launch_bounds__(kSplatThreads) void splat_kernel(RenderArgs a) {
+  const int cam = blockIdx.y, scene = cam / a.M, P = a.P, r = a.radius;
+  const long long s0 = max(a.scene_start[scene], 0), s1 = min(a.scene_start[scene + 1], a.n);      // (device values: never read past n)
+  const long long i = s0 + (long long)blockIdx.x * kSplatThreads + threadIdx.x;
+  if (i >= s1) return;
+  const float X[3] = {a.xyz[i * 3 + 0], a.xyz[i * 3 + 1], a.xyz[i * 3 + 2]};
+  float u, w, zc;
+  project_z(load_cam(a.cams + (size_t)cam * MVD_CAM_RECORD), X, u, w, zc);
+  if (!(zc > a.znear)) return;                                               // behind the near plane (a NaN compares false)
+  const float P2 = 0.5f * (float)P;
+  const float cx = (1.f - u) * P2 - 0.5f, cy = (1.f - w) * P2 - 0.5f;          // the fuse kernel's depth lookup, P for S, no clamp
+  // a centre further than r + 1 pixels outside covers nothing; the test also drops NaN / inf and keeps the conversion below in range
+  const float lo = -(float)(r + 2), hi = (float)(P + r + 1);
+  if (!(cx >= lo && cx <= hi && cy >= lo && cy <= hi)) return;
+  const int px = (int)floorf(cx + 0.5f), py = (int)floorf(cy + 0.5f);
+  const int x0 = max(px - r, 0), x1 = min(px + r, P - 1), y0 = max(py - r, 0), y1 = min(py + r, P - 1);
+  const unsigned long long key = ((unsigned long long)__float_as_uint(zc) << 32) | (unsigned long long)(unsigned)i;      // zc > 0: bits order like values
+  unsigned long long* z = a.zbuf + (size_t)cam * P * P;
+  for (int y = y0; y <= y1; ++y)
+    for (int x = x0; x <= x1; ++x) {
+      unsigned long long* cell = z + (size_t)y * P + x;
+      if (MVD_SPLAT_EARLY_OUT && *cell <= key) continue;
+      atomicMin(cell, key);
+    }
+}
+
+__global__ __launch_bounds__(kSplatThreads) void resolve_kernel(RenderArgs a, unsigned total) {
+  const unsigned pix = blockIdx.x * kSplatThreads + threadIdx.x;      // (camera, y, x); total < 2^31
+  if (pix >= total) return;
+  const unsigned long long key = a.zbuf[pix];
+  const unsigned i = (unsigned)(key & 0xffffffffull);
+  const bool hit = key != kEmptyKey && i < (unsigned)a.n;      // (i < n always behind the splat kernel; a z-buffer of the caller's is not trusted)
+  a.index[pix] = hit ? (int)i : -1;
+  a.depth[pix] = hit ? __uint_as_float((unsigned)(key >> 32)) : a.empty_depth;
+  if (a.color) {
+    const unsigned PP = (unsigned)a.P * a.P, cam = pix / PP, rem = pix % PP;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a.rgb[((size_t)cam * 3 + c) * PP + rem] = hit ? a.color[(size_t)i * 3 + c] : a.bg[c];
+  }
+}
+
 }  // namespace
 
 // the staged form's workgroups per scene: what is resident at once, but at least kFusePointsPerThread points per thread -- staging is
@@ -265,4 +332,50 @@ extern "C" int mvd_compact_points(const float* xyz, const float* color, const ui
   hipLaunchKernelGGL(scatter_kernel, dim3(nblocks), dim3(kCompactThreads), 0, (hipStream_t)stream, a);
   MVD_CHECK_LAUNCH("mvd_compact_points");
   return 0;
+}
+
+extern "C" size_t mvd_render_points_scratch(int ncam, int P) {
+  return ncam >= 1 && P >= 1 ? (size_t)ncam * P * P * sizeof(unsigned long long) : 0;
+}
+
+extern "C" int mvd_render_points_stages(const float* xyz, const float* color, const int* scene_start, const float* cams, size_t n, int nscene,
+                                        int M, int P, int radius, float znear, float empty_depth, const float* background, int* index,
+                                        float* depth, float* rgb, void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream) {
+  const char* fn = stages == MVD_RENDER_ALL ? "mvd_render_points" : "mvd_render_points_stages";
+  MVD_CHECK_ARG(stages >= 1 && stages <= MVD_RENDER_ALL, "%s: stages=%d outside [1, %d]", fn, stages, MVD_RENDER_ALL);
+  MVD_CHECK_ARG(n <= 0x7fffffffull, "%s: n=%zu beyond 2^31 - 1", fn, n);
+  MVD_CHECK_ARG(xyz || n == 0, "%s: null xyz with n=%zu", fn, n);
+  MVD_CHECK_ARG(scene_start && cams && index && depth && scratch, "%s: null pointer", fn);
+  MVD_CHECK_ARG(!color || (rgb && background), "%s: color without an rgb output and a background", fn);
+  MVD_CHECK_ARG(nscene >= 1 && M >= 1 && (unsigned long long)nscene * M <= 65535ull, "%s: nscene=%d, M=%d (>= 1, nscene * M <= 65535)", fn,
+                nscene, M);
+  MVD_CHECK_ARG(P >= 1 && P <= 46340 && (unsigned long long)nscene * M * P * P <= 0x7fffffffull,
+                "%s: nscene * M * P^2 pixels outside [1, 2^31 - 1] (nscene=%d, M=%d, P=%d)", fn, nscene, M, P);
+  MVD_CHECK_ARG(radius >= 0 && radius <= MVD_SPLAT_MAX_RADIUS, "%s: radius=%d outside [0, %d]", fn, radius, MVD_SPLAT_MAX_RADIUS);
+  MVD_CHECK_ARG(znear >= 0.f, "%s: znear=%g (>= 0)", fn, (double)znear);
+  const int ncam = nscene * M;
+  MVD_CHECK_ARG(scratch_bytes >= mvd_render_points_scratch(ncam, P) && ((uintptr_t)scratch & 7) == 0,
+                "%s: scratch of %zu bytes (needs %zu, 8-byte aligned)", fn, scratch_bytes, mvd_render_points_scratch(ncam, P));
+  RenderArgs a{xyz, color, cams, scene_start, (unsigned long long*)scratch, index, depth, rgb, (int)n, M, P, radius, znear, empty_depth,
+               {0.f, 0.f, 0.f}};
+  if (color)
+    for (int c = 0; c < 3; ++c) a.bg[c] = background[c];
+  const unsigned total = (unsigned)ncam * P * P;
+  if (stages & MVD_RENDER_FILL) {
+    const hipError_t e = hipMemsetAsync(scratch, 0xff, (size_t)total * sizeof(unsigned long long), (hipStream_t)stream);
+    MVD_CHECK_ARG(e == hipSuccess, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+  }
+  if ((stages & MVD_RENDER_SPLAT) && n > 0)      // a scene has at most n points: blocks past its range exit
+    hipLaunchKernelGGL(splat_kernel, dim3(cdiv((long)n, kSplatThreads), ncam), dim3(kSplatThreads), 0, (hipStream_t)stream, a);
+  if (stages & MVD_RENDER_RESOLVE)
+    hipLaunchKernelGGL(resolve_kernel, dim3(cdiv((long)total, kSplatThreads)), dim3(kSplatThreads), 0, (hipStream_t)stream, a, total);
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
+extern "C" int mvd_render_points(const float* xyz, const float* color, const int* scene_start, const float* cams, size_t n, int nscene, int M,
+                                 int P, int radius, float znear, float empty_depth, const float* background, int* index, float* depth,
+                                 float* rgb, void* scratch, size_t scratch_bytes, mvd_stream_t stream) {
+  return mvd_render_points_stages(xyz, color, scene_start, cams, n, nscene, M, P, radius, znear, empty_depth, background, index, depth, rgb,
+                                  scratch, scratch_bytes, MVD_RENDER_ALL, stream);
 }

@@ -5,6 +5,9 @@ camera, lets every other view of the rig vote on each point (support: that view'
 in front of the surface that view sees), keeps the foreground points with enough support and few enough conflicts and returns them as one
 cloud, coloured from the decoded images when given.  ``ViewFusion.fuse`` is the same call with the model's own depth map and decoder;
 ``write_ply`` saves a cloud.  Both kernels run on torch's current stream; the only host synchronisation is the read of the point count.
+
+``render_points`` goes the other way (include/mvd_hip.h: mvd_render_points): a cloud splatted into any cameras with a z-buffer -- a novel
+view, the depth map the rig as a whole implies for a view, and the map of which point each pixel shows.  It synchronises nothing.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -137,6 +140,114 @@ def fuse_views(latents, cameras, rgb=None, up=1, tau=None, min_support=1, max_co
     i = index.long()
     return PointCloud(xyz=xyz, rgb=color, support=support, scene=i // (V * P * P), view=(i // (P * P)) % V,
                       pixel=torch.stack([(i // P) % P, i % P], dim=1), index=index)
+
+
+@dataclass
+class RenderedViews:
+    """What ``render_points`` returns; the leading scene dimension is present only when a list of camera sets was passed."""
+    rgb: Optional[torch.Tensor]              # (.., M, 3, P, P) fp32: the colour of the nearest point, or the background; None without colour
+    depth: torch.Tensor                      # (.., M, P, P) fp32: its camera-space z, or empty_depth
+    index: torch.Tensor                      # (.., M, P, P) int32: its position in the cloud, or -1
+    hit: torch.Tensor                        # (.., M, P, P) bool: index >= 0
+
+    _depth_map = (DEPTH_SCALE, DEPTH_SHIFT)  # depth_latent's defaults (not a field; ViewFusion.render binds the model's own per instance)
+
+    def depth_latent(self, depth_scale=None, depth_shift=None):
+        """The depth map in the model's depth-channel convention, clamp(2 (z - shift) / scale - 1, -1, 1) with empty pixels at +1: the
+        inverse of ``fuse_views``' map z = clamp((lat + 1) / 2, 0, 1) * scale + shift.  Defaults: DEPTH_SCALE, DEPTH_SHIFT."""
+        scale = self._depth_map[0] if depth_scale is None else depth_scale
+        shift = self._depth_map[1] if depth_shift is None else depth_shift
+        lat = torch.clamp(2.0 * (self.depth - float(shift)) / float(scale) - 1.0, -1.0, 1.0)
+        return torch.where(self.hit, lat, torch.ones_like(lat))
+
+
+def _render(xyz, color, scene_start, cams, N, M, P, radius, znear, empty_depth, background):
+    """The three enqueues of mvd_render_points.  xyz (n, 3), color (n, 3) or None, scene_start (N + 1) int32, cams (N*M, CAM_RECORD), all
+    contiguous on one GPU.  Returns (rgb or None, depth, index) of shapes (N*M, [3,] P, P).  No host synchronisation."""
+    import ctypes
+    L = hip.lib()
+    dev, n = xyz.device, int(xyz.shape[0])
+    hip._req(xyz), hip._req(cams), hip._req(scene_start, torch.int32)
+    if color is not None:
+        hip._req(color)
+    index = torch.empty(N * M, P, P, dtype=torch.int32, device=dev)
+    depth = torch.empty(N * M, P, P, dtype=torch.float32, device=dev)
+    rgb = torch.empty(N * M, 3, P, P, dtype=torch.float32, device=dev) if color is not None else None
+    nbytes = int(L.mvd_render_points_scratch(N * M, P))
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    bg = (ctypes.c_float * 3)(*background)
+    hip.check(L.mvd_render_points(hip.ptr(xyz), hip.ptr(color), hip.ptr(scene_start), hip.ptr(cams), n, N, M, P, radius, float(znear),
+                                  float(empty_depth), bg, hip.ptr(index), hip.ptr(depth), hip.ptr(rgb), hip.ptr(scratch), nbytes, hip.stream()))
+    return rgb, depth, index
+
+
+def render_points(cloud, cameras, size=256, radius=1, background=(1.0, 1.0, 1.0), znear=1e-3, empty_depth=float("inf")):
+    """Render a cloud into cameras by z-buffered point splatting (include/mvd_hip.h: mvd_render_points) -> RenderedViews.
+
+    cloud   : a PointCloud, or an (n, 3) tensor (one scene, no colour).
+    cameras : M cameras (anything with .R .T .focal_length .principal_point): every point is drawn into each of them, and the cloud must
+              be one scene's.  Or a list of N sets of M cameras each: scene s of the cloud goes into set s (``cloud.scene`` < N), and
+              the outputs get a leading dimension N.
+    size    : P, the output side in pixels.  radius: a point covers the (2 radius + 1)^2 pixels around its centre pixel,
+              0 <= radius <= hip.SPLAT_MAX_RADIUS.  Per pixel the nearest point with camera z > znear wins (ties: the first in the cloud).
+    background, empty_depth : what a pixel no point covers holds in rgb / depth.
+    Nothing is read back from the device, so ``cloud.scene`` < N is checked only for a cloud in host memory; on the GPU a point of a
+    scene >= N is drawn nowhere."""
+    if isinstance(cloud, PointCloud):
+        xyz, color, scene = cloud.xyz, cloud.rgb, cloud.scene
+    elif torch.is_tensor(cloud):
+        xyz, color, scene = cloud, None, None
+    else:
+        raise ValueError("cloud must be a PointCloud or an (n, 3) tensor")
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"cloud: xyz of shape {tuple(xyz.shape)}, need (n, 3)")
+    n = int(xyz.shape[0])
+    if n > 2 ** 31 - 1:
+        raise ValueError(f"cloud: {n} points, the point index is 31 bits")
+    if color is not None and tuple(color.shape) != (n, 3):
+        raise ValueError(f"cloud: rgb of shape {tuple(color.shape)} for {n} points")
+    if scene is not None and tuple(scene.shape) != (n,):
+        raise ValueError(f"cloud: scene of shape {tuple(scene.shape)} for {n} points")
+    if int(size) != size or size < 1:
+        raise ValueError(f"size = {size}: an integer >= 1")
+    if int(radius) != radius or not 0 <= radius <= hip.SPLAT_MAX_RADIUS:
+        raise ValueError(f"radius = {radius}: an integer in [0, {hip.SPLAT_MAX_RADIUS}]")
+    P, radius, znear = int(size), int(radius), float(znear)
+    if not znear >= 0:
+        raise ValueError(f"znear = {znear}: >= 0")
+    background = tuple(float(v) for v in background)
+    if len(background) != 3:
+        raise ValueError(f"background = {background}: three floats")
+    single = not isinstance(cameras, (list, tuple))
+    sets = [_as_cameras(c) for c in ([cameras] if single else cameras)]
+    N = len(sets)
+    if N < 1:
+        raise ValueError("cameras: an empty list")
+    M = len(sets[0])
+    if M < 1 or any(len(c) != M for c in sets):
+        raise ValueError(f"cameras: every scene needs the same number M >= 1 of cameras, got {[len(c) for c in sets]}")
+    if N * M > 65535:
+        raise ValueError(f"cameras: {N} x {M} cameras, at most 65535 per call")
+    if N * M * P * P >= 2 ** 31:
+        raise ValueError(f"size = {P}: {N * M * P * P} pixels for {N} x {M} cameras, the pixel index is 31 bits")
+    if scene is None and N != 1:
+        raise ValueError(f"cameras: a list of {N} camera sets needs a PointCloud (an (n, 3) tensor is one scene)")
+    if scene is not None and n and scene.device.type == "cpu" and not 0 <= int(scene.min()) <= int(scene.max()) < N:
+        raise ValueError(f"cameras: {N} camera set(s) for a cloud with scenes {int(scene.min())} .. {int(scene.max())}")
+    dev = xyz.device
+    xyz = xyz.float().contiguous()
+    color = None if color is None else color.to(dev, torch.float32).contiguous()
+    if scene is None or n == 0:
+        scene_start = torch.tensor([0] + [n] * N, dtype=torch.int32).to(dev)
+    else:      # offsets of the sorted scene ids, on the device: a scene id >= N leaves its points past the last range, drawn nowhere
+        bounds = torch.arange(N + 1, dtype=scene.dtype, device=scene.device)
+        scene_start = torch.searchsorted(scene.contiguous(), bounds).to(dev, torch.int32)
+    cams = Cameras(*(torch.cat([getattr(c, k) for c in sets]) for k in ("R", "T", "focal_length", "principal_point")))
+    rgb, depth, index = _render(xyz, color, scene_start, pack_cameras(cams).to(dev).contiguous(), N, M, P, radius, znear, empty_depth, background)
+    lead = (M,) if single else (N, M)
+    index = index.reshape(*lead, P, P)
+    return RenderedViews(rgb=None if rgb is None else rgb.reshape(*lead, 3, P, P), depth=depth.reshape(*lead, P, P), index=index,
+                         hit=index >= 0)
 
 
 def write_ply(path, cloud):

@@ -49,6 +49,8 @@ CAM_RECORD = 20
 TOKEN_DIM, TOKEN_LD = 723, 736
 FUSE_FOREGROUND = 1                                        # flags byte of mvd_fuse_points
 FUSE_STAGE_AUTO, FUSE_STAGE_GLOBAL, FUSE_STAGE_LDS = 0, 1, 2
+SPLAT_MAX_RADIUS = 4                                       # MVD_SPLAT_MAX_RADIUS: the largest footprint radius of mvd_render_points
+RENDER_FILL, RENDER_SPLAT, RENDER_RESOLVE, RENDER_ALL = 1, 2, 4, 7      # stages of mvd_render_points_stages
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -159,6 +161,9 @@ SIGNATURES = {
     "mvd_fuse_points": (_i, [_vp] * 9 + [_i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _vp]),
     "mvd_compact_points_scratch": (_sz, [_sz]),
     "mvd_compact_points": (_i, [_vp] * 5 + [_sz, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_render_points_scratch": (_sz, [_i, _i]),
+    "mvd_render_points": (_i, [_vp] * 4 + [_sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_render_points_stages": (_i, [_vp] * 4 + [_sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),

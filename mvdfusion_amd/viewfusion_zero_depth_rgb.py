@@ -670,6 +670,20 @@ class ViewFusion(nn.Module):
                           **kw)
 
     @torch.no_grad()
+    def render(self, cloud, cameras, size=256, radius=1, **kw):
+        """A fused cloud seen from any cameras (fusion.render_points; ``depth_latent`` of the result defaults to this model's depth_scale /
+        depth_shift).  cameras: M cameras, or a list of N sets of M for an N-scene cloud.  Other keywords: background, znear, empty_depth.
+
+            cloud = model.fuse(latents, batch_cameras)
+            views = model.render(cloud, batch_cameras, size=256)      # views.rgb (V, 3, 256, 256), views.depth, views.index, views.hit
+            lat4 = views.depth_latent()                                # the depth the whole rig implies for each view, as a depth channel
+        """
+        from .fusion import render_points
+        out = render_points(cloud, cameras, size=size, radius=radius, **kw)
+        out._depth_map = (float(self.view_attn.depth_scale), float(self.view_attn.depth_shift))
+        return out
+
+    @torch.no_grad()
     def p_losses(self, batch, trainer_config, noise_source=None, _aux=None):
         """viewfusion_zero_depth_rgb.py:362-392 -- the training objective's FORWARD pass on the HIP path: prepare_batch, shared
         random timestep, q_sample, apply_model (cfg 1, condition dropout when self.training), MSE against the noise.
