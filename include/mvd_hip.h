@@ -586,6 +586,76 @@ int mvd_render_points_stages(const float* xyz, const float* color, const int* sc
                              float* rgb, void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Volumetric fusion: the sampled RGB-D views integrated into a truncated signed distance volume (TSDF), and a watertight indexed triangle
+ * mesh with vertex colours extracted from it by marching tetrahedra (csrc/tsdf.hip, csrc/tsdf_mesh.hpp; host: mvdfusion_amd/fusion.py
+ * integrate_tsdf, extract_mesh).  Not in the reference either.  Cameras, projection, depth map and depth lookup are those of the point
+ * fusion above (one copy of each in the source, csrc/fusion_common.hpp).
+ *
+ * The integrate call:
+ *   lat (nscene*V, 5, S, S), rgb (nscene*V, 3, P, P) or NULL with P = S * up, cams (nscene*V, MVD_CAM_RECORD) as for the point fusion.
+ *   Volume    : G^3 voxels per scene, arrays (nscene, G, G, G) in z, y, x order (x fastest).  The world box is center +- half_extent
+ *               (cx, cy, cz, half_extent: host floats, one box for all scenes).  With vs = 2 * half_extent / G in fp32, voxel (k, j, i)
+ *               has its centre at X = ((cx - half_extent) + (i + 0.5) * vs, (cy - half_extent) + (j + 0.5) * vs,
+ *               (cz - half_extent) + (k + 0.5) * vs), evaluated in fp32 as written.
+ *   View rule : views v = 0 .. V-1 of the voxel's scene in that order.  (u, w, zc) = NDC and camera-space z of X exactly as the point
+ *               fusion's pair rule computes them.  Skipped unless zc > 0, |u| <= 1 and |w| <= 1 (a NaN: skipped).  Depth lookup as in the
+ *               pair rule: ix = clamp((1 - u) * S / 2 - 0.5, 0, S - 1), iy alike, taps x0 = floor(ix), x1 = min(x0 + 1, S - 1), y alike,
+ *               dn = clamp((lat + 1) / 2, 0, 1) per tap, a tap is foreground iff lo < dn < hi, zs = the bilinear mix of
+ *               dn * depth_scale + depth_shift in the pair rule's evaluation order.
+ *                 four foreground taps : sdf = zs - zc.  sdf < -trunc: the voxel is hidden behind the surface view v sees -- skipped.
+ *                                        Else the observation d = min(1, sdf / trunc).
+ *                 four background taps : with carve != 0 the observation d = 1 (free space in front of nothing); carve == 0: skipped.
+ *                 mixed taps (a silhouette): skipped.
+ *   Outputs   : weight (nscene, G, G, G) uint8 = the number of observations (1 <= V <= 255); tsdf fp32 = (sum of d in view order) /
+ *               weight, and exactly 1.0f where weight == 0.  With rgb: the observations with four foreground taps and |sdf| <= trunc
+ *               also sample rgb of view v bilinearly at (u, w) -- the same pixel-centre lookup at side P, border clamp, the same mix
+ *               per channel; color (nscene, G, G, G, 3) fp32 = their mean in view order, cweight uint8 = their number, the mean is 0
+ *               where cweight == 0.  rgb NULL: color and cweight are not touched and may be NULL.
+ *   One thread per voxel sums its views in order: no atomics, the same bits run to run.  All fp32, compiled without contraction.
+ *   Refused   : G outside [2, 256]; 7 * nscene * G^3 >= 2^31; trunc <= 0; half_extent <= 0 (NaN included); lo >= hi; V outside [1, 255];
+ *               nscene outside [1, 65535]; S < 2; up < 1; S * up > 46340.
+ *
+ * The mesh calls: marching tetrahedra over a volume (tsdf, weight as above; any caller-made volume will do).
+ *   Cells     : the cube between voxel centres (k..k+1, j..j+1, i..i+1), (G-1)^3 per scene, split into the six Kuhn tetrahedra around
+ *               its main diagonal: tetrahedron q = 0 .. 5 follows the axis permutation (a, b, c) = xyz, xzy, yxz, yzx, zxy, zyx and has
+ *               the corners v0, v0 + e_a, v0 + e_a + e_b, v0 + (1,1,1).  The split is the same in every cell, so neighbours agree on
+ *               their shared faces and the surface is closed wherever the volume is observed.
+ *   Edges     : a lattice edge belongs to its lower corner; a corner owns the 7 directions (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1),
+ *               (0,1,1), (1,1,1) in (x, y, z); edge number e = ((scene*G^3 + (k*G + j)*G + i) * 7 + direction.  Edges that leave the
+ *               grid do not exist.  A voxel is observed iff weight > 0, inside iff observed and tsdf < 0 (zero is outside).
+ *   Vertices  : an edge carries a vertex iff both ends are observed and exactly one is inside.  With a the inside end, b the other:
+ *               t = d_a / (d_a - d_b) in fp32 (the denominator is never 0) and position x_a + t * (x_b - x_a) per axis from the voxel
+ *               centres above.  Colour: c_a + t * (c_b - c_a) when both ends have cweight > 0, the one available colour when one has,
+ *               `fill` (3 host floats) when neither has.  The vertex id is the rank of its edge among the carrying edges of the whole
+ *               call in edge-number order: ids are global, scene s owns [vertex_start[s], vertex_start[s + 1]).
+ *   Triangles : a tetrahedron emits only when its four corners are observed.  One or three corners inside: 1 triangle; two: a quad cut
+ *               into 2 triangles along the diagonal through its smallest vertex id.  Every triangle is wound so that its normal points
+ *               from inside to outside and rotated so that its smallest vertex id comes first.  Of a quad wound (m, n1, n2, n3) with m
+ *               its smallest id, the FIRST triangle is (m, n1, n2) and the second (m, n2, n3).  Faces are ordered by (scene, cell k, j,
+ *               i, tetrahedron, triangle); scene s owns [face_start[s], face_start[s + 1]).  A corner with tsdf == 0 is outside and
+ *               puts the vertices of its crossing edges on itself (t = 1): such triangles are DEGENERATE (zero area) but are emitted,
+ *               so the surface stays closed.
+ *   The count call flags the edges and ranks them (wavefront ballots, block counts, the single-workgroup carry scan of the point
+ *               compaction: no atomic decides an order), writes the dense int32 map edge -> vertex id (-1: no vertex) to scratch,
+ *               counts and scans the triangles per cell, and writes vertex_start and face_start ((nscene + 1) int32 each, DEVICE).
+ *               Blocks are padded per scene: none straddles scenes.  The host reads those 2 (nscene + 1) values and allocates.
+ *   The emit call writes vertices (nvert, 3) fp32, colors (nvert, 3) fp32 (with color and cweight non-NULL; all three NULL: no
+ *               colour), faces (nface, 3) int32 from the SAME scratch; nvert = vertex_start[nscene] and nface = face_start[nscene] as read
+ *               by the host -- ids beyond them are not written.
+ *   mvd_mesh_scratch(nscene, G): the bytes of scratch (edge map, block counts, per-cell face offsets); 4-byte aligned; 0 for arguments
+ *               the calls refuse: G outside [2, 256], nscene outside [1, 65535], 7 * nscene * G^3 >= 2^31 or 12 * nscene * (G-1)^3 >= 2^31
+ *               (the most faces there can be). */
+int mvd_tsdf_integrate(const float* lat, const float* rgb, const float* cams, float* tsdf, uint8_t* weight, float* color, uint8_t* cweight,
+                       int nscene, int V, int S, int up, int G, float cx, float cy, float cz, float half_extent, float trunc, int carve,
+                       float depth_scale, float depth_shift, float lo, float hi, mvd_stream_t stream);
+size_t mvd_mesh_scratch(int nscene, int G);
+int mvd_mesh_count(const float* tsdf, const uint8_t* weight, int nscene, int G, int* vertex_start, int* face_start, void* scratch,
+                   size_t scratch_bytes, mvd_stream_t stream);
+int mvd_mesh_emit(const float* tsdf, const uint8_t* weight, const float* color, const uint8_t* cweight, int nscene, int G, float cx, float cy,
+                  float cz, float half_extent, const float* fill, float* vertices, float* colors, int* faces, size_t nvert, size_t nface,
+                  const void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

@@ -5,7 +5,7 @@
 // unprojected through its camera and reprojected into every other view of the rig, whose depth map votes: support (|dz| <= tau), conflict
 // (dz < -tau: the point floats in front of the surface that view sees) or nothing (unseen, background under a tap, occluded).  All fp32,
 // compiled without contraction; the geometry is gridattn_common.hpp's (Cam, load_cam, unproject) plus the projection below, which also
-// returns camera-space z.
+// returns camera-space z (fusion_common.hpp, shared with tsdf.hip).
 //
 // Two forms of the same kernel (bit-identical results): the default reads the depth maps from global memory (they are small and stay in
 // L1 / L2; a wavefront reprojects into one view at a time, so its lanes hit neighbouring texels); kLds stages the scene's V normalised depth
@@ -21,12 +21,11 @@
 // one thread per (point, camera), project_z above, the centre pixel by the fuse kernel's pixel-centre convention, one 64-bit unsigned
 // atomicMin of (depth bits << 32 | point position) per covered pixel -> resolve_kernel: one thread per pixel unpacks the winner.  The minimum
 // of a set does not depend on the order its members arrive in: the outputs are the same bits run to run.
-#include "gridattn_common.hpp"
+#include "fusion_common.hpp"
 
 namespace {
 
 constexpr int kFuseThreads = 512;
-constexpr int kCompactThreads = 256;                  // 4 wavefronts: a block count is at most 256
 constexpr size_t kFuseLdsMax = 128 * 1024;            // of the CU's 160 KiB: V = 24, S = 32 is 98 KiB
 constexpr int kFusePointsPerThread = 4;               // staged form: a workgroup walks at least this many points per thread
 
@@ -37,19 +36,6 @@ struct FuseArgs {
   int V, S, up, P;
   float depth_scale, depth_shift, lo, hi, tau;
 };
-
-// the depth channel normalised to [0, 1], the value the foreground test and the metric depth are taken from
-__device__ __forceinline__ float depth01(float lat) { return fminf(fmaxf((lat + 1.0f) / 2.0f, 0.f), 1.f); }
-
-// project() of gridattn_common.hpp that also returns camera-space z (the depth the other view's map is compared with)
-__device__ __forceinline__ void project_z(const Cam& c, const float* X, float& u, float& w, float& zc) {
-  float xc[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) xc[j] = X[0] * c.R[0 * 3 + j] + X[1] * c.R[1 * 3 + j] + X[2] * c.R[2 * 3 + j] + c.T[j];
-  zc = xc[2];
-  u = c.f[0] * xc[0] / xc[2] + c.p[0];
-  w = c.f[1] * xc[1] / xc[2] + c.p[1];
-}
 
 template <bool kLds>
 __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(FuseArgs a) {
@@ -65,7 +51,6 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(FuseArgs a) {
     cams = lds + V * SS;
   }
   const unsigned total = (unsigned)V * PP;   // points of this scene (< 2^31: checked by the entry point, so i + stride fits 32 bits)
-  const float S2 = 0.5f * (float)S, Sm1 = (float)(S - 1);
   for (unsigned i = blockIdx.x * kFuseThreads + threadIdx.x; i < total; i += gridDim.x * kFuseThreads) {
     const int b = (int)(i / (unsigned)PP), rem = (int)(i % (unsigned)PP), Y = rem / P, X = rem % P;
     const int own = (Y / a.up) * S + X / a.up;
@@ -80,22 +65,17 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_kernel(FuseArgs a) {
       float u, w, zc;
       project_z(load_cam(cams + (size_t)v * MVD_CAM_RECORD), Xw, u, w, zc);
       if (!(zc > 0.f && fabsf(u) <= 1.f && fabsf(w) <= 1.f)) continue;      // unseen (a NaN compares false)
-      // geometric pixel centres with a border clamp: NDC +1 is the left / top edge of pixel 0
-      const float ix = fminf(fmaxf((1.f - u) * S2 - 0.5f, 0.f), Sm1), iy = fminf(fmaxf((1.f - w) * S2 - 0.5f, 0.f), Sm1);
-      const float x0f = floorf(ix), y0f = floorf(iy);
-      const int x0 = (int)x0f, y0 = (int)y0f, x1 = min(x0 + 1, S - 1), y1 = min(y0 + 1, S - 1);
-      const float wx = ix - x0f, wy = iy - y0f;
-      const int idx[4] = {y0 * S + x0, y0 * S + x1, y1 * S + x0, y1 * S + x1};
+      const PixelTaps t = pixel_taps(u, w, S);
       float zt[4];
       bool all_fg = true;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float d = kLds ? lds[v * SS + idx[k]] : depth01(lat[((size_t)v * 5 + 4) * SS + idx[k]]);
+        const float d = kLds ? lds[v * SS + t.idx[k]] : depth01(lat[((size_t)v * 5 + 4) * SS + t.idx[k]]);
         all_fg = all_fg && a.lo < d && d < a.hi;
         zt[k] = d * a.depth_scale + a.depth_shift;
       }
       if (!all_fg) continue;      // view v looks at background or a silhouette there: no vote
-      const float zs = (zt[0] * (1.f - wx) + zt[1] * wx) * (1.f - wy) + (zt[2] * (1.f - wx) + zt[3] * wx) * wy;
+      const float zs = bilinear_mix(zt, t);
       const float dz = zc - zs;
       support += fabsf(dz) <= a.tau;
       conflict += dz < -a.tau;
@@ -145,35 +125,6 @@ __global__ __launch_bounds__(kCompactThreads) void count_kernel(CompactArgs a) {
     for (int w = 0; w < kCompactThreads / 64; ++w) n += wave_n[w];
     a.blocks[blockIdx.x] = n;
   }
-}
-
-// one workgroup: exclusive scan of the block counts in place, kCompactThreads at a time with a running carry; the total to *count
-__global__ __launch_bounds__(kCompactThreads) void scan_kernel(unsigned* __restrict__ blocks, unsigned nblocks, unsigned* __restrict__ count) {
-  __shared__ unsigned wave_n[kCompactThreads / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned carry = 0;
-  for (unsigned base = 0; base < nblocks; base += kCompactThreads) {
-    const unsigned i = base + threadIdx.x;
-    const unsigned v = i < nblocks ? blocks[i] : 0u;
-    unsigned incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned t = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += t;
-    }
-    if (lane == 63) wave_n[wave] = incl;
-    __syncthreads();
-    unsigned before = carry, all = 0;
-#pragma unroll
-    for (int w = 0; w < kCompactThreads / 64; ++w) {
-      if (w < wave) before += wave_n[w];
-      all += wave_n[w];
-    }
-    if (i < nblocks) blocks[i] = before + incl - v;
-    carry += all;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *count = carry;
 }
 
 __global__ __launch_bounds__(kCompactThreads) void scatter_kernel(CompactArgs a) {

@@ -8,6 +8,11 @@ cloud, coloured from the decoded images when given.  ``ViewFusion.fuse`` is the 
 
 ``render_points`` goes the other way (include/mvd_hip.h: mvd_render_points): a cloud splatted into any cameras with a z-buffer -- a novel
 view, the depth map the rig as a whole implies for a view, and the map of which point each pixel shows.  It synchronises nothing.
+
+``integrate_tsdf`` is the volumetric form of the fusion (include/mvd_hip.h: mvd_tsdf_integrate): every view's depth map integrated into a
+truncated signed distance volume, and ``extract_mesh`` (mvd_mesh_count, mvd_mesh_emit) turns a volume into a closed indexed triangle mesh
+with vertex colours by marching tetrahedra.  ``ViewFusion.mesh`` is both with the model's own depth map and decoder; ``write_ply`` saves a
+mesh too.  The only host synchronisation is the read of the vertex and face counts.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -75,22 +80,9 @@ def _cat_cameras(cs):
     return Cameras(*(torch.cat([getattr(c, k) for c in cs]) for k in ("R", "T", "focal_length", "principal_point")))
 
 
-def fuse_views(latents, cameras, rgb=None, up=1, tau=None, min_support=1, max_conflicts=0, foreground=(0.02, 0.98),
-               depth_scale=DEPTH_SCALE, depth_shift=DEPTH_SHIFT):
-    """Fuse sampled views into a PointCloud.
-
-    latents : (V, 5, S, S) with ``cameras`` the V batch cameras, or (N, V, 5, S, S) with a list of N camera sets (what ``sample_scenes``
-              returns); channel 4 is the depth map in [-1, 1].
-    rgb     : (.., 3, H, H) in [0, 1] with the latents' leading dimensions, or None.  The output grid has P = S * up pixels per side; an
-              image with H > P is resized to P with F.interpolate(mode="area"), H < P is refused (choose a smaller ``up``).
-    up      : integer >= 1.  A fine pixel takes the depth of the latent pixel it lies in and its own ray.
-    tau     : depth agreement in the units of depth_scale; default 0.025 * depth_scale.
-    A point is kept when it is foreground (foreground[0] < normalised depth < foreground[1]), at least ``min_support`` other views agree
-    with it and at most ``max_conflicts`` see their own surface behind it.
-
-    The defaults (tau, min_support, max_conflicts, foreground) are INTERFACE defaults: no trained checkpoint was available when this
-    was written, so nobody has tuned them on real samples -- expect to.  depth_scale / depth_shift must be those of the model that made
-    the latents (``ViewFusion.fuse`` passes its own)."""
+def _check_views(latents, cameras, rgb, up, foreground):
+    """The argument conventions shared by ``fuse_views`` and ``integrate_tsdf``: (V, 5, S, S) latents with one camera set or (N, V, 5, S, S)
+    with a list of N.  Returns (latents (N, V, 5, S, S), camera sets, rgb with a scene dimension or None, single, (N, V, S, up, P), (lo, hi))."""
     if not torch.is_tensor(latents) or latents.dim() not in (4, 5):
         raise ValueError("latents must be a (V, 5, S, S) or (N, V, 5, S, S) tensor")
     single = latents.dim() == 4
@@ -115,11 +107,12 @@ def fuse_views(latents, cameras, rgb=None, up=1, tau=None, min_support=1, max_co
     lo, hi = (float(v) for v in foreground)
     if not lo < hi:
         raise ValueError(f"foreground = {foreground}: need lo < hi")
-    tau = TAU_FRACTION * float(depth_scale) if tau is None else float(tau)
-    if not tau >= 0:
-        raise ValueError(f"tau = {tau}: >= 0")
-    if not (0 <= int(min_support) <= 255 and 0 <= int(max_conflicts) <= 255):
-        raise ValueError("min_support and max_conflicts are counts in [0, 255]")
+    return latents, cameras, rgb, single, (N, V, S, up, P), (lo, hi)
+
+
+def _pack_views(latents, cameras, rgb, N, V, S, up, P):
+    """The checked views as the kernels take them: (lat (N*V, 5, S, S) fp32, camera records on its device, rgb (N*V, 3, P, P) or None) --
+    an image wider than P is area-resized, a narrower one refused."""
     cams = _cat_cameras(cameras)
     if len(cams) != N * V:
         raise ValueError(f"{len(cams)} cameras for {N} x {V} views")
@@ -135,7 +128,33 @@ def fuse_views(latents, cameras, rgb=None, up=1, tau=None, min_support=1, max_co
             rgb = torch.nn.functional.interpolate(rgb, size=(P, P), mode="area")
         rgb = rgb.contiguous()
     lat = latents.reshape(N * V, 5, S, S).float().contiguous()
-    xyz, color, support, index = _run(lat, rgb, pack_cameras(cams).to(dev), N, V, S, up, depth_scale, depth_shift, lo, hi, tau, min_support,
+    return lat, pack_cameras(cams).to(dev), rgb
+
+
+def fuse_views(latents, cameras, rgb=None, up=1, tau=None, min_support=1, max_conflicts=0, foreground=(0.02, 0.98),
+               depth_scale=DEPTH_SCALE, depth_shift=DEPTH_SHIFT):
+    """Fuse sampled views into a PointCloud.
+
+    latents : (V, 5, S, S) with ``cameras`` the V batch cameras, or (N, V, 5, S, S) with a list of N camera sets (what ``sample_scenes``
+              returns); channel 4 is the depth map in [-1, 1].
+    rgb     : (.., 3, H, H) in [0, 1] with the latents' leading dimensions, or None.  The output grid has P = S * up pixels per side; an
+              image with H > P is resized to P with F.interpolate(mode="area"), H < P is refused (choose a smaller ``up``).
+    up      : integer >= 1.  A fine pixel takes the depth of the latent pixel it lies in and its own ray.
+    tau     : depth agreement in the units of depth_scale; default 0.025 * depth_scale.
+    A point is kept when it is foreground (foreground[0] < normalised depth < foreground[1]), at least ``min_support`` other views agree
+    with it and at most ``max_conflicts`` see their own surface behind it.
+
+    The defaults (tau, min_support, max_conflicts, foreground) are INTERFACE defaults: no trained checkpoint was available when this
+    was written, so nobody has tuned them on real samples -- expect to.  depth_scale / depth_shift must be those of the model that made
+    the latents (``ViewFusion.fuse`` passes its own)."""
+    latents, cameras, rgb, single, (N, V, S, up, P), (lo, hi) = _check_views(latents, cameras, rgb, up, foreground)
+    tau = TAU_FRACTION * float(depth_scale) if tau is None else float(tau)
+    if not tau >= 0:
+        raise ValueError(f"tau = {tau}: >= 0")
+    if not (0 <= int(min_support) <= 255 and 0 <= int(max_conflicts) <= 255):
+        raise ValueError("min_support and max_conflicts are counts in [0, 255]")
+    lat, cams, rgb = _pack_views(latents, cameras, rgb, N, V, S, up, P)
+    xyz, color, support, index = _run(lat, rgb, cams, N, V, S, up, depth_scale, depth_shift, lo, hi, tau, min_support,
                                       max_conflicts)
     i = index.long()
     return PointCloud(xyz=xyz, rgb=color, support=support, scene=i // (V * P * P), view=(i // (P * P)) % V,
@@ -250,22 +269,192 @@ def render_points(cloud, cameras, size=256, radius=1, background=(1.0, 1.0, 1.0)
                          hit=index >= 0)
 
 
+@dataclass
+class TSDFVolume:
+    """What ``integrate_tsdf`` returns.  The arrays are (G, G, G) in z, y, x order for (V, 5, S, S) latents and (N, G, G, G) for a list of
+    scenes, on the latents' device; voxel (k, j, i) has its centre at center - half_extent + (index + 0.5) * 2 * half_extent / G per axis."""
+    tsdf: torch.Tensor                       # fp32: the mean truncated signed distance in units of trunc, <= 1; 1 where weight == 0
+    weight: torch.Tensor                     # uint8: the views that observed the voxel
+    rgb: Optional[torch.Tensor]              # (.., 3) fp32: the mean colour sample, 0 where cweight == 0; None without colour
+    cweight: Optional[torch.Tensor]          # uint8: the views that contributed a colour sample
+    center: tuple
+    half_extent: float
+    trunc: float
+
+
+@dataclass
+class TriangleMesh:
+    """What ``extract_mesh`` returns: an indexed triangle mesh, scene after scene.  ``faces`` holds GLOBAL vertex ids; scene s owns the
+    vertices [vertex_start[s], vertex_start[s + 1]) and the faces [face_start[s], face_start[s + 1]).  vertices, faces and rgb live on the
+    volume's device, the two offset tables on the host (they are what the host read to allocate the rest)."""
+    vertices: torch.Tensor                   # (n, 3) fp32 world coordinates
+    faces: torch.Tensor                      # (m, 3) int32, wound so that the normal points out of the surface
+    rgb: Optional[torch.Tensor]              # (n, 3) fp32, or None without colour
+    vertex_start: torch.Tensor               # (N + 1,) int32, host
+    face_start: torch.Tensor                 # (N + 1,) int32, host
+
+    def __len__(self):
+        return int(self.faces.shape[0])
+
+    def scene(self, s):
+        """The sub-mesh of scene s, its faces rebased to its own vertices."""
+        N = int(self.vertex_start.numel()) - 1
+        if not 0 <= s < N:
+            raise ValueError(f"scene {s} of a mesh of {N} scene(s)")
+        v0, v1, f0, f1 = (int(t[i]) for t in (self.vertex_start, self.face_start) for i in (s, s + 1))
+        return TriangleMesh(vertices=self.vertices[v0:v1], faces=self.faces[f0:f1] - v0, rgb=None if self.rgb is None else self.rgb[v0:v1],
+                            vertex_start=torch.tensor([0, v1 - v0], dtype=torch.int32), face_start=torch.tensor([0, f1 - f0], dtype=torch.int32))
+
+
+def _check_box(grid, center, half_extent, N):
+    if int(grid) != grid or not 2 <= grid <= 256:
+        raise ValueError(f"grid = {grid}: an integer in [2, 256]")
+    G = int(grid)
+    if 7 * N * G ** 3 >= 2 ** 31 or 12 * N * (G - 1) ** 3 >= 2 ** 31:
+        raise ValueError(f"grid = {G} for {N} scene(s): the edge and face indices are 31 bits (7 N G^3 and 12 N (G - 1)^3 < 2^31)")
+    center = tuple(float(v) for v in center)
+    if len(center) != 3:
+        raise ValueError(f"center = {center}: three floats")
+    half_extent = float(half_extent)
+    if not half_extent > 0:
+        raise ValueError(f"half_extent = {half_extent}: > 0")
+    return G, center, half_extent
+
+
+def _integrate(lat, rgb, cams, N, V, S, up, G, center, half_extent, trunc, carve, depth_scale, depth_shift, lo, hi):
+    """The launch of mvd_tsdf_integrate.  lat (N*V, 5, S, S), rgb (N*V, 3, P, P) or None, cams (N*V, CAM_RECORD), all fp32 on one GPU.
+    Returns (tsdf, weight, color or None, cweight or None) with a leading scene dimension.  No host synchronisation."""
+    dev = lat.device
+    hip._req(lat), hip._req(cams)
+    tsdf = torch.empty(N, G, G, G, dtype=torch.float32, device=dev)
+    weight = torch.empty(N, G, G, G, dtype=torch.uint8, device=dev)
+    color = cweight = None
+    if rgb is not None:
+        hip._req(rgb)
+        color = torch.empty(N, G, G, G, 3, dtype=torch.float32, device=dev)
+        cweight = torch.empty(N, G, G, G, dtype=torch.uint8, device=dev)
+    hip.check(hip.lib().mvd_tsdf_integrate(hip.ptr(lat), hip.ptr(rgb), hip.ptr(cams), hip.ptr(tsdf), hip.ptr(weight), hip.ptr(color),
+                                           hip.ptr(cweight), N, V, S, up, G, *center, half_extent, trunc, int(carve),
+                                           float(depth_scale), float(depth_shift), lo, hi, hip.stream()))
+    return tsdf, weight, color, cweight
+
+
+def integrate_tsdf(latents, cameras, rgb=None, grid=128, center=(0, 0, 0), half_extent=0.75, trunc=None, carve=True,
+                   foreground=(0.02, 0.98), up=1, depth_scale=DEPTH_SCALE, depth_shift=DEPTH_SHIFT):
+    """Integrate sampled views into a TSDFVolume (include/mvd_hip.h: mvd_tsdf_integrate has the rule in full).
+
+    latents, cameras, rgb, up, foreground : as ``fuse_views`` takes them.  ``up`` only sets the side P = S * up of the colour images.
+    grid        : G, voxels per side, 2 .. 256; center, half_extent: the world box center +- half_extent, the same for every scene.
+    trunc       : the truncation distance in the units of depth_scale; default 3 voxels, 3 * 2 * half_extent / grid.
+    Per voxel centre and view: the view's depth map is looked up where the voxel projects.  On foreground, sdf = surface depth - voxel
+    depth: the voxel is skipped when sdf < -trunc (hidden), else it observes min(1, sdf / trunc), and samples the colour when
+    |sdf| <= trunc.  On background it observes 1 (free space) when ``carve``, nothing otherwise; at a silhouette nothing.
+
+    half_extent, trunc, carve and foreground are INTERFACE defaults: no trained checkpoint was available when this was written, so nobody
+    has tuned them on real samples -- expect to (half_extent = 0.75 merely holds the unit-radius-ish objects of the GSO rig at distance
+    1.5).  depth_scale / depth_shift must be those of the model that made the latents (``ViewFusion.mesh`` passes its own)."""
+    latents, cameras, rgb, single, (N, V, S, up, P), (lo, hi) = _check_views(latents, cameras, rgb, up, foreground)
+    G, center, half_extent = _check_box(grid, center, half_extent, N)
+    trunc = 3 * 2 * half_extent / G if trunc is None else float(trunc)
+    if not trunc > 0:
+        raise ValueError(f"trunc = {trunc}: > 0")
+    lat, cams, rgb = _pack_views(latents, cameras, rgb, N, V, S, up, P)
+    tsdf, weight, color, cweight = _integrate(lat, rgb, cams, N, V, S, up, G, center, half_extent, trunc, bool(carve), depth_scale,
+                                              depth_shift, lo, hi)
+    cut = (lambda t: None if t is None else t[0]) if single else (lambda t: t)
+    return TSDFVolume(tsdf=cut(tsdf), weight=cut(weight), rgb=cut(color), cweight=cut(cweight), center=center, half_extent=half_extent,
+                      trunc=trunc)
+
+
+def _march(tsdf, weight, color, cweight, N, G, center, half_extent, fill):
+    """mvd_mesh_count, the host read of the 2 (N + 1) offsets, mvd_mesh_emit into exact outputs.  tsdf (N, G, G, G) on a GPU; weight None =
+    every voxel observed.  Returns (vertices, colors or None, faces, vertex_start, face_start), the last two on the host."""
+    import ctypes
+    L = hip.lib()
+    dev = tsdf.device
+    tsdf = hip._req(tsdf.float().contiguous())
+    weight = torch.ones(tsdf.shape, dtype=torch.uint8, device=dev) if weight is None else hip._req(weight.to(dev).contiguous(), torch.uint8)
+    if color is not None:
+        color, cweight = hip._req(color.to(dev, torch.float32).contiguous()), hip._req(cweight.to(dev).contiguous(), torch.uint8)
+    nbytes = int(L.mvd_mesh_scratch(N, G))
+    scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    starts = torch.empty(2, N + 1, dtype=torch.int32, device=dev)
+    hip.check(L.mvd_mesh_count(hip.ptr(tsdf), hip.ptr(weight), N, G, hip.ptr(starts[0]), hip.ptr(starts[1]), hip.ptr(scratch), nbytes,
+                               hip.stream()))
+    starts = starts.cpu()                                          # the one host synchronisation
+    nvert, nface = int(starts[0, N]), int(starts[1, N])
+    vertices = torch.empty(nvert, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(nface, 3, dtype=torch.int32, device=dev)
+    colors = torch.empty(nvert, 3, dtype=torch.float32, device=dev) if color is not None else None
+    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
+    hip.check(L.mvd_mesh_emit(hip.ptr(tsdf), hip.ptr(weight), hip.ptr(color), hip.ptr(cweight), N, G, *center, half_extent,
+                              (ctypes.c_float * 3)(*fill), p(vertices), p(colors), p(faces), nvert, nface, hip.ptr(scratch), nbytes,
+                              hip.stream()))
+    return vertices, colors, faces, starts[0].clone(), starts[1].clone()
+
+
+def extract_mesh(volume, fill=(0.5, 0.5, 0.5)):
+    """A TSDFVolume -> TriangleMesh by marching tetrahedra (include/mvd_hip.h: mvd_mesh_count, mvd_mesh_emit): closed wherever the volume
+    is observed, every triangle wound with its normal out of the surface, vertices and faces in a fixed order (the same bits run to run).
+
+    volume : a TSDFVolume, or a bare (G, G, G) / (N, G, G, G) tensor of signed distances (negative inside): every voxel observed, no
+             colour, the box of ``integrate_tsdf``'s defaults (center 0, half_extent 0.75).
+    fill   : the colour of a vertex neither of whose voxels has a colour sample -- an INTERFACE default like those of ``integrate_tsdf``,
+             tuned by nobody."""
+    if isinstance(volume, TSDFVolume):
+        tsdf, weight, color, cweight = volume.tsdf, volume.weight, volume.rgb, volume.cweight
+        center, half_extent = volume.center, volume.half_extent
+    elif torch.is_tensor(volume):
+        tsdf, weight, color, cweight, center, half_extent = volume, None, None, None, (0.0, 0.0, 0.0), 0.75
+    else:
+        raise ValueError("volume must be a TSDFVolume or a (G, G, G) / (N, G, G, G) tensor")
+    if tsdf.dim() not in (3, 4) or len(set(tsdf.shape[-3:])) != 1:
+        raise ValueError(f"volume: tsdf of shape {tuple(tsdf.shape)}, need (G, G, G) or (N, G, G, G)")
+    lead = tuple(tsdf.shape[:-3])
+    N = lead[0] if lead else 1
+    if N < 1:
+        raise ValueError("volume: no scene")
+    G, center, half_extent = _check_box(tsdf.shape[-1], center, half_extent, N)
+    if weight is not None and tuple(weight.shape) != tuple(tsdf.shape):
+        raise ValueError(f"volume: weight of shape {tuple(weight.shape)} for tsdf of shape {tuple(tsdf.shape)}")
+    if (color is None) != (cweight is None):
+        raise ValueError("volume: rgb and cweight go together")
+    if color is not None and (tuple(color.shape) != tuple(tsdf.shape) + (3,) or tuple(cweight.shape) != tuple(tsdf.shape)):
+        raise ValueError(f"volume: rgb of shape {tuple(color.shape)}, cweight of shape {tuple(cweight.shape)} for tsdf of shape {tuple(tsdf.shape)}")
+    fill = tuple(float(v) for v in fill)
+    if len(fill) != 3:
+        raise ValueError(f"fill = {fill}: three floats")
+    if tsdf.dim() == 3:
+        tsdf, weight, color, cweight = (None if t is None else t[None] for t in (tsdf, weight, color, cweight))
+    vertices, colors, faces, vertex_start, face_start = _march(tsdf, weight, color, cweight, N, G, center, half_extent, fill)
+    return TriangleMesh(vertices=vertices, faces=faces, rgb=colors, vertex_start=vertex_start, face_start=face_start)
+
+
 def write_ply(path, cloud):
-    """Binary little-endian PLY: float x y z per vertex, and uchar red green blue (round(255 rgb)) when the cloud has colour."""
+    """Binary little-endian PLY: float x y z per vertex, and uchar red green blue (round(255 rgb)) when the cloud has colour.  A
+    TriangleMesh is written the same way from its vertices, followed by ``element face`` with ``property list uchar int vertex_indices``."""
     import numpy as np
-    n = len(cloud)
+    mesh = isinstance(cloud, TriangleMesh)
+    pos = cloud.vertices if mesh else cloud.xyz
+    n = int(pos.shape[0])
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     if cloud.rgb is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     v = np.zeros(n, dtype=np.dtype(fields))
-    xyz = cloud.xyz.detach().cpu().numpy().astype("<f4")
+    xyz = pos.detach().cpu().numpy().astype("<f4")
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     if cloud.rgb is not None:
         c = np.rint(np.clip(cloud.rgb.detach().cpu().numpy(), 0.0, 1.0) * 255.0).astype("u1")
         v["red"], v["green"], v["blue"] = c[:, 0], c[:, 1], c[:, 2]
     names = {"<f4": "float", "u1": "uchar"}
     header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {n}\n" + \
-        "".join(f"property {names[t]} {k}\n" for k, t in fields) + "end_header\n"
+        "".join(f"property {names[t]} {k}\n" for k, t in fields)
+    body = v.tobytes()
+    if mesh:
+        f = np.zeros(len(cloud), dtype=np.dtype([("n", "u1"), ("v", "<i4", (3,))]))
+        f["n"], f["v"] = 3, cloud.faces.detach().cpu().numpy()
+        header += f"element face {len(cloud)}\nproperty list uchar int vertex_indices\n"
+        body += f.tobytes()
     with open(path, "wb") as fh:
-        fh.write(header.encode("ascii"))
-        fh.write(v.tobytes())
+        fh.write((header + "end_header\n").encode("ascii"))
+        fh.write(body)

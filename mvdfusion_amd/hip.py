@@ -164,6 +164,10 @@ SIGNATURES = {
     "mvd_render_points_scratch": (_sz, [_i, _i]),
     "mvd_render_points": (_i, [_vp] * 4 + [_sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvd_render_points_stages": (_i, [_vp] * 4 + [_sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "mvd_tsdf_integrate": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _vp]),
+    "mvd_mesh_scratch": (_sz, [_i, _i]),
+    "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_mesh_emit": (_i, [_vp] * 4 + [_i, _i, _f, _f, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),

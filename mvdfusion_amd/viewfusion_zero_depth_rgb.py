@@ -662,12 +662,30 @@ class ViewFusion(nn.Module):
         otherwise pass ``rgb=`` or get an uncoloured cloud.  Other keywords: tau, min_support, max_conflicts, foreground."""
         from .fusion import fuse_views
         if decode:
-            S = latents.shape[-1]
-            flat = latents.reshape(-1, 5, S, S)[:, :4]
-            img = torch.cat([self.decode(c) for c in flat.split(self.vae_max_batch)]).float()
-            kw["rgb"] = img.reshape(*latents.shape[:-3], 3, img.shape[-2], img.shape[-1])
+            kw["rgb"] = self._decoded(latents)
         return fuse_views(latents, batch_cameras, up=up, depth_scale=self.view_attn.depth_scale, depth_shift=self.view_attn.depth_shift,
                           **kw)
+
+    def _decoded(self, latents):
+        """``self.decode`` of the four image channels of (.., 5, S, S) latents, with their leading dimensions."""
+        S = latents.shape[-1]
+        flat = latents.reshape(-1, 5, S, S)[:, :4]
+        img = torch.cat([self.decode(c) for c in flat.split(self.vae_max_batch)]).float()
+        return img.reshape(*latents.shape[:-3], 3, img.shape[-2], img.shape[-1])
+
+    @torch.no_grad()
+    def mesh(self, latents, batch_cameras, grid=128, up=8, decode=True, **kw):
+        """The sampled views as a closed triangle mesh with vertex colours: fusion.integrate_tsdf with this model's depth_scale /
+        depth_shift, then fusion.extract_mesh.  latents and cameras as ``fuse`` takes them; decode: colour from ``self.decode``
+        (8 S pixels per side, so up <= 8), otherwise pass ``rgb=`` or get an uncoloured mesh.  Other keywords: center, half_extent, trunc,
+        carve, foreground (integrate_tsdf) and fill (extract_mesh)."""
+        from .fusion import extract_mesh, integrate_tsdf
+        if decode:
+            kw["rgb"] = self._decoded(latents)
+        fill = {"fill": kw.pop("fill")} if "fill" in kw else {}
+        vol = integrate_tsdf(latents, batch_cameras, grid=grid, up=up, depth_scale=self.view_attn.depth_scale,
+                             depth_shift=self.view_attn.depth_shift, **kw)
+        return extract_mesh(vol, **fill)
 
     @torch.no_grad()
     def render(self, cloud, cameras, size=256, radius=1, **kw):
