@@ -586,6 +586,77 @@ int mvd_render_points_stages(const float* xyz, const float* color, const int* sc
                              float* rgb, void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rendering a triangle mesh into cameras: z-buffered rasterisation (csrc/raster.hip; host: mvdfusion_amd/fusion.py render_mesh).
+ * Not in the reference either.  The mesh counterpart of mvd_render_points with the same 64-bit z-buffer: a hole-free novel view, the depth
+ * map the surface implies for a camera, and the map of which face each pixel shows.  It takes the arrays mvd_mesh_emit (below) makes.
+ *
+ * mvd_render_mesh:
+ *   vertices (nvert, 3) fp32 world points; colors (nvert, 3) fp32 or NULL; faces (nface, 3) int32 GLOBAL vertex ids; vertex_start,
+ *   face_start: nscene + 1 int32 DEVICE values each, as mvd_mesh_count writes them -- scene s owns the vertices
+ *   [vertex_start[s], vertex_start[s + 1]) and the faces [face_start[s], face_start[s + 1]) (values are clamped to [0, nvert] and
+ *   [0, nface]); cams (nscene*M, MVD_CAM_RECORD): M target cameras per scene, camera c = s*M + j; P: output side in pixels; cull: 0 or 1;
+ *   znear >= 0; empty_depth; background: 3 floats on the HOST (read at the call; may be NULL when colors is NULL).
+ *   Projection: for every vertex of face f of scene s and camera j of that scene, (u, w, zc) = NDC and camera-space z exactly as
+ *               mvd_render_points computes them (one function in the source).  px = (1 - u) * P / 2 - 0.5, py alike from w: the pixel
+ *               coordinates of the point renderer, in which pixel (x, y) has its centre at the integers (x, y).  Below a, b, c are the
+ *               face's three vertices in the order faces lists them, (ax, ay) ... their pixel coordinates, z_a ... their zc.
+ *   Dropped   : face f = (a, b, c) draws nothing into camera j unless ALL of
+ *                 - the three ids lie in the scene's vertex range (no other vertex is ever read);
+ *                 - z_a, z_b, z_c > znear.  There is NO near-plane clipping: a face with one vertex at or behind znear is dropped whole
+ *                   (the rigs here look at an object in front of them);
+ *                 - the six pixel coordinates are finite (a NaN anywhere drops the face);
+ *                 - area2 = (bx - ax) * (cy - ay) - (by - ay) * (cx - ax) is finite and non-zero (mvd_mesh_emit emits zero-area
+ *                   triangles by design: they draw nothing);
+ *                 - with cull = 1: area2 < 0, the face is a FRONT face.  A face is front when its geometric normal n = (b - a) x (c - a)
+ *                   -- which mvd_mesh_emit winds out of the surface -- faces the camera: n . a < 0 with a, b, c in camera space (a
+ *                   rotation keeps the cross product).  n . a is the determinant det[a; b; c], and the signed area of the triangle
+ *                   (x / z, y / z) is det[a; b; c] / (z_a z_b z_c); px and py both DEcrease with x / z and y / z, which cancels, and the
+ *                   focal lengths (assumed of one sign, as in every camera here) and z are positive: area2 has the sign of n . a.
+ *                   cull = 0 draws both sides.
+ *   Coverage  : with e_a = (bx - x) * (cy - y) - (by - y) * (cx - x), e_b = (cx - x) * (ay - y) - (cy - y) * (ax - x),
+ *               e_c = (ax - x) * (by - y) - (ay - y) * (bx - x) and sg = +1 for area2 > 0, else -1, pixel (x, y) is covered when
+ *               e_a * sg >= 0, e_b * sg >= 0 and e_c * sg >= 0.  Edges are inclusive and there is no top-left rule: a centre exactly on a
+ *               shared edge is covered by both faces and the depth rule decides.  Candidates are the integer pixels of
+ *               [ceil(min x), floor(max x)] x [ceil(min y), floor(max y)] clipped to [0, P - 1] (the conversion to int happens after
+ *               the clip).
+ *   Depth, barycentrics (perspective-correct), in THIS order: q_i = (e_i / area2) / z_i; iz = (q_a + q_b) + q_c; z = 1 / iz;
+ *               b_i = q_i * z.  A covered pixel whose z is not finite or not > znear draws nothing.
+ *   Depth rule: every drawn pixel takes the minimum of key = (uint64(bits(z)) << 32) | f.  z > 0, so the bit pattern orders like the
+ *               value: the nearest face wins, between faces with identical z bits the one with the lowest id.  The result is a pure
+ *               function of the inputs, bit-identical run to run whatever order the atomics arrive in.  An empty pixel holds all ones.
+ *   Outputs per (camera, pixel), planar like those of mvd_render_points:
+ *               face_out (nscene*M, P, P) int32 = the winner's f, or -1;
+ *               depth (nscene*M, P, P) fp32 = its z, the bits of the key's high word, or empty_depth;
+ *               bary (nscene*M, 3, P, P) fp32 = b_a, b_b, b_c of the winner at the pixel, or 0;
+ *               normal (nscene*M, 3, P, P) fp32 = the face's unit normal in camera space, or 0: n = (b - a) x (c - a) from the WORLD
+ *               positions, divided by its largest |component| m, rotated (n_j = n_0 R[0][j] + n_1 R[1][j] + n_2 R[2][j], the
+ *               convention of the projection), divided by sqrt((n_0^2 + n_1^2) + n_2^2), and negated when n_2 > 0: normal_z <= 0 always,
+ *               the normal points at the image plane whichever side of the face is seen.  (Decided on normal_z, not on n . a: at a
+ *               grazing angle off the optical axis the two can differ.)  m == 0 or not finite: 0;
+ *               rgb (nscene*M, 3, P, P) fp32 = (b_a * c_a + b_b * c_b) + b_c * c_c per channel, or background -- with colors NULL rgb must
+ *               be NULL.
+ *   All fp32, compiled without contraction.  nface, nvert <= 2^31 - 1; nscene * M * P * P < 2^31; nscene * M <= 65535.  nface = 0 is a
+ *   valid call (vertices and faces may be NULL) and gives empty images.
+ *   scratch   : the 64-bit z-buffer, mvd_render_mesh_scratch(nscene*M, P) = nscene*M*P*P*8 bytes (0 for a non-positive argument),
+ *               8-byte aligned.
+ *   Three enqueues on the caller's stream: fill the z-buffer with ones; the raster kernel -- one thread per (face, camera), workgroups
+ *   never straddle scenes or cameras; a thread walks a clipped bounding box of at most 64 pixels itself, larger boxes are walked by the
+ *   thread's whole wavefront, 64 pixels at a time; one 64-bit unsigned atomicMin per drawn pixel, device scope; the resolve kernel -- one
+ *   thread per output pixel, which evaluates the winner again through the same expressions.  Every argument is checked before anything
+ *   is enqueued.
+ * mvd_render_mesh_stages: the same call restricted to the stages in `stages` (an OR of MVD_RENDER_FILL / _SPLAT / _RESOLVE as for the
+ *   points, _SPLAT being the raster kernel; MVD_RENDER_ALL is mvd_render_mesh). */
+size_t mvd_render_mesh_scratch(int ncam, int P);
+int mvd_render_mesh(const float* vertices, const float* colors, const int* faces, const int* vertex_start, const int* face_start,
+                    const float* cams, size_t nvert, size_t nface, int nscene, int M, int P, int cull, float znear, float empty_depth,
+                    const float* background, int* face_out, float* depth, float* bary, float* normal, float* rgb, void* scratch,
+                    size_t scratch_bytes, mvd_stream_t stream);
+int mvd_render_mesh_stages(const float* vertices, const float* colors, const int* faces, const int* vertex_start, const int* face_start,
+                           const float* cams, size_t nvert, size_t nface, int nscene, int M, int P, int cull, float znear,
+                           float empty_depth, const float* background, int* face_out, float* depth, float* bary, float* normal, float* rgb,
+                           void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Volumetric fusion: the sampled RGB-D views integrated into a truncated signed distance volume (TSDF), and a watertight indexed triangle
  * mesh with vertex colours extracted from it by marching tetrahedra (csrc/tsdf.hip, csrc/tsdf_mesh.hpp; host: mvdfusion_amd/fusion.py
  * integrate_tsdf, extract_mesh).  Not in the reference either.  Cameras, projection, depth map and depth lookup are those of the point

@@ -13,6 +13,10 @@ view, the depth map the rig as a whole implies for a view, and the map of which 
 truncated signed distance volume, and ``extract_mesh`` (mvd_mesh_count, mvd_mesh_emit) turns a volume into a closed indexed triangle mesh
 with vertex colours by marching tetrahedra.  ``ViewFusion.mesh`` is both with the model's own depth map and decoder; ``write_ply`` saves a
 mesh too.  The only host synchronisation is the read of the vertex and face counts.
+
+``render_mesh`` brings a mesh back into images (include/mvd_hip.h: mvd_render_mesh): a triangle rasteriser with the point renderer's 64-bit
+z-buffer -- a hole-free novel view, the depth map the surface implies for a camera, perspective-correct barycentrics, face normals and
+the map of which face each pixel shows.  ``ViewFusion.render_mesh`` binds the model's depth map.  It synchronises nothing.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -161,6 +165,12 @@ def fuse_views(latents, cameras, rgb=None, up=1, tau=None, min_support=1, max_co
                       pixel=torch.stack([(i // P) % P, i % P], dim=1), index=index)
 
 
+def _depth_latent(depth, hit, scale, shift):
+    """clamp(2 (z - shift) / scale - 1, -1, 1) with empty pixels at +1: the one formula behind ``depth_latent`` of both renderers."""
+    lat = torch.clamp(2.0 * (depth - float(shift)) / float(scale) - 1.0, -1.0, 1.0)
+    return torch.where(hit, lat, torch.ones_like(lat))
+
+
 @dataclass
 class RenderedViews:
     """What ``render_points`` returns; the leading scene dimension is present only when a list of camera sets was passed."""
@@ -176,8 +186,7 @@ class RenderedViews:
         inverse of ``fuse_views``' map z = clamp((lat + 1) / 2, 0, 1) * scale + shift.  Defaults: DEPTH_SCALE, DEPTH_SHIFT."""
         scale = self._depth_map[0] if depth_scale is None else depth_scale
         shift = self._depth_map[1] if depth_shift is None else depth_shift
-        lat = torch.clamp(2.0 * (self.depth - float(shift)) / float(scale) - 1.0, -1.0, 1.0)
-        return torch.where(self.hit, lat, torch.ones_like(lat))
+        return _depth_latent(self.depth, self.hit, scale, shift)
 
 
 def _render(xyz, color, scene_start, cams, N, M, P, radius, znear, empty_depth, background):
@@ -428,6 +437,125 @@ def extract_mesh(volume, fill=(0.5, 0.5, 0.5)):
         tsdf, weight, color, cweight = (None if t is None else t[None] for t in (tsdf, weight, color, cweight))
     vertices, colors, faces, vertex_start, face_start = _march(tsdf, weight, color, cweight, N, G, center, half_extent, fill)
     return TriangleMesh(vertices=vertices, faces=faces, rgb=colors, vertex_start=vertex_start, face_start=face_start)
+
+
+@dataclass
+class RenderedMesh:
+    """What ``render_mesh`` returns; the leading scene dimension is present only when a list of camera sets was passed."""
+    rgb: Optional[torch.Tensor]              # (.., M, 3, P, P) fp32: the vertex colours interpolated perspective-correctly, or the background;
+    #                                          None for a mesh without colour
+    depth: torch.Tensor                      # (.., M, P, P) fp32: camera-space z of the surface, or empty_depth
+    face: torch.Tensor                       # (.., M, P, P) int32: the face the pixel shows (its row in mesh.faces), or -1
+    bary: torch.Tensor                       # (.., M, 3, P, P) fp32: perspective-correct barycentrics of that face's three vertices, or 0
+    normal: torch.Tensor                     # (.., M, 3, P, P) fp32: the face's unit normal in camera space turned to normal_z <= 0, or 0
+    hit: torch.Tensor                        # (.., M, P, P) bool: face >= 0
+
+    _depth_map = (DEPTH_SCALE, DEPTH_SHIFT)  # depth_latent's defaults (not a field; ViewFusion.render_mesh binds the model's own per instance)
+
+    def depth_latent(self, depth_scale=None, depth_shift=None):
+        """The depth map in the model's depth-channel convention, exactly as ``RenderedViews.depth_latent`` forms it."""
+        scale = self._depth_map[0] if depth_scale is None else depth_scale
+        shift = self._depth_map[1] if depth_shift is None else depth_shift
+        return _depth_latent(self.depth, self.hit, scale, shift)
+
+    def shaded(self, background=(1.0, 1.0, 1.0)):
+        """(.., M, 3, P, P): clamp(-normal_z, 0, 1) as grey where hit, the background elsewhere -- a headlight image, the way to look
+        at a mesh without colour."""
+        grey = torch.clamp(-self.normal[..., 2:3, :, :], 0.0, 1.0).expand(*self.normal.shape)
+        bg = torch.tensor([float(v) for v in background], dtype=grey.dtype, device=grey.device).reshape(3, 1, 1).expand_as(grey)
+        return torch.where(self.hit.unsqueeze(-3), grey, bg)
+
+
+def _raster(vertices, colors, faces, vertex_start, face_start, cams, N, M, P, cull, znear, empty_depth, background):
+    """The three enqueues of mvd_render_mesh.  vertices (n, 3), colors (n, 3) or None, faces (m, 3) int32, vertex_start / face_start
+    (N + 1) int32, cams (N*M, CAM_RECORD), all contiguous on one GPU.  Returns (rgb or None, depth, face, bary, normal) of shapes
+    (N*M, [3,] P, P).  No host synchronisation."""
+    import ctypes
+    L = hip.lib()
+    dev, nvert, nface = vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    hip._req(vertices), hip._req(cams), hip._req(faces, torch.int32), hip._req(vertex_start, torch.int32), hip._req(face_start, torch.int32)
+    if colors is not None:
+        hip._req(colors)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    face = torch.empty(N * M, P, P, dtype=torch.int32, device=dev)
+    depth, bary, normal = f32(N * M, P, P), f32(N * M, 3, P, P), f32(N * M, 3, P, P)
+    rgb = f32(N * M, 3, P, P) if colors is not None else None
+    nbytes = int(L.mvd_render_mesh_scratch(N * M, P))
+    scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    bg = (ctypes.c_float * 3)(*background)
+    if colors is not None and nvert == 0:
+        colors = f32(1, 3)                   # (an empty mesh with colour: the library pairs a non-NULL colors with rgb; nothing reads it)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_render_mesh(p(vertices), hip.ptr(colors), p(faces), hip.ptr(vertex_start), hip.ptr(face_start),
+                                hip.ptr(cams), nvert, nface, N, M, P, int(cull), float(znear), float(empty_depth), bg, hip.ptr(face),
+                                hip.ptr(depth), hip.ptr(bary), hip.ptr(normal), hip.ptr(rgb), hip.ptr(scratch), nbytes, hip.stream()))
+    return rgb, depth, face, bary, normal
+
+
+def render_mesh(mesh, cameras, size=256, cull=True, background=(1.0, 1.0, 1.0), znear=1e-3, empty_depth=float("inf")):
+    """Render a TriangleMesh into cameras by z-buffered rasterisation (include/mvd_hip.h: mvd_render_mesh has the rule) -> RenderedMesh.
+
+    mesh    : a TriangleMesh of one or several scenes (what ``extract_mesh`` returns).
+    cameras : M cameras (anything with .R .T .focal_length .principal_point): the mesh must be one scene's.  Or a list of N sets of M
+              cameras each, N the mesh's scene count: scene s goes into set s, and the outputs get a leading dimension N.
+    size    : P, the output side in pixels.  Per pixel centre the nearest face covering it with camera z > znear wins (ties: the lowest
+              face id); depth, colour and barycentrics are interpolated perspective-correctly.
+    cull    : drop back faces -- ``extract_mesh`` winds every triangle with its normal out of the surface.  A face with a vertex at or
+              behind znear is dropped whole (no near-plane clipping).
+    background, empty_depth : what a pixel no face covers holds in rgb / depth.
+    Nothing is read back from the device; the mesh's two offset tables are copied to it."""
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a TriangleMesh")
+    vertices, faces, colors = mesh.vertices, mesh.faces, mesh.rgb
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"mesh: vertices of shape {tuple(vertices.shape)}, need (n, 3)")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"mesh: faces of shape {tuple(faces.shape)} and dtype {faces.dtype}, need (m, 3) int32")
+    nvert, nface = int(vertices.shape[0]), int(faces.shape[0])
+    if nface > 2 ** 31 - 1 or nvert > 2 ** 31 - 1:
+        raise ValueError(f"mesh: {nface} faces of {nvert} vertices, the face and vertex indices are 31 bits")
+    if colors is not None and tuple(colors.shape) != (nvert, 3):
+        raise ValueError(f"mesh: rgb of shape {tuple(colors.shape)} for {nvert} vertices")
+    scenes = int(mesh.vertex_start.numel()) - 1
+    if scenes < 1 or mesh.vertex_start.dim() != 1 or tuple(mesh.face_start.shape) != (scenes + 1,):
+        raise ValueError(f"mesh: vertex_start of shape {tuple(mesh.vertex_start.shape)}, face_start of shape {tuple(mesh.face_start.shape)}: "
+                         "need (N + 1,) each, N >= 1")
+    if int(size) != size or size < 1:
+        raise ValueError(f"size = {size}: an integer >= 1")
+    P, znear = int(size), float(znear)
+    if not znear >= 0:
+        raise ValueError(f"znear = {znear}: >= 0")
+    if cull not in (True, False, 0, 1):
+        raise ValueError(f"cull = {cull}: True or False")
+    background = tuple(float(v) for v in background)
+    if len(background) != 3:
+        raise ValueError(f"background = {background}: three floats")
+    single = not isinstance(cameras, (list, tuple))
+    sets = [_as_cameras(c) for c in ([cameras] if single else cameras)]
+    N = len(sets)
+    if N < 1:
+        raise ValueError("cameras: an empty list")
+    M = len(sets[0])
+    if M < 1 or any(len(c) != M for c in sets):
+        raise ValueError(f"cameras: every scene needs the same number M >= 1 of cameras, got {[len(c) for c in sets]}")
+    if N != scenes:
+        raise ValueError(f"cameras: {N} camera set(s) for a mesh of {scenes} scene(s)" + (" (pass a list of sets)" if single else ""))
+    if N * M > 65535:
+        raise ValueError(f"cameras: {N} x {M} cameras, at most 65535 per call")
+    if N * M * P * P >= 2 ** 31:
+        raise ValueError(f"size = {P}: {N * M * P * P} pixels for {N} x {M} cameras, the pixel index is 31 bits")
+    dev = vertices.device
+    vertices = vertices.float().contiguous()
+    faces = faces.to(dev).contiguous()
+    colors = None if colors is None else colors.to(dev, torch.float32).contiguous()
+    vertex_start, face_start = (t.to(torch.int32).to(dev).contiguous() for t in (mesh.vertex_start, mesh.face_start))
+    cams = Cameras(*(torch.cat([getattr(c, k) for c in sets]) for k in ("R", "T", "focal_length", "principal_point")))
+    rgb, depth, face, bary, normal = _raster(vertices, colors, faces, vertex_start, face_start, pack_cameras(cams).to(dev).contiguous(), N, M,
+                                             P, bool(cull), znear, empty_depth, background)
+    lead = (M,) if single else (N, M)
+    face = face.reshape(*lead, P, P)
+    return RenderedMesh(rgb=None if rgb is None else rgb.reshape(*lead, 3, P, P), depth=depth.reshape(*lead, P, P), face=face,
+                        bary=bary.reshape(*lead, 3, P, P), normal=normal.reshape(*lead, 3, P, P), hit=face >= 0)
 
 
 def write_ply(path, cloud):

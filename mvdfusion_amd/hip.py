@@ -50,7 +50,7 @@ TOKEN_DIM, TOKEN_LD = 723, 736
 FUSE_FOREGROUND = 1                                        # flags byte of mvd_fuse_points
 FUSE_STAGE_AUTO, FUSE_STAGE_GLOBAL, FUSE_STAGE_LDS = 0, 1, 2
 SPLAT_MAX_RADIUS = 4                                       # MVD_SPLAT_MAX_RADIUS: the largest footprint radius of mvd_render_points
-RENDER_FILL, RENDER_SPLAT, RENDER_RESOLVE, RENDER_ALL = 1, 2, 4, 7      # stages of mvd_render_points_stages
+RENDER_FILL, RENDER_SPLAT, RENDER_RESOLVE, RENDER_ALL = 1, 2, 4, 7      # stages of mvd_render_points_stages and mvd_render_mesh_stages
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -164,6 +164,9 @@ SIGNATURES = {
     "mvd_render_points_scratch": (_sz, [_i, _i]),
     "mvd_render_points": (_i, [_vp] * 4 + [_sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _vp, _sz, _vp]),
     "mvd_render_points_stages": (_i, [_vp] * 4 + [_sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "mvd_render_mesh_scratch": (_sz, [_i, _i]),
+    "mvd_render_mesh": (_i, [_vp] * 6 + [_sz, _sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f)] + [_vp] * 6 + [_sz, _vp]),
+    "mvd_render_mesh_stages": (_i, [_vp] * 6 + [_sz, _sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f)] + [_vp] * 6 + [_sz, _i, _vp]),
     "mvd_tsdf_integrate": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _vp]),
     "mvd_mesh_scratch": (_sz, [_i, _i]),
     "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),

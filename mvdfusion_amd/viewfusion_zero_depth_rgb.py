@@ -702,6 +702,22 @@ class ViewFusion(nn.Module):
         return out
 
     @torch.no_grad()
+    def render_mesh(self, mesh, cameras, size=256, **kw):
+        """A mesh of ``self.mesh`` seen from any cameras (fusion.render_mesh; ``depth_latent`` of the result defaults to this model's
+        depth_scale / depth_shift).  cameras: M cameras, or a list of N sets of M for an N-scene mesh.  Other keywords: cull, background,
+        znear, empty_depth.
+
+            mesh = model.mesh(latents, batch_cameras)
+            views = model.render_mesh(mesh, batch_cameras, size=256)   # views.rgb (V, 3, 256, 256), views.depth, views.face, views.normal
+            lat4 = views.depth_latent()                                # the depth the surface implies for each view, as a depth channel
+            grey = views.shaded()                                      # a headlight image (the way to look at a mesh made with decode=False)
+        """
+        from .fusion import render_mesh
+        out = render_mesh(mesh, cameras, size=size, **kw)
+        out._depth_map = (float(self.view_attn.depth_scale), float(self.view_attn.depth_shift))
+        return out
+
+    @torch.no_grad()
     def p_losses(self, batch, trainer_config, noise_source=None, _aux=None):
         """viewfusion_zero_depth_rgb.py:362-392 -- the training objective's FORWARD pass on the HIP path: prepare_batch, shared
         random timestep, q_sample, apply_model (cfg 1, condition dropout when self.training), MSE against the noise.
