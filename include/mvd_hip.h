@@ -657,6 +657,67 @@ int mvd_render_mesh_stages(const float* vertices, const float* colors, const int
                            void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Measuring geometry: the exact nearest target point of every query point (csrc/nearest.hip; host: mvdfusion_amd/fusion.py
+ * nearest_points, compare_geometry).  Not in the reference either.  Accuracy, completeness, Chamfer distance and precision / recall /
+ * F-score between two fused clouds (or the surface samples of two meshes) are reductions of these distances.
+ *
+ * mvd_nearest_points:
+ *   query (nq, 3), target (nt, 3) fp32 world points; query_start, target_start: nscene + 1 int32 DEVICE values each, non-decreasing (the
+ *   arrays are sorted by scene); every value is clamped to [0, nq] or [0, nt] before it indexes anything.
+ *   Scenes    : query i belongs to scene s when query_start[s] <= i < query_start[s + 1]; its candidates are the targets j with
+ *               target_start[s] <= j < target_start[s + 1].
+ *   Distance  : d2(i, j) = ((qx - tx) * (qx - tx) + (qy - ty) * (qy - ty)) + (qz - tz) * (qz - tz) in fp32, in exactly this order, every
+ *               operation rounded once (compiled without contraction).
+ *   Selection : starts from best = +inf with no winner; candidate j wins only with d2 < best, or d2 == best and j below the winner so
+ *               far.  The result is the minimum of d2 over the candidates, between equal minima the lowest j: a pure function of the
+ *               inputs, whatever order the candidates are met in.
+ *   Outputs   : index (nq,) int32 = the winner's j, a global row of target; dist2 (nq,) fp32 = its d2.  Without a winner index = -1 and
+ *               dist2 = +inf.  Every element [0, nq) of both is written.
+ *   The strict comparison against +inf decides every odd case, with no rule of its own: a target with a NaN or infinite coordinate (or
+ *   so far away that d2 overflows) is never chosen; a query with a non-finite coordinate has no winner; neither has a query whose scene
+ *   holds no target, nor a query outside [query_start[0], query_start[nscene]).
+ *   method    : MVD_NN_BRUTE -- every query of a scene against every target of the scene, the targets staged through LDS in tiles of
+ *               16-byte records (x, y, z, j) that all lanes read at the same address.
+ *               MVD_NN_GRID -- per scene a uniform grid over the bounding box of the scene's finite targets (found on the device;
+ *               minimum and maximum are exact in any order): cubic cells of side h = max(largest extent / grid, 1e-30), per axis
+ *               clamp(floor(extent / h) + 1, 1, grid) of them, so coincident, collinear and coplanar targets give a valid grid.  Build:
+ *               box, count per cell (integer atomics), exclusive scan, scatter into a cell-sorted copy of records (x, y, z, j); a target
+ *               with a non-finite coordinate is in no cell.  The order inside a cell differs from run to run; the selection rule does
+ *               not see it.  Query: one thread per query, clamped to its cell, visits the Chebyshev shells of cells r = 0, 1, ... around
+ *               it and stops after shell r once best lies strictly below a lower bound of d2 to every point of an unvisited cell.  The
+ *               bound is taken from the query's own position in cell units against the faces of the visited block, plus what the query
+ *               lies outside the box along the other axes, shrunk by 0.1 % and 0.001 cell -- orders above the fp32 rounding of the
+ *               cell assignment, the bound and d2.  The search is exact: index and dist2 are the bits MVD_NN_BRUTE gives.
+ *               MVD_NN_AUTO -- chosen from nt / nscene on the host (csrc/nearest.hip: kGridMinTargets; DESIGN.md section
+ *               6.000000000000000 has the sweep); nt = 0 runs the brute kernel, which writes -1 / +inf.
+ *   grid      : cells per axis of MVD_NN_GRID, 1 .. 256, or 0 for the library's choice from nt / nscene (a host computation that aims
+ *               at a few targets per occupied cell of a surface, at most 256).  Ignored by MVD_NN_BRUTE.
+ *   Bounded whatever the data: the shell loop ends at r = grid at the latest; cell ranges read back from the scratch are clamped to
+ *   [0, nt] and a record counts only when its j lies in the scene's target range; no NaN or out-of-range value reaches a float-to-int
+ *   conversion unclamped.
+ *   nq, nt <= 2^31 - 1; 1 <= nscene <= 65535; nscene * grid^3 <= 2^31 - 1.  nq = 0 and nt = 0 are valid calls (query, index, dist2 may
+ *   be NULL with nq = 0, target with nt = 0).
+ *   scratch   : mvd_nearest_points_scratch(nt, nscene, method, grid) bytes, 16-byte aligned; 0 bytes (NULL allowed) for MVD_NN_BRUTE
+ *               and wherever MVD_NN_AUTO resolves to it.  The function returns 0 for a non-positive or out-of-range argument.
+ *   Everything is enqueued on the caller's stream with no host synchronisation; every argument is checked before anything is enqueued.
+ * mvd_nearest_points_stages: the same call restricted to the stages in `stages` (an OR of MVD_NN_BUILD -- box, count, scan, scatter;
+ *   nothing for MVD_NN_BRUTE -- and MVD_NN_QUERY; MVD_NN_ALL is mvd_nearest_points) -- for timing the two (tools/bench_nearest.py) or
+ *   for several query sets against one built grid. */
+#define MVD_NN_AUTO 0
+#define MVD_NN_BRUTE 1
+#define MVD_NN_GRID 2
+#define MVD_NN_BUILD 1
+#define MVD_NN_QUERY 2
+#define MVD_NN_ALL 3
+size_t mvd_nearest_points_scratch(size_t nt, int nscene, int method, int grid);
+int mvd_nearest_points(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq, size_t nt,
+                       int nscene, int method, int grid, int* index, float* dist2, void* scratch, size_t scratch_bytes,
+                       mvd_stream_t stream);
+int mvd_nearest_points_stages(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,
+                              size_t nt, int nscene, int method, int grid, int* index, float* dist2, void* scratch, size_t scratch_bytes,
+                              int stages, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Volumetric fusion: the sampled RGB-D views integrated into a truncated signed distance volume (TSDF), and a watertight indexed triangle
  * mesh with vertex colours extracted from it by marching tetrahedra (csrc/tsdf.hip, csrc/tsdf_mesh.hpp; host: mvdfusion_amd/fusion.py
  * integrate_tsdf, extract_mesh).  Not in the reference either.  Cameras, projection, depth map and depth lookup are those of the point

@@ -1,0 +1,432 @@
+// The exact nearest target point of every query point (include/mvd_hip.h: mvd_nearest_points has the rule in full).
+//
+// BRUTE: one thread per query; the workgroup walks the scenes its queries belong to and stages each scene's targets through LDS in tiles
+// of kTile 16-byte records (x, y, z, j).  Every lane reads the same record at once: a broadcast, no bank conflict.  Targets arrive in
+// ascending j, so the strict comparison alone keeps the lowest j between equal minima.
+// GRID: box_kernel (the bounding box of every scene's finite targets: order-preserving integer keys under atomicMin, exact in any order)
+// -> count_kernel (one integer atomicAdd per finite target into its cell) -> an exclusive scan of the cell counts (two levels: chunk
+// sums, scan_kernel of fusion_common.hpp over the chunk sums, chunk scans) -> scatter_kernel (the atomicAdd that hands out a record's
+// place turns a cell's begin into its end: afterwards cell c owns the records [cells[c - 1], cells[c])) -> grid_query_kernel, one
+// thread per query through nn_query_grid: Chebyshev shells of cells around the query's (clamped) cell, a row of cells along x being ONE
+// range of records, until the best distance lies below the lower bound of everything unvisited.
+// The per-element pieces (nn_scene_grid, nn_cell, nn_query_grid, nn_find_scene) are host-and-device functions, so that the search can
+// be run serially on a CPU against the brute force.
+//
+// Not tried: sorting the queries by cell, one wavefront per query cell, a hashed grid.
+#include "fusion_common.hpp"
+
+namespace {
+
+#define NN_HD __host__ __device__ __forceinline__
+
+constexpr int kNNThreads = 256;
+constexpr int kTile = 1024;                           // records per LDS tile of the brute kernel (16 KB)
+constexpr int kMaxGrid = 256;
+constexpr int kChunk = 4096;                          // cell counts one workgroup scans: 16 consecutive words per thread
+constexpr float kHFloor = 1e-30f;                     // the positive floor of the cell side
+constexpr float kUClamp = 1e9f;                       // a query's position in cell units is clamped to this (towards the box: conservative)
+// MVD_NN_AUTO: the grid from this many targets per scene upward; automatic grid = sqrt(targets per scene / kGridDivisor)
+// (DESIGN.md section 6.000000000000000 has the sweeps both come from)
+constexpr long long kGridMinTargets = 1024;
+constexpr float kGridDivisor = 16.f;
+
+struct alignas(16) Rec {
+  float x, y, z;
+  int id;
+};
+
+struct NNArgs {
+  const float *query, *target;
+  const int *qstart, *tstart;
+  int* index;
+  float* dist2;
+  Rec* sorted;                                        // nt records, cell after cell
+  unsigned* box;                                      // per scene: keys of min x, y, z, then ~keys of max x, y, z (both under atomicMin)
+  unsigned* cells;                                    // nscene * g^3 words padded to kChunk: counts -> begins -> ends
+  unsigned* blocks;                                   // one word per chunk, and the total behind them
+  long long nq, nt;
+  int nscene, g;
+};
+
+// fp32 -> unsigned that orders like the value (-inf lowest; NaNs at the two ends, and no NaN is ever encoded here)
+NN_HD unsigned nn_key(float v) {
+#ifdef __HIP_DEVICE_COMPILE__
+  const unsigned b = __float_as_uint(v);
+#else
+  unsigned b;
+  __builtin_memcpy(&b, &v, 4);
+#endif
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+NN_HD float nn_unkey(unsigned k) {
+  const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+#ifdef __HIP_DEVICE_COMPILE__
+  return __uint_as_float(b);
+#else
+  float v;
+  __builtin_memcpy(&v, &b, 4);
+  return v;
+#endif
+}
+
+NN_HD bool nn_finite(float v) { return fabsf(v) < INFINITY; }      // (a NaN compares false)
+
+NN_HD long long nn_clamp(long long v, long long n) { return v < 0 ? 0 : (v > n ? n : v); }
+NN_HD int nn_lo(int a, int b) { return a < b ? a : b; }
+NN_HD int nn_hi(int a, int b) { return a > b ? a : b; }
+
+// The scene s with start[s] <= i < start[s + 1] (values clamped to [0, n]), or -1.  At most 16 steps.
+NN_HD int nn_find_scene(const int* start, int nscene, long long n, long long i) {
+  if (i < nn_clamp(start[0], n)) return -1;
+  int lo = 0, hi = nscene;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (nn_clamp(start[mid], n) <= i) lo = mid;
+    else hi = mid;
+  }
+  return i < nn_clamp(start[lo + 1], n) ? lo : -1;
+}
+
+// THE distance of the header, in its order
+NN_HD float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
+  const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+// THE selection rule of the header
+NN_HD void nn_take(float d2, int j, float& best, int& bestj) {
+  if (d2 < best || (d2 == best && j < bestj)) best = d2, bestj = j;      // (bestj = -1 with best = +inf: an infinite d2 never wins)
+}
+
+// A scene's grid from its box: cubic cells of side h, n[a] cells along axis a.  ok is false for a scene without a finite target.
+struct SceneGrid {
+  float mn[3], mx[3], h, inv_h;
+  int n[3];
+  bool ok;
+};
+NN_HD SceneGrid nn_scene_grid(const unsigned* box, int g) {
+  SceneGrid G;
+  float ext[3], big = 0.f;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    G.mn[a] = nn_unkey(box[a]);
+    G.mx[a] = nn_unkey(~box[3 + a]);
+    ext[a] = fminf(fmaxf(G.mx[a] - G.mn[a], 0.f), 3e38f);      // (a NaN -- the empty box -- gives 0)
+    big = fmaxf(big, ext[a]);
+  }
+  G.ok = G.mn[0] <= G.mx[0] && G.mn[1] <= G.mx[1] && G.mn[2] <= G.mx[2];
+  G.h = fmaxf(big / (float)g, kHFloor);
+  G.inv_h = 1.0f / G.h;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) G.n[a] = (int)fminf(fmaxf(floorf(ext[a] * G.inv_h) + 1.f, 1.f), (float)g);      // clamped BEFORE the conversion
+  return G;
+}
+// position along axis a in cell units (not clamped), and the cell: clamped to [0, n - 1] before the conversion, a NaN to 0
+NN_HD float nn_units(const SceneGrid& G, int a, float x) { return (x - G.mn[a]) * G.inv_h; }
+NN_HD int nn_cell(const SceneGrid& G, int a, float u) { return (int)fminf(fmaxf(floorf(u), 0.f), (float)(G.n[a] - 1)); }
+NN_HD long long nn_cell_of(const SceneGrid& G, float x, float y, float z) {
+  const int cx = nn_cell(G, 0, nn_units(G, 0, x)), cy = nn_cell(G, 1, nn_units(G, 1, y)), cz = nn_cell(G, 2, nn_units(G, 2, z));
+  return ((long long)cz * G.n[1] + cy) * G.n[0] + cx;
+}
+
+// The records of the cells [ca, cb] of scene s (local ids, ca <= cb: consecutive cells own consecutive records) against the query.
+NN_HD void nn_visit(const NNArgs& a, long long scene_cell0, long long ca, long long cb, long long t0, long long t1, float qx, float qy, float qz,
+                    float& best, int& bestj) {
+  const long long first = scene_cell0 + ca, last = scene_cell0 + cb;
+  const long long begin = nn_clamp(first > 0 ? (long long)a.cells[first - 1] : 0ll, a.nt), end = nn_clamp((long long)a.cells[last], a.nt);
+  for (long long k = begin; k < end; ++k) {
+    const Rec r = a.sorted[k];
+    if (r.id >= t0 && r.id < t1) nn_take(nn_d2(qx, qy, qz, r.x, r.y, r.z), r.id, best, bestj);
+  }
+}
+
+// One query against the built grid.  Writes index[i] and dist2[i].
+NN_HD void nn_query_grid(const NNArgs& a, long long i) {
+  float best = INFINITY;
+  int bestj = -1;
+  const int s = nn_find_scene(a.qstart, a.nscene, a.nq, i);
+  if (s >= 0) {
+    const long long t0 = nn_clamp(a.tstart[s], a.nt), t1 = nn_clamp(a.tstart[s + 1], a.nt);
+    const SceneGrid G = nn_scene_grid(a.box + (size_t)s * 6, a.g);
+    if (G.ok && t0 < t1) {
+      const float q[3] = {a.query[i * 3 + 0], a.query[i * 3 + 1], a.query[i * 3 + 2]};
+      const long long cell0 = (long long)s * a.g * a.g * a.g;
+      float u[3], out2[3];
+      int c[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const float uk = nn_units(G, k, q[k]);
+        c[k] = nn_cell(G, k, uk);
+        u[k] = fminf(fmaxf(uk, -kUClamp), kUClamp);
+        // what the query lies outside the box along the axis: every target is inside it, exactly
+        const float o = fmaxf(fmaxf(G.mn[k] - q[k], q[k] - G.mx[k]), 0.f) * 0.999f;
+        out2[k] = o * o;
+      }
+      for (int r = 0; r < a.g; ++r) {      // (a host value bounds the loop whatever the data)
+        const int z0 = nn_hi(c[2] - r, 0), z1 = nn_lo(c[2] + r, G.n[2] - 1), y0 = nn_hi(c[1] - r, 0), y1 = nn_lo(c[1] + r, G.n[1] - 1);
+        const int xa = nn_hi(c[0] - r, 0), xb = nn_lo(c[0] + r, G.n[0] - 1);
+        for (int z = z0; z <= z1; ++z)
+          for (int y = y0; y <= y1; ++y) {
+            const long long row = ((long long)z * G.n[1] + y) * G.n[0];
+            if (z - c[2] == r || c[2] - z == r || y - c[1] == r || c[1] - y == r) {
+              nn_visit(a, cell0, row + xa, row + xb, t0, t1, q[0], q[1], q[2], best, bestj);      // a face of the shell: the whole row
+            } else {                                                                              // inside: the row's two ends
+              if (c[0] - r >= 0) nn_visit(a, cell0, row + c[0] - r, row + c[0] - r, t0, t1, q[0], q[1], q[2], best, bestj);
+              if (c[0] + r < G.n[0]) nn_visit(a, cell0, row + c[0] + r, row + c[0] + r, t0, t1, q[0], q[1], q[2], best, bestj);
+            }
+          }
+        // a lower bound of d2 to any point of an unvisited cell: such a cell lies beyond a face of the visited block along some axis
+        float bound = INFINITY;
+        bool left = false;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const float others = (out2[(k + 1) % 3] + out2[(k + 2) % 3]);
+          if (c[k] + r + 1 < G.n[k]) {      // cells >= c + r + 1: their points sit at >= c + r + 1 cell units
+            const float gap = fmaxf(((float)(c[k] + r + 1) - u[k]) - 0.001f, 0.f) * 0.999f * G.h;
+            bound = fminf(bound, gap * gap + others);
+            left = true;
+          }
+          if (c[k] - r > 0) {               // cells <= c - r - 1: their points sit below c - r cell units
+            const float gap = fmaxf((u[k] - (float)(c[k] - r)) - 0.001f, 0.f) * 0.999f * G.h;
+            bound = fminf(bound, gap * gap + others);
+            left = true;
+          }
+        }
+        if (!left || best < bound * 0.999f) break;
+      }
+    }
+  }
+  a.index[i] = bestj;
+  a.dist2[i] = best;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- kernels
+__global__ __launch_bounds__(kNNThreads) void brute_kernel(NNArgs a) {
+  __shared__ Rec tile[kTile];
+  __shared__ int span[2];
+  const long long i = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+  const bool live = i < a.nq;
+  const int s = live ? nn_find_scene(a.qstart, a.nscene, a.nq, i) : -1;
+  if (threadIdx.x == 0) span[0] = a.nscene, span[1] = -1;
+  __syncthreads();
+  if (s >= 0) atomicMin(&span[0], s), atomicMax(&span[1], s);
+  __syncthreads();
+  const int s_lo = span[0], s_hi = span[1];      // (uniform: the scenes this workgroup's queries belong to)
+  float qx = 0.f, qy = 0.f, qz = 0.f, best = INFINITY;
+  int bestj = -1;
+  if (live) qx = a.query[i * 3 + 0], qy = a.query[i * 3 + 1], qz = a.query[i * 3 + 2];
+  for (int sc = s_lo; sc <= s_hi; ++sc) {
+    const long long t0 = nn_clamp(a.tstart[sc], a.nt), t1 = nn_clamp(a.tstart[sc + 1], a.nt);
+    for (long long base = t0; base < t1; base += kTile) {
+      const int m = (int)min((long long)kTile, t1 - base);
+      __syncthreads();      // the previous tile has been read
+      for (int k = threadIdx.x; k < m; k += kNNThreads) {
+        const long long j = base + k;
+        tile[k] = Rec{a.target[j * 3 + 0], a.target[j * 3 + 1], a.target[j * 3 + 2], (int)j};
+      }
+      __syncthreads();
+      if (s == sc)
+        for (int k = 0; k < m; ++k) {
+          const Rec r = tile[k];
+          nn_take(nn_d2(qx, qy, qz, r.x, r.y, r.z), r.id, best, bestj);
+        }
+    }
+  }
+  if (live) a.index[i] = bestj, a.dist2[i] = best;
+}
+
+// keys only decrease: a stale read costs an unnecessary atomic, never a wrong result (fusion.hip: splat_kernel)
+__device__ __forceinline__ void key_min(unsigned* slot, unsigned key) {
+  if (*slot <= key) return;
+  atomicMin(slot, key);
+}
+
+// One thread per target.  A wavefront whose live lanes share one scene reduces its six keys across the lanes first.
+__global__ __launch_bounds__(kNNThreads) void box_kernel(NNArgs a) {
+  const long long j = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+  const int s = j < a.nt ? nn_find_scene(a.tstart, a.nscene, a.nt, j) : -1;
+  unsigned key[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};
+  bool in = false;
+  if (s >= 0) {
+    const float x = a.target[j * 3 + 0], y = a.target[j * 3 + 1], z = a.target[j * 3 + 2];
+    if (nn_finite(x) && nn_finite(y) && nn_finite(z)) {
+      in = true;
+      key[0] = nn_key(x), key[1] = nn_key(y), key[2] = nn_key(z);
+      key[3] = ~key[0], key[4] = ~key[1], key[5] = ~key[2];
+    }
+  }
+  const unsigned long long members = __ballot(in);
+  if (!members) return;      // (uniform)
+  const int s0 = __builtin_amdgcn_readlane(s, __builtin_amdgcn_readfirstlane(__ffsll((long long)members) - 1));
+  if (__ballot(in && s != s0) == 0ull) {      // (uniform) one scene: all-ones is the neutral key of the lanes that are out
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      unsigned v = key[k];
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) v = min(v, (unsigned)__shfl_xor((int)v, o, 64));
+      key[k] = v;
+    }
+    if ((threadIdx.x & 63) == 0)
+      for (int k = 0; k < 6; ++k) key_min(a.box + (size_t)s0 * 6 + k, key[k]);
+  } else if (in) {
+    for (int k = 0; k < 6; ++k) key_min(a.box + (size_t)s * 6 + k, key[k]);
+  }
+}
+
+// One thread per target: count (scatter = 0) or place (scatter = 1) it in its cell.  A target with a non-finite coordinate is in no cell.
+template <int SCATTER>
+__global__ __launch_bounds__(kNNThreads) void cell_kernel(NNArgs a) {
+  const long long j = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+  if (j >= a.nt) return;
+  const int s = nn_find_scene(a.tstart, a.nscene, a.nt, j);
+  if (s < 0) return;
+  const float x = a.target[j * 3 + 0], y = a.target[j * 3 + 1], z = a.target[j * 3 + 2];
+  if (!(nn_finite(x) && nn_finite(y) && nn_finite(z))) return;
+  const SceneGrid G = nn_scene_grid(a.box + (size_t)s * 6, a.g);
+  if (!G.ok) return;
+  unsigned* cell = a.cells + (long long)s * a.g * a.g * a.g + nn_cell_of(G, x, y, z);      // (n[a] <= g: inside the scene's g^3 words)
+  const unsigned at = atomicAdd(cell, 1u);
+  if (SCATTER && (long long)at < a.nt) a.sorted[at] = Rec{x, y, z, (int)j};
+}
+
+// The two chunk levels of the scan around scan_kernel.  The cell array is padded to whole chunks (and zeroed): no bounds in here.
+__global__ __launch_bounds__(kNNThreads) void chunk_sum_kernel(const unsigned* __restrict__ cells, unsigned* __restrict__ blocks) {
+  __shared__ unsigned wave_n[kNNThreads / 64];
+  const uint4* p = (const uint4*)(cells + (size_t)blockIdx.x * kChunk + threadIdx.x * 16);
+  unsigned v = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint4 w = p[k];
+    v += (w.x + w.y) + (w.z + w.w);
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor((int)v, o, 64);
+  if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) blocks[blockIdx.x] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+}
+
+__global__ __launch_bounds__(kNNThreads) void chunk_scan_kernel(unsigned* __restrict__ cells, const unsigned* __restrict__ blocks) {
+  __shared__ unsigned wave_n[kNNThreads / 64];
+  uint4* p = (uint4*)(cells + (size_t)blockIdx.x * kChunk + threadIdx.x * 16);
+  unsigned w[16], mine = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint4 t = p[k];
+    w[k * 4 + 0] = t.x, w[k * 4 + 1] = t.y, w[k * 4 + 2] = t.z, w[k * 4 + 3] = t.w;
+  }
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {      // exclusive within the thread
+    const unsigned t = w[k];
+    w[k] = mine;
+    mine += t;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) wave_n[wave] = incl;
+  __syncthreads();
+  unsigned before = blocks[blockIdx.x] + incl - mine;
+  for (int k = 0; k < wave; ++k) before += wave_n[k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) p[k] = make_uint4(w[k * 4 + 0] + before, w[k * 4 + 1] + before, w[k * 4 + 2] + before, w[k * 4 + 3] + before);
+}
+
+__global__ __launch_bounds__(kNNThreads) void grid_query_kernel(NNArgs a) {
+  const long long i = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+  if (i < a.nq) nn_query_grid(a, i);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host
+struct NNPlan {
+  int method, g;              // resolved: MVD_NN_BRUTE or MVD_NN_GRID; cells per axis
+  size_t ncell, chunks;       // nscene * g^3, and the kChunk-word chunks that hold them
+  size_t off_box, off_cells, off_blocks, bytes;
+};
+
+static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// false: an argument is out of range (the caller says which)
+static bool nn_plan(size_t nt, int nscene, int method, int grid, NNPlan& p) {
+  p = NNPlan{};
+  if (nscene < 1 || nscene > 65535 || nt > 0x7fffffffull || method < MVD_NN_AUTO || method > MVD_NN_GRID || grid < 0 || grid > kMaxGrid) return false;
+  const size_t per = nt / (size_t)nscene;
+  p.method = method == MVD_NN_AUTO ? ((long long)per >= kGridMinTargets ? MVD_NN_GRID : MVD_NN_BRUTE) : method;
+  if (nt == 0) p.method = MVD_NN_BRUTE;
+  if (p.method == MVD_NN_BRUTE) return true;
+  int g = grid;
+  if (g == 0) {
+    g = (int)fminf(fmaxf(floorf(sqrtf((float)per / kGridDivisor) + 0.5f), 1.f), (float)kMaxGrid);
+    while (g > 1 && (unsigned long long)nscene * g * g * g > (1ull << 28)) --g;
+  }
+  if ((unsigned long long)nscene * g * g * g > 0x7fffffffull) return false;
+  p.g = g;
+  p.ncell = (size_t)nscene * g * g * g;
+  p.chunks = (p.ncell + kChunk - 1) / kChunk;
+  p.off_box = up16(nt * sizeof(Rec));
+  p.off_cells = p.off_box + up16((size_t)nscene * 6 * sizeof(unsigned));
+  p.off_blocks = p.off_cells + p.chunks * kChunk * sizeof(unsigned);
+  p.bytes = p.off_blocks + up16((p.chunks + 1) * sizeof(unsigned));
+  return true;
+}
+
+}  // namespace
+
+extern "C" size_t mvd_nearest_points_scratch(size_t nt, int nscene, int method, int grid) {
+  NNPlan p;
+  return nn_plan(nt, nscene, method, grid, p) ? p.bytes : 0;
+}
+
+extern "C" int mvd_nearest_points_stages(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,
+                                         size_t nt, int nscene, int method, int grid, int* index, float* dist2, void* scratch,
+                                         size_t scratch_bytes, int stages, mvd_stream_t stream) {
+  const char* fn = stages == MVD_NN_ALL ? "mvd_nearest_points" : "mvd_nearest_points_stages";
+  MVD_CHECK_ARG(stages >= 1 && stages <= MVD_NN_ALL, "%s: stages=%d outside [1, %d]", fn, stages, MVD_NN_ALL);
+  MVD_CHECK_ARG(method >= MVD_NN_AUTO && method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, method);
+  MVD_CHECK_ARG(grid >= 0 && grid <= kMaxGrid, "%s: grid=%d outside [0, %d]", fn, grid, kMaxGrid);
+  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
+  MVD_CHECK_ARG(nq <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: nq=%zu, nt=%zu beyond 2^31 - 1", fn, nq, nt);
+  MVD_CHECK_ARG(query_start && target_start, "%s: null query_start or target_start", fn);
+  MVD_CHECK_ARG((query && index && dist2) || nq == 0, "%s: null query, index or dist2 with nq=%zu", fn, nq);
+  MVD_CHECK_ARG(target || nt == 0, "%s: null target with nt=%zu", fn, nt);
+  NNPlan p;
+  MVD_CHECK_ARG(nn_plan(nt, nscene, method, grid, p), "%s: nscene * grid^3 cells beyond 2^31 - 1 (nscene=%d, grid=%d)", fn, nscene, grid);
+  MVD_CHECK_ARG(p.bytes == 0 || (scratch && scratch_bytes >= p.bytes && ((uintptr_t)scratch & 15) == 0),
+                "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn, scratch_bytes, p.bytes);
+  char* base = (char*)scratch;
+  NNArgs a{query, target, query_start, target_start, index, dist2, nullptr, nullptr, nullptr, nullptr, (long long)nq, (long long)nt, nscene, p.g};
+  const hipStream_t st = (hipStream_t)stream;
+  if (p.method == MVD_NN_GRID) {
+    a.sorted = (Rec*)base;
+    a.box = (unsigned*)(base + p.off_box);
+    a.cells = (unsigned*)(base + p.off_cells);
+    a.blocks = (unsigned*)(base + p.off_blocks);
+    if (stages & MVD_NN_BUILD) {
+      hipError_t e = hipMemsetAsync(a.box, 0xff, (size_t)nscene * 6 * sizeof(unsigned), st);
+      if (e == hipSuccess) e = hipMemsetAsync(a.cells, 0, p.chunks * kChunk * sizeof(unsigned), st);
+      MVD_CHECK_ARG(e == hipSuccess, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+      const dim3 per_target(cdiv((long)nt, kNNThreads)), threads(kNNThreads);
+      hipLaunchKernelGGL(box_kernel, per_target, threads, 0, st, a);
+      hipLaunchKernelGGL(cell_kernel<0>, per_target, threads, 0, st, a);
+      hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)p.chunks), threads, 0, st, a.cells, a.blocks);
+      hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kCompactThreads), 0, st, a.blocks, (unsigned)p.chunks, a.blocks + p.chunks);
+      hipLaunchKernelGGL(chunk_scan_kernel, dim3((unsigned)p.chunks), threads, 0, st, a.cells, a.blocks);
+      hipLaunchKernelGGL(cell_kernel<1>, per_target, threads, 0, st, a);
+    }
+    if ((stages & MVD_NN_QUERY) && nq > 0) hipLaunchKernelGGL(grid_query_kernel, dim3(cdiv((long)nq, kNNThreads)), dim3(kNNThreads), 0, st, a);
+  } else if ((stages & MVD_NN_QUERY) && nq > 0) {
+    hipLaunchKernelGGL(brute_kernel, dim3(cdiv((long)nq, kNNThreads)), dim3(kNNThreads), 0, st, a);
+  }
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
+extern "C" int mvd_nearest_points(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,
+                                  size_t nt, int nscene, int method, int grid, int* index, float* dist2, void* scratch, size_t scratch_bytes,
+                                  mvd_stream_t stream) {
+  return mvd_nearest_points_stages(query, query_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, scratch, scratch_bytes,
+                                   MVD_NN_ALL, stream);
+}

@@ -17,6 +17,12 @@ mesh too.  The only host synchronisation is the read of the vertex and face coun
 ``render_mesh`` brings a mesh back into images (include/mvd_hip.h: mvd_render_mesh): a triangle rasteriser with the point renderer's 64-bit
 z-buffer -- a hole-free novel view, the depth map the surface implies for a camera, perspective-correct barycentrics, face normals and
 the map of which face each pixel shows.  ``ViewFusion.render_mesh`` binds the model's depth map.  It synchronises nothing.
+
+``nearest_points`` measures that geometry (include/mvd_hip.h: mvd_nearest_points): the exact nearest point of one cloud for every point
+of another, by brute force or through a uniform grid, the same bits either way.  ``compare_geometry`` reduces the two directions to
+accuracy, completeness, Chamfer distance and precision / recall / F-score per scene, and ``sample_mesh`` turns a mesh into the
+deterministic surface samples both take.  ``nearest_points`` synchronises nothing; ``compare_geometry`` reads the scene offsets once.
+Nothing of the model is bound here, so there is no ``ViewFusion`` method.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -556,6 +562,248 @@ def render_mesh(mesh, cameras, size=256, cull=True, background=(1.0, 1.0, 1.0), 
     face = face.reshape(*lead, P, P)
     return RenderedMesh(rgb=None if rgb is None else rgb.reshape(*lead, 3, P, P), depth=depth.reshape(*lead, P, P), face=face,
                         bary=bary.reshape(*lead, 3, P, P), normal=normal.reshape(*lead, 3, P, P), hit=face >= 0)
+
+
+@dataclass
+class NearestPoints:
+    """What ``nearest_points`` returns, per query point."""
+    index: torch.Tensor                      # (nq,) int32: the row of the nearest target, or -1 without one
+    dist2: torch.Tensor                      # (nq,) fp32: the squared distance to it, or +inf
+
+    @property
+    def dist(self):
+        return torch.sqrt(self.dist2)
+
+    @property
+    def hit(self):
+        return self.index >= 0
+
+
+@dataclass
+class SurfaceSamples:
+    """What ``sample_mesh`` returns: points on a mesh's surface, scene after scene; every field is a tensor on the mesh's device."""
+    xyz: torch.Tensor                        # (n, 3) fp32 world coordinates
+    rgb: Optional[torch.Tensor]              # (n, 3) fp32: the vertex colours mixed like xyz, or None without colour
+    scene: torch.Tensor                      # (n,) int64, sorted
+    face: torch.Tensor                       # (n,) int32: the row of mesh.faces the sample lies in
+    bary: torch.Tensor                       # (n, 3) fp32: its barycentrics on that face's three vertices
+
+    def __len__(self):
+        return int(self.xyz.shape[0])
+
+
+NN_METHODS = {"auto": hip.NN_AUTO, "brute": hip.NN_BRUTE, "grid": hip.NN_GRID}
+COMPARE_SAMPLES = 65536                      # compare_geometry's default samples per scene of a mesh
+_R2 = 1.32471795724474602596                 # the plastic constant: x^3 = x + 1
+
+
+def sample_mesh(mesh, n):
+    """``n`` points per scene on the surface of a TriangleMesh, by area and deterministically (no random numbers) -> SurfaceSamples.
+
+    Sample k of a scene falls in the face whose interval of the scene's cumulative face area contains (k + 0.5) / n of the scene's
+    area: a face of area a gets n a / A samples to within one.  Inside the face it sits at the k-th point of the R2 sequence (Roberts'
+    additive recurrence on the plastic constant g: (0.5 + k / g, 0.5 + k / g^2) mod 1, formed in float64), folded into the triangle
+    ((r1, r2) -> (1 - r1, 1 - r2) where r1 + r2 > 1) and read as the barycentrics (1 - r1 - r2, r1, r2) of the face's vertices.  xyz and
+    rgb are that mix of the vertices and vertex colours.  Areas and the cumulative sum are float64; plain torch ops on the mesh's device
+    (CPU tensors too).  A scene without faces, or whose area is zero or not finite, contributes no samples."""
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a TriangleMesh")
+    if isinstance(n, bool) or int(n) != n or not 1 <= n <= 2 ** 31 - 1:
+        raise ValueError(f"n = {n}: an integer in [1, 2^31 - 1]")
+    n = int(n)
+    vertices, faces = mesh.vertices, mesh.faces
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh: vertices of shape {tuple(vertices.shape)}, faces of shape {tuple(faces.shape)}, need (n, 3) and (m, 3)")
+    if mesh.rgb is not None and tuple(mesh.rgb.shape) != tuple(vertices.shape):
+        raise ValueError(f"mesh: rgb of shape {tuple(mesh.rgb.shape)} for {vertices.shape[0]} vertices")
+    dev = vertices.device
+    start = [int(v) for v in mesh.face_start.tolist()]
+    if len(start) < 2 or start[0] < 0 or start[-1] > faces.shape[0] or any(a > b for a, b in zip(start, start[1:])):
+        raise ValueError(f"mesh: face_start = {start} for {faces.shape[0]} faces")
+    v64, f = vertices.double(), faces.long()
+    tri = v64[f]                                                                         # (m, 3 vertices, 3)
+    area = 0.5 * torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]).norm(dim=1)
+    k = torch.arange(n, dtype=torch.float64, device=dev)
+    r1, r2 = torch.remainder(0.5 + k / _R2, 1.0), torch.remainder(0.5 + k / (_R2 * _R2), 1.0)
+    fold = r1 + r2 > 1.0
+    r1, r2 = torch.where(fold, 1.0 - r1, r1), torch.where(fold, 1.0 - r2, r2)
+    b12 = torch.stack([r1, r2], dim=1).float()
+    b0 = (1.0 - b12[:, 0].double() - b12[:, 1].double()).clamp(min=0.0).float()
+    bary1 = torch.cat([b0[:, None], b12], dim=1)                                         # (n, 3): the same for every scene
+    face, scene = [], []
+    for s_, (f0, f1) in enumerate(zip(start, start[1:])):
+        if f1 == f0:
+            continue
+        cs = torch.cumsum(area[f0:f1], dim=0)
+        total = float(cs[-1])
+        if not 0.0 < total < float("inf"):
+            continue
+        at = torch.searchsorted(cs, (k + 0.5) / n * cs[-1], right=True).clamp(max=f1 - f0 - 1)
+        face.append(at + f0)
+        scene.append(torch.full((n,), s_, dtype=torch.int64, device=dev))
+    if face:
+        face, scene = torch.cat(face), torch.cat(scene)
+    else:
+        face, scene = torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+    bary = bary1.repeat(face.shape[0] // n, 1)
+    mix = lambda values: (bary.double()[:, :, None] * values.double()[f[face]]).sum(1).float()
+    return SurfaceSamples(xyz=mix(vertices), rgb=None if mesh.rgb is None else mix(mesh.rgb.to(dev)), scene=scene, face=face.to(torch.int32),
+                          bary=bary)
+
+
+def _nearest(query, query_start, target, target_start, N, method, grid):
+    """The enqueues of mvd_nearest_points.  query (nq, 3), target (nt, 3) fp32, query_start / target_start (N + 1) int32, all contiguous
+    on one GPU.  Returns (index (nq,) int32, dist2 (nq,) fp32).  No host synchronisation."""
+    L = hip.lib()
+    dev, nq, nt = query.device, int(query.shape[0]), int(target.shape[0])
+    hip._req(query), hip._req(target), hip._req(query_start, torch.int32), hip._req(target_start, torch.int32)
+    index = torch.empty(nq, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
+    nbytes = int(L.mvd_nearest_points_scratch(nt, N, method, grid))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_nearest_points(p(query), hip.ptr(query_start), p(target), hip.ptr(target_start), nq, nt, N, method, grid, p(index),
+                                   p(dist2), p(scratch), nbytes, hip.stream()))
+    return index, dist2
+
+
+def _points_of(side, name, scenes):
+    """(xyz (n, 3), sorted scene ids (n,) or None for one scene) of an argument of ``nearest_points``, checked."""
+    if isinstance(side, TriangleMesh):
+        raise ValueError(f"{name}: a TriangleMesh has no points to search -- pass sample_mesh(mesh, n)")
+    if torch.is_tensor(side):
+        xyz, scene = side, None
+    elif hasattr(side, "xyz") and hasattr(side, "scene"):
+        xyz, scene = side.xyz, side.scene
+    else:
+        raise ValueError(f"{name} must be an (n, 3) tensor, a PointCloud or SurfaceSamples")
+    if not torch.is_tensor(xyz) or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"{name}: xyz of shape {tuple(xyz.shape) if torch.is_tensor(xyz) else None}, need (n, 3)")
+    n = int(xyz.shape[0])
+    if n > 2 ** 31 - 1:
+        raise ValueError(f"{name}: {n} points, the point index is 31 bits")
+    if scene is not None and tuple(scene.shape) != (n,):
+        raise ValueError(f"{name}: scene of shape {tuple(scene.shape)} for {n} points")
+    if scene is not None and n and scene.device.type == "cpu" and not 0 <= int(scene.min()) <= int(scene.max()) < scenes:
+        raise ValueError(f"{name}: scenes {int(scene.min())} .. {int(scene.max())} with scenes = {scenes}")
+    return xyz, scene
+
+
+def _scene_start(scene, n, N, dev):
+    """(N + 1,) int32 offsets of sorted scene ids, formed on the device (``render_points`` does the same); one scene without ids."""
+    if scene is None or n == 0:
+        return torch.tensor([0] + [n] * N, dtype=torch.int32).to(dev)
+    bounds = torch.arange(N + 1, dtype=scene.dtype, device=scene.device)
+    return torch.searchsorted(scene.contiguous(), bounds).to(dev, torch.int32)
+
+
+def _check_nn(scenes, method, grid):
+    if isinstance(scenes, bool) or int(scenes) != scenes or not 1 <= scenes <= 65535:
+        raise ValueError(f"scenes = {scenes}: an integer in [1, 65535]")
+    if method not in NN_METHODS:
+        raise ValueError(f"method = {method!r}: one of {sorted(NN_METHODS)}")
+    if grid is not None and (isinstance(grid, bool) or int(grid) != grid or not 1 <= grid <= hip.NN_MAX_GRID):
+        raise ValueError(f"grid = {grid}: None or an integer in [1, {hip.NN_MAX_GRID}]")
+    return int(scenes), NN_METHODS[method], 0 if grid is None else int(grid)
+
+
+def nearest_points(query, target, scenes=1, method="auto", grid=None):
+    """For every point of ``query`` the exact nearest point of ``target`` (include/mvd_hip.h: mvd_nearest_points has the rule)
+    -> NearestPoints.
+
+    query, target : an (n, 3) tensor (one scene, scene 0), or anything with ``.xyz`` and a sorted ``.scene`` -- a PointCloud, or the
+              SurfaceSamples of ``sample_mesh``.  A point searches the target points of its own scene only.  A TriangleMesh is refused.
+    scenes  : N, the number of scenes both sides are split into (scene ids < N).
+    method  : "brute" (every pair), "grid" (a uniform grid over the targets of each scene) or "auto" (the library chooses from the
+              sizes).  All three return the same bits: the minimum squared distance in fp32, between equal minima the lowest row.
+    grid    : cells per axis for "grid", 1 .. hip.NN_MAX_GRID; None leaves it to the library.
+    ``index`` is a row of ``target`` (-1, with ``dist2`` = +inf, for a query without a candidate: no target in its scene, or a
+    non-finite coordinate).  Nothing is read back from the device, so scene ids < N are checked only for ids in host memory; on the
+    GPU a point of a scene >= N finds nothing and is found by nothing."""
+    N, method, grid = _check_nn(scenes, method, grid)
+    q, q_scene = _points_of(query, "query", N)
+    t, t_scene = _points_of(target, "target", N)
+    dev = q.device
+    q, t = q.float().contiguous(), t.to(dev, torch.float32).contiguous()
+    index, dist2 = _nearest(q, _scene_start(q_scene, int(q.shape[0]), N, dev), t, _scene_start(t_scene, int(t.shape[0]), N, dev), N, method, grid)
+    return NearestPoints(index=index, dist2=dist2)
+
+
+@dataclass
+class GeometryDistance:
+    """What ``compare_geometry`` returns.  The metrics are (N,) float64 tensors, one value per scene, NaN for a scene with an empty side."""
+    a_to_b: NearestPoints                    # for every point of a its nearest point of b
+    b_to_a: NearestPoints
+    accuracy: torch.Tensor                   # mean distance from a to b
+    completeness: torch.Tensor               # mean distance from b to a
+    chamfer: torch.Tensor                    # accuracy + completeness
+    chamfer_sq: torch.Tensor                 # mean squared distance a to b + mean squared distance b to a
+    precision: torch.Tensor                  # the share of a within `threshold` of b
+    recall: torch.Tensor                     # the share of b within `threshold` of a
+    fscore: torch.Tensor                     # 2 P R / (P + R), 0 when P + R == 0
+
+
+def geometry_metrics(a_dist2, a_scene, b_dist2, b_scene, scenes, threshold):
+    """The arithmetic of ``compare_geometry``: squared nearest distances of the two directions with their sorted scene ids (None: all
+    scene 0) -> dict of the seven (N,) float64 metrics of GeometryDistance.  Every scene is reduced on its own slice by torch.sum --
+    no float atomics, no index_add_: the same bits run to run.  One host read, of the scene offsets."""
+    N = int(scenes)
+    dev = a_dist2.device
+    starts = torch.stack([_scene_start(a_scene, int(a_dist2.shape[0]), N, dev), _scene_start(b_scene, int(b_dist2.shape[0]), N, dev)]).tolist()
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    rows = {k: [] for k in ("accuracy", "completeness", "chamfer_sq", "precision", "recall")}
+    for s in range(N):
+        sides = []
+        for d2, st in ((a_dist2, starts[0]), (b_dist2, starts[1])):
+            part = d2[st[s]:st[s + 1]].double()
+            sides.append((part, part.sqrt(), max(st[s + 1] - st[s], 0)))
+        if min(c for _, _, c in sides) == 0:
+            for k in rows:
+                rows[k].append(nan)
+            continue
+        (a2, a1, na), (b2, b1, nb) = sides
+        rows["accuracy"].append(a1.sum() / na)
+        rows["completeness"].append(b1.sum() / nb)
+        rows["chamfer_sq"].append(a2.sum() / na + b2.sum() / nb)
+        rows["precision"].append((a1 <= threshold).sum().double() / na)
+        rows["recall"].append((b1 <= threshold).sum().double() / nb)
+    out = {k: torch.stack(v) for k, v in rows.items()}
+    out["chamfer"] = out["accuracy"] + out["completeness"]
+    pr = out["precision"] + out["recall"]
+    out["fscore"] = torch.where(pr == 0, torch.zeros_like(pr), 2.0 * out["precision"] * out["recall"] / pr)
+    return out
+
+
+def compare_geometry(a, b, threshold=0.02, scenes=1, samples=None, method="auto"):
+    """Distances between two geometries, scene by scene -> GeometryDistance: accuracy (mean distance from a to b), completeness (from
+    b to a), their sum the Chamfer distance, its squared form, and precision / recall / F-score at ``threshold``.  With a the
+    reconstruction and b the ground truth these are the usual names; any two clouds, rigs or settings can be compared.
+
+    a, b    : what ``nearest_points`` takes, or a TriangleMesh, which is first turned into ``sample_mesh(mesh, samples)``;
+              ``samples`` defaults to COMPARE_SAMPLES = 65536 per scene.
+    threshold : in world units, the distance up to which a point counts as matched.  An INTERFACE default: no trained checkpoint was
+              available when this was written, so nobody has tuned it on real samples -- expect to.
+    scenes, method : as for ``nearest_points``.
+    The only host synchronisation is the read of the scene offsets (and, for a mesh, the per-scene areas in ``sample_mesh``)."""
+    N, _, _ = _check_nn(scenes, method, None)
+    threshold = float(threshold)
+    if not threshold >= 0:
+        raise ValueError(f"threshold = {threshold}: >= 0")
+    if samples is not None and (isinstance(samples, bool) or int(samples) != samples or samples < 1):
+        raise ValueError(f"samples = {samples}: None or an integer >= 1")
+    sides = []
+    for name, side in (("a", a), ("b", b)):
+        if isinstance(side, TriangleMesh):
+            if int(side.face_start.numel()) - 1 > N:
+                raise ValueError(f"{name}: a mesh of {int(side.face_start.numel()) - 1} scenes with scenes = {N}")
+            side = sample_mesh(side, COMPARE_SAMPLES if samples is None else int(samples))
+        _points_of(side, name, N)
+        sides.append(side)
+    ab = nearest_points(sides[0], sides[1], scenes=N, method=method)
+    ba = nearest_points(sides[1], sides[0], scenes=N, method=method)
+    scene_of = lambda side: None if torch.is_tensor(side) else side.scene
+    m = geometry_metrics(ab.dist2, scene_of(sides[0]), ba.dist2, scene_of(sides[1]), N, threshold)
+    return GeometryDistance(a_to_b=ab, b_to_a=ba, **m)
 
 
 def write_ply(path, cloud):

@@ -51,6 +51,9 @@ FUSE_FOREGROUND = 1                                        # flags byte of mvd_f
 FUSE_STAGE_AUTO, FUSE_STAGE_GLOBAL, FUSE_STAGE_LDS = 0, 1, 2
 SPLAT_MAX_RADIUS = 4                                       # MVD_SPLAT_MAX_RADIUS: the largest footprint radius of mvd_render_points
 RENDER_FILL, RENDER_SPLAT, RENDER_RESOLVE, RENDER_ALL = 1, 2, 4, 7      # stages of mvd_render_points_stages and mvd_render_mesh_stages
+NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2                       # method of mvd_nearest_points
+NN_BUILD, NN_QUERY, NN_ALL = 1, 2, 3                       # stages of mvd_nearest_points_stages
+NN_MAX_GRID = 256                                          # the largest `grid` of mvd_nearest_points
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -167,6 +170,9 @@ SIGNATURES = {
     "mvd_render_mesh_scratch": (_sz, [_i, _i]),
     "mvd_render_mesh": (_i, [_vp] * 6 + [_sz, _sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f)] + [_vp] * 6 + [_sz, _vp]),
     "mvd_render_mesh_stages": (_i, [_vp] * 6 + [_sz, _sz, _i, _i, _i, _i, _f, _f, C.POINTER(_f)] + [_vp] * 6 + [_sz, _i, _vp]),
+    "mvd_nearest_points_scratch": (_sz, [_sz, _i, _i, _i]),
+    "mvd_nearest_points": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_nearest_points_stages": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]),
     "mvd_tsdf_integrate": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _vp]),
     "mvd_mesh_scratch": (_sz, [_i, _i]),
     "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
