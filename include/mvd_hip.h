@@ -718,6 +718,73 @@ int mvd_nearest_points_stages(const float* query, const int* query_start, const 
                               int stages, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Aligning geometry: a similarity transform per scene that takes a source cloud onto a target -- the closed form for given pairs, and
+ * point-to-point ICP around the search above (csrc/align.hip; host: mvdfusion_amd/fusion.py fit_similarity, align_geometry,
+ * Alignment.apply).  Not in the reference either.  A distance between two geometries means something only in one frame.
+ *
+ * Scenes are those of mvd_nearest_points: nscene + 1 int32 DEVICE offsets, clamped to [0, n] before they index anything.
+ * Transform : per scene 12 doubles m[3][4], row-major, m[r][0..2] = s R[r], m[r][3] = t[r]; (nscene, 12) on the device.
+ * Apply     : moved[r] = (float)(((m[r][0] * (double)x + m[r][1] * (double)y) + m[r][2] * (double)z) + m[r][3]) in fp64, in this order,
+ *             every operation rounded once (compiled without contraction), one rounding to fp32 at the end.  A point of no scene is
+ *             copied unchanged.  ICP applies the accumulated transform to the ORIGINAL source every time, never transform on transform.
+ * Pairs     : source row i goes with target row j = index[i], or j = i with index == NULL; no pair unless 0 <= j < nt.  Its d2 is
+ *             dist2[i], or with dist2 == NULL the distance of mvd_nearest_points ((dx * dx + dy * dy) + dz * dz in fp32) between the
+ *             moved point p and the target q.  The pair is ACCEPTED when d2 < +inf and d2 <= max_dist2, compared in fp32 (a NaN is
+ *             not accepted; max_dist2 = +inf is no gate).  An accepted pair has finite p and q.
+ * Sums      : per scene, over the accepted pairs of its rows, MVD_ALIGN_SUMS = 19 doubles: [0] the count, [1..3] sum p, [4..6] sum q,
+ *             [7 + 3 a + b] sum p_a q_b, [16] sum (px px + py py) + pz pz, [17] the same of q, [18] sum (double)d2.  Every product of
+ *             two fp32 values is exact in fp64; only the additions round.  A scene is cut into chunks of MVD_ALIGN_CHUNK consecutive
+ *             rows counted from the scene's own first row; one workgroup reduces a chunk in a fixed order (thread t its rows
+ *             t, t + 256, ...; the lanes of a wavefront in an xor butterfly; the four wavefronts as (w0 + w1) + (w2 + w3)) and the
+ *             chunk sums are added per scene in ascending chunk order.  No float atomics: the same bits run to run, and for a scene
+ *             alone and inside a batch.  The workgroup-to-(scene, chunk) map is a device prefix of ceil(len_s / chunk); the launch is
+ *             sized by the host bound ceil(n / chunk) + nscene.
+ *             The moments are raw, not centred in a first pass: their cancellation costs a relative (1 + |mu|^2 / sigma^2) n 2^-53
+ *             (mu, sigma^2: mean and variance of the points) -- nothing for objects in the +-0.75 box.
+ * Solve     : with n = sums[0], M = sum pq / n - (sum p / n)(sum q / n)^T and var = sum |p|^2 / n - |sum p / n|^2: Horn's symmetric
+ *             4 x 4 matrix of M, its dominant eigenvector by cyclic Jacobi in fp64 (a fixed number of sweeps; a rotation is skipped
+ *             where the off-diagonal is 0; tan = 1 / (|theta| + sqrt(theta^2 + 1)), and 1 / (2 |theta|) beyond |theta| = 1e150 where
+ *             the square would overflow), normalised to a unit quaternion, R formed from it -- a proper rotation whatever the data.
+ *             s = sum_ab R_ba M_ab / var with MVD_ALIGN_SCALE, else exactly 1;  t = sum q / n - s R sum p / n.  The step D = [s R | t]
+ *             composes as m <- D m in fp64.  D is the identity (s = 1) when fewer than 3 pairs were accepted, when var is not
+ *             positive, when a sum or a result is not finite, or when MVD_ALIGN_SCALE finds s <= 0.
+ * History   : a row is MVD_ALIGN_HISTORY = 3 doubles per scene: rms = sqrt(sums[18] / n) (NaN with n = 0), n, and the scale so far: the s
+ *             of the step (1 without one) times that entry of the row before -- one product per row, in row order, exactly 1 while no
+ *             step fits a scale.
+ *
+ * mvd_align_apply: out (n, 3) = src (n, 3) under transform.  n = 0 is valid.
+ * mvd_align_fit  : sums, solve and composition for given pairs: moved (n, 3), start its scene offsets, target (nt, 3), index / dist2
+ *             (n,) or NULL as above.  flags: MVD_ALIGN_SCALE; MVD_ALIGN_NO_STEP writes history_row only and leaves transform alone.
+ *             history_row (nscene, 3) describes the pairs as given, before the step.  transform is read and written.
+ *             scratch: mvd_align_scratch(n, 0, nscene, MVD_NN_BRUTE, 0) bytes, 16-byte aligned.
+ * mvd_align_icp  : MVD_NN_BUILD once over target; then iters times { apply transform to source -> moved; MVD_NN_QUERY of moved through
+ *             mvd_nearest_points_stages -> index, dist2 (so the correspondences are mvd_nearest_points' bits); fit; history row k };
+ *             then a last apply, query and history row (iters) without a step.  transform holds the start on entry and the result on
+ *             return; moved, index, dist2 are left as that last pass wrote them; history is (iters + 1, nscene, 3).
+ *             0 <= iters <= MVD_ALIGN_MAX_ITERS, a fixed count: nothing is read back, there is no early exit.  method, grid: those
+ *             of mvd_nearest_points.  scratch: mvd_align_scratch(nq, nt, nscene, method, grid) bytes (0 for an argument out of range).
+ * mvd_align_solve: the solve alone, on the host, the same function the kernel calls: sums[19] -> step[12], *scale.  Needs no GPU.
+ * Everything else is enqueued on the caller's stream with no host synchronisation and no allocation; every argument is checked before
+ * anything is enqueued, a refused call writes nothing (a failed ENQUEUE inside mvd_align_icp's loop ends the call there, with what the
+ * earlier iterations wrote).  Every word of the scratch that is read is written earlier in the same call. */
+#define MVD_ALIGN_SCALE 1
+#define MVD_ALIGN_NO_STEP 2
+#define MVD_ALIGN_CHUNK 1024
+#define MVD_ALIGN_SUMS 19
+#define MVD_ALIGN_HISTORY 3
+#define MVD_ALIGN_MAX_ITERS 1024
+size_t mvd_align_scratch(size_t nq, size_t nt, int nscene, int method, int grid);
+int mvd_align_solve(const double* sums, int flags, double* step, double* scale);
+int mvd_align_apply(const float* src, const int* src_start, size_t n, int nscene, const double* transform, float* out,
+                    mvd_stream_t stream);
+int mvd_align_fit(const float* moved, const int* start, const float* target, const int* index, const float* dist2, size_t n, size_t nt,
+                  int nscene, int flags, float max_dist2, double* transform, double* history_row, void* scratch, size_t scratch_bytes,
+                  mvd_stream_t stream);
+int mvd_align_icp(const float* source, const int* source_start, const float* target, const int* target_start, size_t nq, size_t nt,
+                  int nscene, int method, int grid, int iters, int flags, float max_dist2, double* transform, double* history,
+                  float* moved, int* index, float* dist2, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Volumetric fusion: the sampled RGB-D views integrated into a truncated signed distance volume (TSDF), and a watertight indexed triangle
  * mesh with vertex colours extracted from it by marching tetrahedra (csrc/tsdf.hip, csrc/tsdf_mesh.hpp; host: mvdfusion_amd/fusion.py
  * integrate_tsdf, extract_mesh).  Not in the reference either.  Cameras, projection, depth map and depth lookup are those of the point

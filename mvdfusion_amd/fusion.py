@@ -23,6 +23,12 @@ of another, by brute force or through a uniform grid, the same bits either way. 
 accuracy, completeness, Chamfer distance and precision / recall / F-score per scene, and ``sample_mesh`` turns a mesh into the
 deterministic surface samples both take.  ``nearest_points`` synchronises nothing; ``compare_geometry`` reads the scene offsets once.
 Nothing of the model is bound here, so there is no ``ViewFusion`` method.
+
+``align_geometry`` puts two geometries into one frame first (include/mvd_hip.h: mvd_align_icp): point-to-point ICP on that search, the
+target's grid built once, every iteration an apply, a query, a deterministic reduction of the matched pairs to moment sums and a
+closed-form similarity solve, all enqueued without a host synchronisation.  ``fit_similarity`` is the closed form alone for known
+pairs; both return an ``Alignment`` whose ``apply`` moves a cloud, surface samples or a mesh, so that
+``compare_geometry(al.apply(cloud), scan)`` measures the reconstruction and not the misalignment.  No ``ViewFusion`` method either.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -804,6 +810,255 @@ def compare_geometry(a, b, threshold=0.02, scenes=1, samples=None, method="auto"
     scene_of = lambda side: None if torch.is_tensor(side) else side.scene
     m = geometry_metrics(ab.dist2, scene_of(sides[0]), ba.dist2, scene_of(sides[1]), N, threshold)
     return GeometryDistance(a_to_b=ab, b_to_a=ba, **m)
+
+
+# ------------------------------------------------------------------------------------------------ alignment
+ALIGN_ITERS = 30                             # align_geometry's default iteration count (an INTERFACE default, see its docstring)
+
+
+def _align_apply(xyz, start, N, transform):
+    """The enqueue of mvd_align_apply: xyz (n, 3) fp32, start (N + 1) int32, transform (N, 12) float64, contiguous on one GPU
+    -> moved (n, 3) fp32.  No host synchronisation."""
+    L = hip.lib()
+    n = int(xyz.shape[0])
+    hip._req(xyz), hip._req(start, torch.int32), hip._req(transform, torch.float64)
+    out = torch.empty_like(xyz)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_align_apply(p(xyz), hip.ptr(start), n, N, hip.ptr(transform), p(out), hip.stream()))
+    return out
+
+
+def _align_fit(moved, start, target, index, N, flags, max_d2, transform):
+    """The enqueues of mvd_align_fit on the given pairing (index (n,) int32 or None: row i with row i; d2 formed by the kernel).
+    transform (N, 12) float64 is composed in place unless flags has hip.ALIGN_NO_STEP.  Returns the history row (N, 3) float64."""
+    L = hip.lib()
+    dev, n, nt = moved.device, int(moved.shape[0]), int(target.shape[0])
+    hip._req(moved), hip._req(target), hip._req(start, torch.int32), hip._req(transform, torch.float64)
+    if index is not None:
+        hip._req(index, torch.int32)
+    row = torch.empty(N, hip.ALIGN_HISTORY, dtype=torch.float64, device=dev)
+    nbytes = int(L.mvd_align_scratch(n, 0, N, hip.NN_BRUTE, 0))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
+    hip.check(L.mvd_align_fit(p(moved), hip.ptr(start), p(target), p(index), None, n, nt, N, flags, max_d2, hip.ptr(transform), hip.ptr(row),
+                              hip.ptr(scratch), nbytes, hip.stream()))
+    return row
+
+
+def _align_icp(source, source_start, target, target_start, N, method, grid, iters, flags, max_d2, transform):
+    """The enqueues of mvd_align_icp.  transform (N, 12) float64 holds the start and is overwritten with the result.  Returns
+    (history (iters + 1, N, 3) float64, moved (n, 3) fp32, index (n,) int32, dist2 (n,) fp32).  No host synchronisation."""
+    L = hip.lib()
+    dev, nq, nt = source.device, int(source.shape[0]), int(target.shape[0])
+    hip._req(source), hip._req(target), hip._req(source_start, torch.int32), hip._req(target_start, torch.int32), hip._req(transform, torch.float64)
+    history = torch.empty(iters + 1, N, hip.ALIGN_HISTORY, dtype=torch.float64, device=dev)
+    moved = torch.empty_like(source)
+    index = torch.empty(nq, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
+    nbytes = int(L.mvd_align_scratch(nq, nt, N, method, grid))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_align_icp(p(source), hip.ptr(source_start), p(target), hip.ptr(target_start), nq, nt, N, method, grid, iters, flags, max_d2,
+                              hip.ptr(transform), hip.ptr(history), p(moved), p(index), p(dist2), hip.ptr(scratch), nbytes, hip.stream()))
+    return history, moved, index, dist2
+
+
+@dataclass
+class Alignment:
+    """What ``fit_similarity`` and ``align_geometry`` return: per scene the similarity x -> s R x + t that takes the source into the
+    target's frame.  Every field is a tensor on the source's device."""
+    matrix: torch.Tensor                     # (N, 4, 4) float64: [[s R, t], [0, 1]]
+    rotation: torch.Tensor                   # (N, 3, 3) float64, proper (det = +1)
+    translation: torch.Tensor                # (N, 3) float64
+    scale: torch.Tensor                      # (N,) float64 (1 exactly when no scale was fitted or given)
+    rms: torch.Tensor                        # (iters + 1, N) float64: RMS distance of the accepted pairs BEFORE step k; last row: under
+    #                                          the returned transform.  NaN for a scene without an accepted pair
+    pairs: torch.Tensor                      # (iters + 1, N) int64: accepted pairs, same rows
+    xyz: torch.Tensor                        # (n, 3) fp32: the source points under the returned transform
+    nearest: NearestPoints                   # of `xyz` against the target (the final correspondences)
+
+    def apply(self, geometry):
+        """``geometry`` with its coordinates moved by this alignment (include/mvd_hip.h: mvd_align_apply has the rule), as the same
+        type through ``dataclasses.replace``: an (n, 3) tensor (scene 0; only when the alignment has one scene), a PointCloud,
+        SurfaceSamples or a TriangleMesh.  Colours, faces and offsets are the objects they were.  No host synchronisation."""
+        import dataclasses
+        N = int(self.matrix.shape[0])
+        if torch.is_tensor(geometry):
+            if N != 1:
+                raise ValueError(f"geometry: a bare tensor is scene 0, the alignment has {N} scenes -- pass a PointCloud or SurfaceSamples")
+            if geometry.dim() != 2 or geometry.shape[1] != 3:
+                raise ValueError(f"geometry: shape {tuple(geometry.shape)}, need (n, 3)")
+            xyz, scene, key, start = geometry, None, None, None
+        elif isinstance(geometry, TriangleMesh):
+            if int(geometry.vertex_start.numel()) - 1 != N:
+                raise ValueError(f"geometry: a mesh of {int(geometry.vertex_start.numel()) - 1} scene(s), the alignment has {N}")
+            xyz, scene, key, start = geometry.vertices, None, "vertices", geometry.vertex_start
+        elif hasattr(geometry, "xyz") and hasattr(geometry, "scene"):
+            xyz, scene = _points_of(geometry, "geometry", N)
+            key, start = "xyz", None
+        else:
+            raise ValueError("geometry must be an (n, 3) tensor, a PointCloud, SurfaceSamples or a TriangleMesh")
+        dev = xyz.device
+        start = _scene_start(scene, int(xyz.shape[0]), N, dev) if start is None else start.to(dev, torch.int32).contiguous()
+        moved = _align_apply(xyz.float().contiguous(), start, N, self.matrix[:, :3, :].to(dev, torch.float64).reshape(N, 12).contiguous())
+        return moved if key is None else dataclasses.replace(geometry, **{key: moved})
+
+
+def _alignment(transform, scale, history, xyz, index, dist2):
+    N = int(transform.shape[0])
+    m34 = transform.reshape(N, 3, 4)
+    bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=transform.device).expand(N, 1, 4)
+    return Alignment(matrix=torch.cat([m34, bottom], dim=1), rotation=m34[:, :, :3] / scale[:, None, None], translation=m34[:, :, 3].clone(),
+                     scale=scale, rms=history[:, :, 0].clone(), pairs=history[:, :, 1].to(torch.int64), xyz=xyz,
+                     nearest=NearestPoints(index=index, dist2=dist2))
+
+
+def _identity_transform(N, dev):
+    return torch.eye(3, 4, dtype=torch.float64, device=dev).reshape(1, 12).repeat(N, 1)
+
+
+def _fl32_square(v):
+    """fl32(fl32(v)^2) as a Python float: the threshold the kernel compares fp32 distances with."""
+    import struct
+    f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]
+    try:
+        return f32(f32(v) * f32(v))
+    except OverflowError:
+        return float("inf")
+
+
+def fit_similarity(source, target, scenes=1, scale=True, pairs=None):
+    """The similarity (rigid with ``scale=False``) that best takes ``source`` onto ``target`` in the least-squares sense, for KNOWN
+    correspondences, in closed form (Horn's quaternion solve; include/mvd_hip.h: mvd_align_fit has the rule) -> Alignment.
+
+    source, target : what ``nearest_points`` takes.  Row i of source goes with row i of target -- both sides then have equal lengths,
+              and the target's scene offsets are TAKEN to be the source's: its own scene ids are not looked at (comparing the two
+              would be a host read) -- or, with ``pairs`` an (n,) int32 tensor, with row pairs[i] of target; -1 skips the row.  A
+              pair with a non-finite coordinate is skipped.
+    scenes  : N; every scene gets its own transform from its own rows.
+    A scene with fewer than 3 pairs, or whose source points coincide, gets the identity.  ``rms`` and ``pairs`` have one row: under
+    the fit.  ``nearest`` holds the given pairing and its squared distances under the fit (-1 / +inf for a skipped row).  Nothing is
+    read back from the device."""
+    N, _, _ = _check_nn(scenes, "auto", None)
+    if not isinstance(scale, bool):
+        raise ValueError(f"scale = {scale!r}: True or False")
+    s, s_scene = _points_of(source, "source", N)
+    t, t_scene = _points_of(target, "target", N)
+    dev, n, nt = s.device, int(s.shape[0]), int(t.shape[0])
+    if pairs is None:
+        if n != nt:
+            raise ValueError(f"target: {nt} points for {n} of source -- row i goes with row i; give pairs otherwise")
+    elif not torch.is_tensor(pairs) or tuple(pairs.shape) != (n,) or pairs.dtype != torch.int32:
+        raise ValueError(f"pairs: an ({n},) int32 tensor, one target row (or -1) per source row")
+    s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
+    start = _scene_start(s_scene, n, N, dev)
+    index = None if pairs is None else pairs.to(dev).contiguous()
+    flags = hip.ALIGN_SCALE if scale else 0
+    transform = _identity_transform(N, dev)
+    first = _align_fit(s, start, t, index, N, flags, float("inf"), transform)
+    moved = _align_apply(s, start, N, transform)
+    last = _align_fit(moved, start, t, index, N, flags | hip.ALIGN_NO_STEP, float("inf"), transform)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    j = rows if index is None else index
+    has = (j >= 0) & (j < nt) & (rows >= start[0]) & (rows < start[N])
+    d = moved - t[j.long().clamp(0, max(nt - 1, 0))] if nt else torch.full_like(moved, float("nan"))
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]          # (the search's order: every torch op rounds once)
+    has = has & (d2 < float("inf"))
+    return _alignment(transform, first[:, 2].clone(), last[None], moved, torch.where(has, j, torch.full_like(j, -1)),
+                      torch.where(has, d2, torch.full_like(d2, float("inf"))))
+
+
+def _centroid_init(s, s_start, t, t_start, N, scale):
+    """(N, 12) float64: per scene the map of the source's centroid onto the target's, with ``scale`` also of the RMS radius.  float64
+    torch ops on each scene's slice (finite rows only); the identity for a scene with an empty side.  Reads the scene offsets once."""
+    starts = torch.stack([s_start, t_start]).tolist()
+    dev = s.device
+    out = []
+    for k in range(N):
+        stats = []
+        for pts, st in ((s, starts[0]), (t, starts[1])):
+            part = pts[st[k]:st[k + 1]].double()
+            fin = torch.isfinite(part).all(1, keepdim=True)
+            cnt = fin.sum().double()
+            c = torch.where(fin, part, torch.zeros_like(part)).sum(0) / cnt
+            r2 = torch.where(fin, (part - c) ** 2, torch.zeros_like(part)).sum() / cnt
+            stats.append((cnt, c, r2))
+        (na, ca, ra), (nb, cb, rb) = stats
+        ok = (na > 0) & (nb > 0)
+        k_ = torch.sqrt(rb / ra) if scale else torch.ones((), dtype=torch.float64, device=dev)
+        ok = ok & torch.isfinite(k_) & (k_ > 0)
+        k_ = torch.where(ok, k_, torch.ones_like(k_))
+        shift = torch.where(ok, cb - k_ * ca, torch.zeros_like(ca))
+        out.append(torch.cat([k_ * torch.eye(3, dtype=torch.float64, device=dev), shift[:, None]], dim=1).reshape(12))
+    return torch.stack(out), torch.stack([o[0] for o in out])
+
+
+def _check_init(init, N, dev):
+    """(transform (N, 12) float64 on dev, scale (N,) float64) of a matrix-like ``init``."""
+    if isinstance(init, Alignment):
+        m, sc = init.matrix, init.scale
+        if tuple(m.shape) != (N, 4, 4):
+            raise ValueError(f"init: an Alignment of {int(m.shape[0])} scene(s) with scenes = {N}")
+        return m[:, :3, :].to(dev, torch.float64).reshape(N, 12).contiguous(), sc.to(dev, torch.float64).clone()
+    if not torch.is_tensor(init) or tuple(init.shape) not in ((4, 4), (N, 4, 4)):
+        raise ValueError(f"init: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
+    m = init.to(torch.float64)
+    if m.device.type == "cpu":
+        flat = m.reshape(-1, 4, 4)
+        if not bool(torch.isfinite(flat).all()) or not bool((flat[:, 3] == torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)).all()):
+            raise ValueError("init: a finite matrix whose last row is (0, 0, 0, 1)")
+        if not bool((torch.linalg.det(flat[:, :3, :3]) > 0).all()):
+            raise ValueError("init: the 3 x 3 block must have a positive determinant (a similarity, not a reflection)")
+    m = m.to(dev).expand(N, 4, 4) if m.dim() == 2 else m.to(dev)
+    return m[:, :3, :].reshape(N, 12).contiguous(), torch.linalg.det(m[:, :3, :3]).abs().pow(1.0 / 3.0)
+
+
+def align_geometry(source, target, scenes=1, iters=ALIGN_ITERS, scale=False, max_distance=None, init=None, method="auto", grid=None):
+    """Point-to-point ICP: ``iters`` times, every source point under the current transform is matched with its exact nearest target
+    point (``nearest_points``' bits) and the transform is re-fitted to the accepted pairs in closed form (include/mvd_hip.h:
+    mvd_align_icp has the rule) -> Alignment, whose ``rms`` / ``pairs`` history is how a caller sees convergence.
+
+    source, target : what ``nearest_points`` takes; a TriangleMesh is refused with the same message.  The target never moves: its
+              grid is built once.
+    scenes  : N; every scene is aligned on its own.
+    iters   : an integer in [0, 1024], a FIXED count: nothing is read back from the device, so there is no early exit.  0 returns
+              ``init`` with its one history row.
+    scale   : also fit a uniform scale (a similarity); False keeps it at exactly 1 times that of ``init``.
+    max_distance : in world units; a pair is accepted when the point found a target and dist2 <= fl32(max_distance)^2, compared in
+              fp32.  None accepts every pair.  With outliers or partial overlap a gate is what keeps the fit honest.
+    init    : where to start: None (the identity), an Alignment, an (N, 4, 4) or (4, 4) matrix [[s R, t], [0, 1]] with det > 0 (a matrix
+              in host memory is checked: finite, last row (0, 0, 0, 1), det > 0; one on the GPU is NOT, nothing being read back -- a
+              reflection or a NaN there is taken as given, and its scale as |det|^(1/3)), or
+              "centroid" -- the source's per-scene centroid mapped onto the target's and, with ``scale``, the RMS radii matched
+              (float64 torch ops per scene slice; reads the scene offsets once).  ICP converges to the nearest local optimum: it needs
+              a start in its basin -- there is no global registration here.
+    method, grid : those of ``nearest_points``.
+    ``iters`` and ``max_distance`` are INTERFACE defaults: no trained checkpoint or scan was available when this was written, so
+    nobody has tuned them on real data -- expect to.  A scene with fewer than 3 accepted pairs keeps its transform.  Apart from
+    ``init="centroid"`` nothing synchronises with the host."""
+    N, method, grid = _check_nn(scenes, method, grid)
+    if isinstance(iters, bool) or not isinstance(iters, (int, float)) or int(iters) != iters or not 0 <= iters <= hip.ALIGN_MAX_ITERS:
+        raise ValueError(f"iters = {iters}: an integer in [0, {hip.ALIGN_MAX_ITERS}]")
+    if not isinstance(scale, bool):
+        raise ValueError(f"scale = {scale!r}: True or False")
+    if max_distance is not None and not float(max_distance) >= 0:
+        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    s, s_scene = _points_of(source, "source", N)
+    t, t_scene = _points_of(target, "target", N)
+    dev = s.device
+    s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
+    s_start, t_start = _scene_start(s_scene, int(s.shape[0]), N, dev), _scene_start(t_scene, int(t.shape[0]), N, dev)
+    if init is None:
+        transform, scale0 = _identity_transform(N, dev), torch.ones(N, dtype=torch.float64, device=dev)
+    elif isinstance(init, str):
+        if init != "centroid":
+            raise ValueError(f"init = {init!r}: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
+        transform, scale0 = _centroid_init(s, s_start, t, t_start, N, scale)
+    else:
+        transform, scale0 = _check_init(init, N, dev)
+    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
+    history, moved, index, dist2 = _align_icp(s, s_start, t, t_start, N, method, grid, int(iters), hip.ALIGN_SCALE if scale else 0, max_d2, transform)
+    return _alignment(transform, scale0 * history[-1, :, 2], history, moved, index, dist2)
 
 
 def write_ply(path, cloud):

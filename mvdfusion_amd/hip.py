@@ -54,6 +54,10 @@ RENDER_FILL, RENDER_SPLAT, RENDER_RESOLVE, RENDER_ALL = 1, 2, 4, 7      # stages
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2                       # method of mvd_nearest_points
 NN_BUILD, NN_QUERY, NN_ALL = 1, 2, 3                       # stages of mvd_nearest_points_stages
 NN_MAX_GRID = 256                                          # the largest `grid` of mvd_nearest_points
+ALIGN_SCALE, ALIGN_NO_STEP = 1, 2                          # flags of mvd_align_fit (mvd_align_icp, mvd_align_solve: ALIGN_SCALE only)
+ALIGN_CHUNK = 1024                                         # MVD_ALIGN_CHUNK: the rows one workgroup of the moment sums reduces
+ALIGN_SUMS, ALIGN_HISTORY = 19, 3                          # doubles per scene: the moment sums; a history row (rms, pairs, step scale)
+ALIGN_MAX_ITERS = 1024                                     # the largest `iters` of mvd_align_icp
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -173,6 +177,11 @@ SIGNATURES = {
     "mvd_nearest_points_scratch": (_sz, [_sz, _i, _i, _i]),
     "mvd_nearest_points": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mvd_nearest_points_stages": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]),
+    "mvd_align_scratch": (_sz, [_sz, _sz, _i, _i, _i]),
+    "mvd_align_solve": (_i, [_vp, _i, _vp, _vp]),
+    "mvd_align_apply": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
+    "mvd_align_fit": (_i, [_vp] * 5 + [_sz, _sz, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_align_icp": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _i, _i, _f] + [_vp] * 6 + [_sz, _vp]),
     "mvd_tsdf_integrate": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _vp]),
     "mvd_mesh_scratch": (_sz, [_i, _i]),
     "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
