@@ -718,6 +718,63 @@ int mvd_nearest_points_stages(const float* query, const int* query_start, const 
                               int stages, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Neighbourhoods: the k nearest target points of every query point, and a normal per point from such a list (csrc/nearest.hip,
+ * csrc/normals.hip; host: mvdfusion_amd/fusion.py knn_points, estimate_normals).  Not in the reference either.
+ *
+ * mvd_knn_points: the search of mvd_nearest_points -- its scenes, its d2 in fp32 in the same operation order without contraction, its
+ *   method / grid / scratch conventions, its grid build (one copy of the code) -- returning the k best candidates instead of one.
+ *   Order     : the candidates of a query (the targets of its scene with d2 < +inf) are totally ordered by (d2, j) lexicographically,
+ *               d2 compared in fp32.  The result is the first min(k, candidates) of that order, ascending: a pure function of the
+ *               inputs, whatever order cells and records are met in (the grid's scatter order differs run to run).
+ *   Outputs   : index (nq, k) int32 and dist2 (nq, k) fp32, row-major; unfilled slots hold -1 / +inf.  Every element is written.
+ *   The strict comparison against +inf decides every odd case exactly as in mvd_nearest_points: a non-finite target is in no list, a
+ *   non-finite query, a query of an empty scene and a query of no scene get k empty slots.
+ *   k         : 1 <= k <= MVD_KNN_MAX_K.  k = 1 gives the bits of mvd_nearest_points.
+ *   Self      : query may be target.  A point is then its own candidate at d2 = 0 and stays in the list (in slot 0 unless a coincident
+ *               point with a lower row precedes it).  There is no exclude flag.
+ *   MVD_NN_GRID : the shell walk of mvd_nearest_points, which stops after shell r once the k-th best so far lies strictly below the
+ *               same lower bound; with fewer than k found it runs to the last shell.  The loop is bounded by the host value grid.
+ *   MVD_NN_BRUTE: the LDS-tiled scan with a k-list per thread.  MVD_NN_AUTO resolves as for mvd_nearest_points, whatever k.
+ *   The list  : kept in registers: the kernels are compiled for list sizes 1, 2, 4, 8, 16 and 32 with the insertion unrolled, and a
+ *               call runs the smallest size that holds k.
+ *   scratch   : mvd_nearest_points_scratch(nt, nscene, method, grid) bytes, the same layout: a grid built by either search
+ *               (MVD_NN_BUILD) serves the MVD_NN_QUERY of both, with the same target, target_start, nt, nscene, method and grid.
+ *   All pointers 4-byte aligned, the scratch 16-byte.  Limits, empty sides, enqueue-only and checked-before-enqueue as for
+ *   mvd_nearest_points; a refused call writes nothing.
+ * mvd_knn_points_stages: the same call restricted to `stages`, as mvd_nearest_points_stages.
+ *
+ * mvd_point_normals: one normal per point from its neighbour rows, in fp64 throughout, in list order.
+ *   target (nt, 3) fp32; index (n, k) int32 rows of target (a row of mvd_knn_points' index, or any list); 1 <= k <= MVD_NORMALS_MAX_K.
+ *   Used rows : the entries j of the point's row with 0 <= j < nt and three finite coordinates; m of them.  x = (double) of each.
+ *   Centre    : c = (sum of x in list order) / m, per axis.
+ *   Covariance: C_ab = sum (x_a - c_a) * (x_b - c_b) for ab = xx, xy, xz, yy, yz, zz: each difference and each product rounded once in
+ *               fp64 (no contraction), the addends added in list order.
+ *   Eigen     : cyclic Jacobi on C in fp64, MVD_NORMALS_SWEEPS sweeps over (0,1), (0,2), (1,2) with the conventions of mvd_align_solve
+ *               (a rotation is skipped where the off-diagonal is 0; tan = 1 / (|theta| + sqrt(theta^2 + 1)), 1 / (2 |theta|) beyond
+ *               |theta| = 1e150).  The eigenvalues are the diagonal, each raised to 0 where rounding left it negative; l0 <= l1 <= l2.
+ *   Normal    : the eigenvector of the smallest eigenvalue (between equal diagonal entries the lowest column), divided by its length.
+ *   Sign      : the component of largest magnitude is made positive, between equal magnitudes the lowest axis decides -- on the fp64
+ *               vector.  Then, with toward (n, 3) fp32 and the points themselves p (n, 3) fp32, the normal is negated when
+ *               (n_x * (t_x - p_x) + n_y * (t_y - p_y)) + n_z * (t_z - p_z) < 0 in fp64 (a NaN negates nothing).  toward == NULL: no
+ *               second step, and points may be NULL.  The normal is rounded to fp32 once, at the end.
+ *   variation : (n,) fp32 = l0 / ((l0 + l1) + l2): the surface variation, 0 on a plane, at most 1 / 3.
+ *   Valid     : m >= 3 and l1 > 0 (the rows are neither coincident nor collinear) and every sum, eigenvalue and component finite.
+ *               Otherwise normal = (0, 0, 0) and variation = NaN: a valid point is one whose variation is not NaN.
+ *   normal (n, 3), variation (n,): every element is written.  n = 0 is valid.  n * k <= 2^31 - 1.  One thread per point; enqueued on
+ *   the caller's stream, nothing synchronised or allocated, every argument checked before the enqueue. */
+#define MVD_KNN_MAX_K 32
+#define MVD_NORMALS_MAX_K 256
+#define MVD_NORMALS_SWEEPS 10
+int mvd_knn_points(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq, size_t nt,
+                   int nscene, int k, int method, int grid, int* index, float* dist2, void* scratch, size_t scratch_bytes,
+                   mvd_stream_t stream);
+int mvd_knn_points_stages(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq, size_t nt,
+                          int nscene, int k, int method, int grid, int* index, float* dist2, void* scratch, size_t scratch_bytes,
+                          int stages, mvd_stream_t stream);
+int mvd_point_normals(const float* target, size_t nt, const int* index, size_t n, int k, const float* points, const float* toward,
+                      float* normal, float* variation, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Aligning geometry: a similarity transform per scene that takes a source cloud onto a target -- the closed form for given pairs, and
  * point-to-point ICP around the search above (csrc/align.hip; host: mvdfusion_amd/fusion.py fit_similarity, align_geometry,
  * Alignment.apply).  Not in the reference either.  A distance between two geometries means something only in one frame.
@@ -782,6 +839,60 @@ int mvd_align_fit(const float* moved, const int* start, const float* target, con
                   mvd_stream_t stream);
 int mvd_align_icp(const float* source, const int* source_start, const float* target, const int* target_start, size_t nq, size_t nt,
                   int nscene, int method, int grid, int iters, int flags, float max_dist2, double* transform, double* history,
+                  float* moved, int* index, float* dist2, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Aligning to a surface: point-to-plane ICP -- the loop, the pairs, the chunked reduction and the apply of the section above with the
+ * linearised point-to-plane error and its six-parameter solve in place of the moments and Horn's closed form (csrc/align.hip; host:
+ * mvdfusion_amd/fusion.py fit_plane_step, align_to_surface).  Not in the reference either.  Rigid only: a step is [R | t] with R a
+ * proper rotation, so a scale in the transform given on entry is carried through untouched.
+ *
+ * normals   : (nt, 3) fp32, one per TARGET row (mvd_point_normals' output, or any); unit length is not required.
+ * Pairs     : those of mvd_align_fit, accepted as there (d2 < +inf and d2 <= max_dist2 in fp32); in addition the target's normal must
+ *             have three finite components, not all zero.
+ * Per pair  : in fp64, with p the moved source point, q the target, n its normal (all exact conversions of fp32 values):
+ *             e = p - q;  r = (e_x n_x + e_y n_y) + e_z n_z;  c = p x n, each component one subtraction of two exact products
+ *             (c_x = p_y n_z - p_z n_y, ...);  a = (c_x, c_y, c_z, n_x, n_y, n_z).  r + a . (omega, t) is the distance of the pair
+ *             along n after the small motion x -> x + omega x x + t.
+ * Sums      : per scene MVD_PLANE_SUMS = 30 doubles: [0] the count, [1..21] the upper triangle of sum a_i a_j, row-major (00, 01, ..,
+ *             05, 11, .., 55), [22..27] sum a_i r, [28] sum r r, [29] sum (double)d2.  Reduced exactly as MVD_ALIGN_SUMS are -- chunks of
+ *             MVD_ALIGN_CHUNK rows from the scene's first row, the fixed in-workgroup order, chunk sums added in ascending order, no
+ *             float atomics, the device prefix map (one copy of that code): the same bits run to run and for a scene alone or in a batch.
+ * Solve     : H (6 x 6, symmetric) from [1..21], g from [22..27].  H is eigen-decomposed by cyclic Jacobi in fp64 (a fixed number of
+ *             sweeps, the conventions of mvd_align_solve); lambda_max is the largest diagonal entry; the directions i with
+ *             lambda_i > MVD_PLANE_EPS_RANK * lambda_max are KEPT and x = - sum_kept v_i (v_i . g) / lambda_i (i ascending, every dot
+ *             product summed in component order).  A direction the data does not constrain is left alone, not blown up: in-plane
+ *             motion on a plane target, rotation about the centre on a sphere.  omega = x[0..2], t = x[3..5]; R = exp([omega]x) through
+ *             the quaternion (cos(a / 2), omega sin(a / 2) / a), a = |omega| (below a = 1e-4 from the series 1 - a^2 / 8 + a^4 / 384
+ *             and 1 / 2 - a^2 / 48 + a^4 / 3840), normalised to unit length -- a proper rotation whatever the data.  D = [R | t]
+ *             composes as m <- D m in fp64.  D is the identity, with rank 0, when fewer than 3 pairs were accepted, when lambda_max
+ *             is not positive, or when a sum or a result is not finite.
+ * History   : a row is MVD_PLANE_HISTORY = 4 doubles per scene: the plane rms sqrt(sums[28] / n), n, the point rms sqrt(sums[29] / n)
+ *             (what mvd_align_fit reports; both NaN with n = 0), and the rank the solve of these sums keeps (computed for a row
+ *             without a step too).
+ *
+ * mvd_plane_fit  : mvd_align_fit with normals: sums, solve and composition for given pairs.  flags: MVD_PLANE_NO_STEP writes history_row
+ *             only.  scratch: mvd_plane_scratch(n, 0, nscene, MVD_NN_BRUTE, 0) bytes, 16-byte aligned.
+ * mvd_plane_icp  : mvd_align_icp's loop with this fit: MVD_NN_BUILD once over target; iters times { apply transform to the ORIGINAL
+ *             source -> moved; MVD_NN_QUERY through mvd_nearest_points_stages -> index, dist2; fit; history row k }; then a last apply,
+ *             query and row (iters) without a step.  history is (iters + 1, nscene, 4); moved, index, dist2 are left as the last pass
+ *             wrote them.  0 <= iters <= MVD_ALIGN_MAX_ITERS, a fixed count, nothing read back.  scratch: mvd_plane_scratch(nq, nt,
+ *             nscene, method, grid) bytes (0 for an argument out of range).
+ * mvd_plane_solve: the solve alone, on the host, the same function the kernel calls: sums[30] -> step[12], *rank.  Needs no GPU.  (The
+ *             rotation goes through cos and sin, so host and device may differ in the last bits; everything before it is sqrt, +, *, /.)
+ * Enqueue-only, nothing allocated, every argument checked before anything is enqueued, a refused call writes nothing, and every word of
+ * the scratch that is read is written earlier in the same call -- as in the section above. */
+#define MVD_PLANE_NO_STEP 2
+#define MVD_PLANE_SUMS 30
+#define MVD_PLANE_HISTORY 4
+#define MVD_PLANE_EPS_RANK 1e-9
+size_t mvd_plane_scratch(size_t nq, size_t nt, int nscene, int method, int grid);
+int mvd_plane_solve(const double* sums, double* step, int* rank);
+int mvd_plane_fit(const float* moved, const int* start, const float* target, const float* normals, const int* index, const float* dist2,
+                  size_t n, size_t nt, int nscene, int flags, float max_dist2, double* transform, double* history_row, void* scratch,
+                  size_t scratch_bytes, mvd_stream_t stream);
+int mvd_plane_icp(const float* source, const int* source_start, const float* target, const int* target_start, const float* normals,
+                  size_t nq, size_t nt, int nscene, int method, int grid, int iters, float max_dist2, double* transform, double* history,
                   float* moved, int* index, float* dist2, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------

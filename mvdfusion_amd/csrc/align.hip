@@ -13,6 +13,11 @@
 // The per-element pieces (al_apply, al_partner, al_accept, al_add_pair, al_solve, al_finish) are host-and-device functions:
 // mvd_align_solve runs the very solve of the kernel on the host, and the pieces can be run serially on a CPU.
 //
+// POINT TO PLANE (mvd_plane_fit, mvd_plane_icp; the header has the rule): the same chunk map, the same reduction and the same loop with
+// another thing summed per pair and another solve.  accumulate_kernel and solve_kernel are templates over the fit -- PointFit: the
+// nineteen moments and Horn's solve; PlaneFit: the thirty sums of the linearised point-to-plane error and a 6 x 6 Jacobi with the
+// unconstrained directions left out (pl_solve, which mvd_plane_solve runs on the host).
+//
 // Not tried: apply fused into the query's head or the accumulate's tail, a tree over the partials.
 #include "fusion_common.hpp"
 
@@ -26,6 +31,9 @@ constexpr int kAlSums = MVD_ALIGN_SUMS;
 constexpr int kSolveTile = 128;                       // chunk sums the solve stages through LDS at a time (19 KB)
 constexpr int kAlSweeps = 12;                         // cyclic Jacobi sweeps of the 4 x 4 solve (converged after 5 or 6; the rest skip)
 constexpr double kAlThetaBig = 1e150;                 // above it theta^2 + 1 == theta^2 in fp64, and theta^2 would overflow near 1.3e154
+constexpr int kPlSums = MVD_PLANE_SUMS;
+constexpr int kPlSweeps = 16;                         // cyclic Jacobi sweeps of the 6 x 6 solve (converged after 6 or 7; the rest skip)
+constexpr double kPlSmallAngle = 1e-4;                // below it the quaternion of the step comes from the series (next term: angle^6 / 645120)
 static_assert(kAlChunk % kAlThreads == 0, "whole rows per thread");
 
 AL_HD long long al_clamp(long long v, long long n) { return v < 0 ? 0 : (v > n ? n : v); }
@@ -199,6 +207,140 @@ AL_HD void al_finish(const double* sums, int flags, double before, double* m, do
   for (int k = 0; k < 12; ++k) m[k] = out[k];
 }
 
+// ---------------------------------------------------------------------------------------------------------------- point to plane
+// one accepted pair into the thirty sums: p the moved source point, q the target, n its normal
+AL_HD void pl_add_pair(double* s, const float* p, const float* q, const float* nrm, float d2) {
+  const double px = p[0], py = p[1], pz = p[2], nx = nrm[0], ny = nrm[1], nz = nrm[2];
+  const double ex = px - (double)q[0], ey = py - (double)q[1], ez = pz - (double)q[2];
+  const double r = (ex * nx + ey * ny) + ez * nz;
+  const double a[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};      // (p x n, n): the products are exact
+  s[0] += 1.0;
+  int at = 1;
+#pragma unroll
+  for (int i = 0; i < 6; ++i)
+#pragma unroll
+    for (int j = i; j < 6; ++j) s[at++] += a[i] * a[j];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) s[22 + i] += a[i] * r;
+  s[28] += r * r;
+  s[29] += (double)d2;
+}
+
+AL_HD bool pl_finitef(float v) { return fabsf(v) < INFINITY; }
+
+// row i of the call: adds its pair, if it is one -- mvd_align_fit's pairs and acceptance, and a finite non-zero normal at the target
+AL_HD void pl_add_row(double* s, const float* moved, const float* target, const float* normals, const int* index, const float* dist2, long long nt,
+                      float max_d2, long long i) {
+  const long long j = al_partner(index, i, nt);
+  if (j < 0) return;
+  const float p[3] = {moved[i * 3 + 0], moved[i * 3 + 1], moved[i * 3 + 2]}, q[3] = {target[j * 3 + 0], target[j * 3 + 1], target[j * 3 + 2]};
+  const float nrm[3] = {normals[j * 3 + 0], normals[j * 3 + 1], normals[j * 3 + 2]};
+  const float d2 = dist2 ? dist2[i] : al_d2(p, q);
+  if (!al_accept(d2, max_d2)) return;
+  if (!(pl_finitef(nrm[0]) && pl_finitef(nrm[1]) && pl_finitef(nrm[2])) || (nrm[0] == 0.f && nrm[1] == 0.f && nrm[2] == 0.f)) return;
+  pl_add_pair(s, p, q, nrm, d2);
+}
+
+// Cyclic Jacobi on a symmetric 6 x 6 (al_jacobi4's conventions): A -> diagonal, the eigenvectors in the columns of V.
+AL_HD void pl_jacobi6(double A[6][6], double V[6][6]) {
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) V[r][c] = r == c ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < kPlSweeps; ++sweep)
+    for (int p = 0; p < 5; ++p)
+      for (int q = p + 1; q < 6; ++q) {
+        const double apq = A[p][q];
+        if (apq == 0.0) continue;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * apq), at = fabs(theta);
+        double t = at > kAlThetaBig ? 0.5 / at : 1.0 / (at + sqrt(at * at + 1.0));
+        if (theta < 0.0) t = -t;
+        const double c = 1.0 / sqrt(t * t + 1.0), sn = t * c;
+        for (int k = 0; k < 6; ++k) {
+          const double akp = A[k][p], akq = A[k][q];
+          A[k][p] = c * akp - sn * akq, A[k][q] = sn * akp + c * akq;
+        }
+        for (int k = 0; k < 6; ++k) {
+          const double apk = A[p][k], aqk = A[q][k];
+          A[p][k] = c * apk - sn * aqk, A[q][k] = sn * apk + c * aqk;
+        }
+        A[p][q] = A[q][p] = 0.0;
+        for (int k = 0; k < 6; ++k) {
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - sn * vkq, V[k][q] = sn * vkp + c * vkq;
+        }
+      }
+}
+
+// THE solve of the header: the thirty sums -> the rigid step D (12 doubles, [R | t]) and the rank kept.  The identity (rank 0) for what
+// cannot be solved.
+AL_HD void pl_solve(const double* sums, double* step, int* rank) {
+  double one;
+  al_identity(step, &one);
+  *rank = 0;
+  for (int k = 0; k < kPlSums; ++k)
+    if (!al_finite(sums[k])) return;
+  if (!(sums[0] >= 3.0)) return;
+  double H[6][6], V[6][6];
+  int at = 1;
+  for (int i = 0; i < 6; ++i)
+    for (int j = i; j < 6; ++j) H[i][j] = H[j][i] = sums[at++];
+  const double* g = sums + 22;
+  pl_jacobi6(H, V);
+  double top = H[0][0];
+  for (int k = 1; k < 6; ++k) top = fmax(top, H[k][k]);
+  if (!(top > 0.0) || !al_finite(top)) return;
+  double x[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int kept = 0;
+  for (int i = 0; i < 6; ++i) {
+    const double lam = H[i][i];
+    if (!(lam > MVD_PLANE_EPS_RANK * top)) continue;      // a direction the data does not constrain is left alone
+    double dot = 0.0;
+    for (int k = 0; k < 6; ++k) dot += V[k][i] * g[k];
+    const double w = dot / lam;
+    for (int k = 0; k < 6; ++k) x[k] -= V[k][i] * w;
+    ++kept;
+  }
+  // R = exp([omega]x) through the unit quaternion (cos(angle / 2), omega sin(angle / 2) / angle)
+  const double ang2 = (x[0] * x[0] + x[1] * x[1]) + x[2] * x[2], ang = sqrt(ang2);
+  double qw, f;
+  if (ang < kPlSmallAngle) qw = 1.0 - ang2 / 8.0 + ang2 * ang2 / 384.0, f = 0.5 - ang2 / 48.0 + ang2 * ang2 / 3840.0;
+  else qw = cos(0.5 * ang), f = sin(0.5 * ang) / ang;
+  double q[4] = {qw, f * x[0], f * x[1], f * x[2]};
+  const double len = sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));
+  if (!(len > 0.0) || !al_finite(len)) return;
+  for (int k = 0; k < 4; ++k) q[k] = q[k] / len;
+  const double w = q[0], a = q[1], b = q[2], c = q[3];
+  const double out[12] = {1.0 - 2.0 * (b * b + c * c), 2.0 * (a * b - w * c), 2.0 * (a * c + w * b), x[3],
+                          2.0 * (a * b + w * c), 1.0 - 2.0 * (a * a + c * c), 2.0 * (b * c - w * a), x[4],
+                          2.0 * (a * c - w * b), 2.0 * (b * c + w * a), 1.0 - 2.0 * (a * a + b * b), x[5]};
+  for (int k = 0; k < 12; ++k)
+    if (!al_finite(out[k])) return;
+  for (int k = 0; k < 12; ++k) step[k] = out[k];
+  *rank = kept;
+}
+
+// m <- D m in fp64 (al_finish's composition)
+AL_HD void al_compose(const double* D, double* m) {
+  double out[12];
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 4; ++c) out[r * 4 + c] = (D[r * 4 + 0] * m[0 * 4 + c] + D[r * 4 + 1] * m[1 * 4 + c]) + D[r * 4 + 2] * m[2 * 4 + c];
+    out[r * 4 + 3] += D[r * 4 + 3];
+  }
+  for (int k = 0; k < 12; ++k) m[k] = out[k];
+}
+
+// A scene's thirty sums -> its history row (plane rms, pairs, point rms, the rank its solve keeps) and, unless MVD_PLANE_NO_STEP, m <- D m.
+AL_HD void pl_finish(const double* sums, int flags, double* m, double* row) {
+  const double n = sums[0];
+  row[0] = n > 0.0 ? sqrt(sums[28] / n) : __builtin_nan("");
+  row[1] = n;
+  row[2] = n > 0.0 ? sqrt(sums[29] / n) : __builtin_nan("");
+  double D[12];
+  int rank;
+  pl_solve(sums, D, &rank);
+  row[3] = (double)rank;
+  if (!(flags & MVD_PLANE_NO_STEP)) al_compose(D, m);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- kernels
 struct FitArgs {
   const float *moved, *target;
@@ -210,6 +352,23 @@ struct FitArgs {
   int nscene;
   unsigned nwg;                                       // the launch's workgroups: the host bound ceil(n / kAlChunk) + nscene
   float max_d2;
+  const float* normals;                               // PlaneFit: (nt, 3) at the target's rows
+};
+
+// What a fit sums per pair and does with a scene's sums.
+struct PointFit {
+  static constexpr int kSums = kAlSums, kHistory = MVD_ALIGN_HISTORY;
+  AL_HD static void add_row(double* s, const FitArgs& a, long long i) { al_add_row(s, a.moved, a.target, a.index, a.dist2, a.nt, a.max_d2, i); }
+  AL_HD static void finish(const double* sums, int flags, const double* previous_row, double* m, double* row) {
+    al_finish(sums, flags, previous_row ? previous_row[2] : 1.0, m, row);
+  }
+};
+struct PlaneFit {
+  static constexpr int kSums = kPlSums, kHistory = MVD_PLANE_HISTORY;
+  AL_HD static void add_row(double* s, const FitArgs& a, long long i) {
+    pl_add_row(s, a.moved, a.target, a.normals, a.index, a.dist2, a.nt, a.max_d2, i);
+  }
+  AL_HD static void finish(const double* sums, int flags, const double*, double* m, double* row) { pl_finish(sums, flags, m, row); }
 };
 
 __global__ __launch_bounds__(kAlThreads) void apply_kernel(const float* __restrict__ src, const int* __restrict__ start, long long n, int nscene,
@@ -230,8 +389,10 @@ __global__ __launch_bounds__(kAlThreads) void chunk_count_kernel(const int* __re
   first[s] = len > 0 ? (unsigned)((len + kAlChunk - 1) / kAlChunk) : 0u;
 }
 
+template <class Fit>
 __global__ __launch_bounds__(kAlThreads) void accumulate_kernel(FitArgs a) {
-  __shared__ double wave_s[kAlThreads / 64][kAlSums];
+  constexpr int kSums = Fit::kSums;
+  __shared__ double wave_s[kAlThreads / 64][kSums];
   const unsigned b = blockIdx.x;
   if (b >= a.first[a.nscene]) return;      // (uniform) the bound's slack
   int lo = 0, hi = a.nscene;               // the last scene with first[s] <= b: first[0] = 0, an empty scene owns no chunk
@@ -242,49 +403,51 @@ __global__ __launch_bounds__(kAlThreads) void accumulate_kernel(FitArgs a) {
   }
   const long long r0 = al_clamp(a.start[lo], a.n) + (long long)(b - a.first[lo]) * kAlChunk;
   const long long end = al_clamp(a.start[lo + 1], a.n), r1 = r0 + kAlChunk < end ? r0 + kAlChunk : end;
-  double acc[kAlSums];
+  double acc[kSums];
 #pragma unroll
-  for (int k = 0; k < kAlSums; ++k) acc[k] = 0.0;
+  for (int k = 0; k < kSums; ++k) acc[k] = 0.0;
   for (int k = 0; k < kAlChunk / kAlThreads; ++k) {
     const long long i = r0 + k * kAlThreads + threadIdx.x;
-    if (i < r1) al_add_row(acc, a.moved, a.target, a.index, a.dist2, a.nt, a.max_d2, i);
+    if (i < r1) Fit::add_row(acc, a, i);
   }
 #pragma unroll
-  for (int k = 0; k < kAlSums; ++k) {
+  for (int k = 0; k < kSums; ++k) {
     double v = acc[k];
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
     acc[k] = v;
   }
   if ((threadIdx.x & 63) == 0)
-    for (int k = 0; k < kAlSums; ++k) wave_s[threadIdx.x >> 6][k] = acc[k];
+    for (int k = 0; k < kSums; ++k) wave_s[threadIdx.x >> 6][k] = acc[k];
   __syncthreads();
-  if (threadIdx.x < kAlSums)
-    a.partial[(size_t)b * kAlSums + threadIdx.x] = (wave_s[0][threadIdx.x] + wave_s[1][threadIdx.x]) + (wave_s[2][threadIdx.x] + wave_s[3][threadIdx.x]);
+  if (threadIdx.x < kSums)
+    a.partial[(size_t)b * kSums + threadIdx.x] = (wave_s[0][threadIdx.x] + wave_s[1][threadIdx.x]) + (wave_s[2][threadIdx.x] + wave_s[3][threadIdx.x]);
 }
 
 // The chunk sums of a scene arrive in LDS kSolveTile chunks at a time, loaded by the whole workgroup (one memory latency per tile,
 // not per chunk); lane k then adds component k in ascending chunk order.
+template <class Fit>
 __global__ __launch_bounds__(kAlThreads) void solve_kernel(FitArgs a, int flags, double* __restrict__ transform, double* __restrict__ history,
                                                            const double* __restrict__ previous) {
-  __shared__ double tile[kSolveTile * kAlSums];
-  __shared__ double sums[kAlSums];
+  constexpr int kSums = Fit::kSums;
+  __shared__ double tile[kSolveTile * kSums];
+  __shared__ double sums[kSums];
   const int s = blockIdx.x;
   const unsigned c0 = min(a.first[s], a.nwg), c1 = min(a.first[s + 1], a.nwg);
   double v = 0.0;
   for (unsigned base = c0; base < c1; base += kSolveTile) {      // (uniform)
     const unsigned m = min((unsigned)kSolveTile, c1 - base);
     __syncthreads();      // the previous tile has been added
-    for (unsigned e = threadIdx.x; e < m * kAlSums; e += kAlThreads) tile[e] = a.partial[(size_t)base * kAlSums + e];
+    for (unsigned e = threadIdx.x; e < m * kSums; e += kAlThreads) tile[e] = a.partial[(size_t)base * kSums + e];
     __syncthreads();
-    if (threadIdx.x < kAlSums)
-      for (unsigned j = 0; j < m; ++j) v += tile[j * kAlSums + threadIdx.x];
+    if (threadIdx.x < kSums)
+      for (unsigned j = 0; j < m; ++j) v += tile[j * kSums + threadIdx.x];
   }
-  if (threadIdx.x < kAlSums) sums[threadIdx.x] = v;
+  if (threadIdx.x < kSums) sums[threadIdx.x] = v;
   __syncthreads();
   if (threadIdx.x == 0)
-    al_finish(sums, flags, previous ? previous[(size_t)s * MVD_ALIGN_HISTORY + 2] : 1.0, transform + (size_t)s * 12,
-              history + (size_t)s * MVD_ALIGN_HISTORY);
+    Fit::finish(sums, flags, previous ? previous + (size_t)s * Fit::kHistory : nullptr, transform + (size_t)s * 12,
+                history + (size_t)s * Fit::kHistory);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
@@ -296,7 +459,7 @@ struct AlignPlan {
 static size_t al_up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // false: an argument is out of range
-static bool al_plan(size_t nq, size_t nt, int nscene, int method, int grid, AlignPlan& p) {
+static bool al_plan(size_t nq, size_t nt, int nscene, int method, int grid, AlignPlan& p, int sums = kAlSums) {
   p = AlignPlan{};
   if (nscene < 1 || nscene > 65535 || nq > 0x7fffffffull || nt > 0x7fffffffull || method < MVD_NN_AUTO || method > MVD_NN_GRID || grid < 0 ||
       grid > 256)
@@ -304,16 +467,17 @@ static bool al_plan(size_t nq, size_t nt, int nscene, int method, int grid, Alig
   if (method != MVD_NN_BRUTE && (unsigned long long)nscene * grid * grid * grid > 0x7fffffffull) return false;
   p.nwg = (unsigned)((nq + kAlChunk - 1) / kAlChunk) + (unsigned)nscene;
   p.off_partial = al_up16((size_t)(nscene + 1) * sizeof(unsigned));
-  p.off_nn = p.off_partial + al_up16((size_t)p.nwg * kAlSums * sizeof(double));
+  p.off_nn = p.off_partial + al_up16((size_t)p.nwg * sums * sizeof(double));
   p.nn_bytes = mvd_nearest_points_scratch(nt, nscene, method, grid);
   p.bytes = p.off_nn + p.nn_bytes;
   return true;
 }
 
 static FitArgs al_args(const AlignPlan& p, void* scratch, const float* moved, const int* start, const float* target, const int* index,
-                       const float* dist2, size_t n, size_t nt, int nscene, float max_d2) {
+                       const float* dist2, size_t n, size_t nt, int nscene, float max_d2, const float* normals = nullptr) {
   char* base = (char*)scratch;
-  return FitArgs{moved, target, start, index, dist2, (unsigned*)base, (double*)(base + p.off_partial), (long long)n, (long long)nt, nscene, p.nwg, max_d2};
+  return FitArgs{moved, target, start, index, dist2, (unsigned*)base, (double*)(base + p.off_partial), (long long)n, (long long)nt, nscene, p.nwg, max_d2,
+                 normals};
 }
 
 // first[]: once per call
@@ -323,9 +487,10 @@ static void al_launch_map(const FitArgs& a, hipStream_t st) {
 }
 
 // previous: the history row before this one (its scale is carried on), or NULL for the first
+template <class Fit = PointFit>
 static void al_launch_fit(const FitArgs& a, int flags, double* transform, double* history, const double* previous, hipStream_t st) {
-  hipLaunchKernelGGL(accumulate_kernel, dim3(a.nwg), dim3(kAlThreads), 0, st, a);
-  hipLaunchKernelGGL(solve_kernel, dim3(a.nscene), dim3(kAlThreads), 0, st, a, flags, transform, history, previous);
+  hipLaunchKernelGGL(accumulate_kernel<Fit>, dim3(a.nwg), dim3(kAlThreads), 0, st, a);
+  hipLaunchKernelGGL(solve_kernel<Fit>, dim3(a.nscene), dim3(kAlThreads), 0, st, a, flags, transform, history, previous);
 }
 
 static void al_launch_apply(const float* src, const int* start, size_t n, int nscene, const double* transform, float* out, hipStream_t st) {
@@ -416,6 +581,85 @@ extern "C" int mvd_align_icp(const float* source, const int* source_start, const
                                    MVD_NN_QUERY, stream);
     if (rc != 0) break;      // (its argument checks are this function's own, so only a failed enqueue gets here: nothing is fitted to it)
     al_launch_fit(a, k < iters ? flags : (flags | MVD_ALIGN_NO_STEP), transform, history + (size_t)k * row, k ? history + (size_t)(k - 1) * row : nullptr, st);
+  }
+  if (rc != 0) {
+    char why[400];
+    snprintf(why, sizeof(why), "%s", mvd_last_error());
+    mvd_set_error("%s: %s", fn, why);
+    return rc;
+  }
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- point to plane: entries
+extern "C" size_t mvd_plane_scratch(size_t nq, size_t nt, int nscene, int method, int grid) {
+  AlignPlan p;
+  return al_plan(nq, nt, nscene, method, grid, p, kPlSums) ? p.bytes : 0;
+}
+
+extern "C" int mvd_plane_solve(const double* sums, double* step, int* rank) {
+  const char* fn = "mvd_plane_solve";
+  MVD_CHECK_ARG(sums && step && rank, "%s: null sums, step or rank", fn);
+  pl_solve(sums, step, rank);
+  return 0;
+}
+
+extern "C" int mvd_plane_fit(const float* moved, const int* start, const float* target, const float* normals, const int* index,
+                             const float* dist2, size_t n, size_t nt, int nscene, int flags, float max_dist2, double* transform,
+                             double* history_row, void* scratch, size_t scratch_bytes, mvd_stream_t stream) {
+  const char* fn = "mvd_plane_fit";
+  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
+  MVD_CHECK_ARG(n <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: n=%zu, nt=%zu beyond 2^31 - 1", fn, n, nt);
+  MVD_CHECK_ARG((flags & ~MVD_PLANE_NO_STEP) == 0, "%s: flags=%d (MVD_PLANE_NO_STEP or 0)", fn, flags);
+  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
+  MVD_CHECK_ARG(start && transform && history_row && al_aligned(transform, 8) && al_aligned(history_row, 8),
+                "%s: null start, null or misaligned transform or history_row", fn);
+  MVD_CHECK_ARG(moved || n == 0, "%s: null moved with n=%zu", fn, n);
+  MVD_CHECK_ARG((target && normals) || nt == 0, "%s: null target or normals with nt=%zu", fn, nt);
+  AlignPlan p;
+  al_plan(n, 0, nscene, MVD_NN_BRUTE, 0, p, kPlSums);
+  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
+                scratch_bytes, p.bytes);
+  const FitArgs a = al_args(p, scratch, moved, start, target, index, dist2, n, nt, nscene, max_dist2, normals);
+  al_launch_map(a, (hipStream_t)stream);
+  al_launch_fit<PlaneFit>(a, flags, transform, history_row, nullptr, (hipStream_t)stream);
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
+extern "C" int mvd_plane_icp(const float* source, const int* source_start, const float* target, const int* target_start, const float* normals,
+                             size_t nq, size_t nt, int nscene, int method, int grid, int iters, float max_dist2, double* transform,
+                             double* history, float* moved, int* index, float* dist2, void* scratch, size_t scratch_bytes,
+                             mvd_stream_t stream) {
+  const char* fn = "mvd_plane_icp";
+  MVD_CHECK_ARG(method >= MVD_NN_AUTO && method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, method);
+  MVD_CHECK_ARG(grid >= 0 && grid <= 256, "%s: grid=%d outside [0, 256]", fn, grid);
+  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
+  MVD_CHECK_ARG(iters >= 0 && iters <= MVD_ALIGN_MAX_ITERS, "%s: iters=%d outside [0, %d]", fn, iters, MVD_ALIGN_MAX_ITERS);
+  MVD_CHECK_ARG(nq <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: nq=%zu, nt=%zu beyond 2^31 - 1", fn, nq, nt);
+  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
+  MVD_CHECK_ARG(source_start && target_start, "%s: null source_start or target_start", fn);
+  MVD_CHECK_ARG(transform && history && al_aligned(transform, 8) && al_aligned(history, 8), "%s: null or misaligned transform or history", fn);
+  MVD_CHECK_ARG((source && moved && index && dist2) || nq == 0, "%s: null source, moved, index or dist2 with nq=%zu", fn, nq);
+  MVD_CHECK_ARG((target && normals) || nt == 0, "%s: null target or normals with nt=%zu", fn, nt);
+  AlignPlan p;
+  MVD_CHECK_ARG(al_plan(nq, nt, nscene, method, grid, p, kPlSums), "%s: nscene * grid^3 cells beyond 2^31 - 1 (nscene=%d, grid=%d)", fn, nscene, grid);
+  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
+                scratch_bytes, p.bytes);
+  const hipStream_t st = (hipStream_t)stream;
+  void* nn = p.nn_bytes ? (void*)((char*)scratch + p.off_nn) : nullptr;
+  const FitArgs a = al_args(p, scratch, moved, source_start, target, index, dist2, nq, nt, nscene, max_dist2, normals);
+  int rc = mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, p.nn_bytes,
+                                     MVD_NN_BUILD, stream);
+  if (rc == 0) al_launch_map(a, st);
+  const size_t row = (size_t)nscene * MVD_PLANE_HISTORY;
+  for (int k = 0; k <= iters && rc == 0; ++k) {      // row k: the pairs under the transform before step k; the last row has no step
+    al_launch_apply(source, source_start, nq, nscene, transform, moved, st);
+    rc = mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, p.nn_bytes,
+                                   MVD_NN_QUERY, stream);
+    if (rc != 0) break;
+    al_launch_fit<PlaneFit>(a, k < iters ? 0 : MVD_PLANE_NO_STEP, transform, history + (size_t)k * row, nullptr, st);
   }
   if (rc != 0) {
     char why[400];

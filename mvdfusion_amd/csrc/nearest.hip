@@ -11,6 +11,10 @@
 // range of records, until the best distance lies below the lower bound of everything unvisited.
 // The per-element pieces (nn_scene_grid, nn_cell, nn_query_grid, nn_find_scene) are host-and-device functions, so that the search can
 // be run serially on a CPU against the brute force.
+// K NEAREST (mvd_knn_points): the same two searches with another thing kept per query.  The shell walk (nn_walk_grid) and the brute
+// scan (nn_brute_scan) are templates over what they keep: NNOne, the single best of mvd_nearest_points, or NNList<K>, the K best in
+// ascending (d2, j) order.  K is a compile-time size (1, 2, 4, 8, 16, 32: the smallest that holds k) and the insertion is unrolled, so
+// the list stays in registers: a runtime-indexed array would go to scratch memory.  Resource usage of the two K = 32 kernels and why not LDS: DESIGN.md section 6.00000000000000000.
 //
 // Not tried: sorting the queries by cell, one wavefront per query cell, a hashed grid.
 #include "fusion_common.hpp"
@@ -46,6 +50,7 @@ struct NNArgs {
   unsigned* blocks;                                   // one word per chunk, and the total behind them
   long long nq, nt;
   int nscene, g;
+  int k;                                              // mvd_knn_points: neighbours per query (index, dist2 are (nq, k)); unused by the others
 };
 
 // fp32 -> unsigned that orders like the value (-inf lowest; NaNs at the two ends, and no NaN is ever encoded here)
@@ -96,6 +101,47 @@ NN_HD float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
 NN_HD void nn_take(float d2, int j, float& best, int& bestj) {
   if (d2 < best || (d2 == best && j < bestj)) best = d2, bestj = j;      // (bestj = -1 with best = +inf: an infinite d2 never wins)
 }
+// the same comparison as a predicate: candidate (d2, j) comes before entry (e2, ej) in the order of the header
+NN_HD bool nn_before(float d2, int j, float e2, int ej) { return d2 < e2 || (d2 == e2 && j < ej); }
+
+// What a search keeps per query.  take() offers a candidate; worst() is the distance the shell walk holds against its bound.
+struct NNOne {
+  float best = INFINITY;
+  int bestj = -1;
+  NN_HD void take(float d2, int j) { nn_take(d2, j, best, bestj); }
+  NN_HD float worst() const { return best; }
+};
+// The k best in ascending (d2, j) order in the LAST k of K slots, empty slots (+inf, -1) behind the ones found.  The K - k slots in
+// front hold (-inf, -1), which no candidate comes before, so the last slot is always the k-th best and nothing depends on k but the
+// initial fill and the final write.  Every loop has a compile-time trip count and every subscript is a constant after unrolling (picking
+// slot k - 1 with a chain of selects instead is turned back into a runtime subscript by the compiler, and the list leaves the registers).
+template <int K>
+struct NNList {
+  float d[K];
+  int j[K];
+  NN_HD explicit NNList(int k) {
+#pragma unroll
+    for (int s = 0; s < K; ++s) d[s] = s < K - k ? -INFINITY : INFINITY, j[s] = -1;
+  }
+  NN_HD void take(float d2, int id) {
+    if (!nn_before(d2, id, d[K - 1], j[K - 1])) return;      // (an infinite or NaN d2 comes before nothing)
+    bool here = true;                                        // the candidate comes before the old entry s
+#pragma unroll
+    for (int s = K - 1; s >= 1; --s) {
+      const bool below = nn_before(d2, id, d[s - 1], j[s - 1]);      // ... and before s - 1 too: that entry moves up to s
+      d[s] = below ? d[s - 1] : (here ? d2 : d[s]);
+      j[s] = below ? j[s - 1] : (here ? id : j[s]);
+      here = below;
+    }
+    if (here) d[0] = d2, j[0] = id;
+  }
+  NN_HD float worst() const { return d[K - 1]; }      // the k-th best so far, +inf with fewer than k
+  NN_HD void write(const NNArgs& a, long long i, int k) const {
+#pragma unroll
+    for (int s = 0; s < K; ++s)
+      if (s >= K - k) a.index[i * k + (s - (K - k))] = j[s], a.dist2[i * k + (s - (K - k))] = d[s];
+  }
+};
 
 // A scene's grid from its box: cubic cells of side h, n[a] cells along axis a.  ok is false for a scene without a finite target.
 struct SceneGrid {
@@ -129,20 +175,20 @@ NN_HD long long nn_cell_of(const SceneGrid& G, float x, float y, float z) {
 }
 
 // The records of the cells [ca, cb] of scene s (local ids, ca <= cb: consecutive cells own consecutive records) against the query.
+template <class Keep>
 NN_HD void nn_visit(const NNArgs& a, long long scene_cell0, long long ca, long long cb, long long t0, long long t1, float qx, float qy, float qz,
-                    float& best, int& bestj) {
+                    Keep& keep) {
   const long long first = scene_cell0 + ca, last = scene_cell0 + cb;
   const long long begin = nn_clamp(first > 0 ? (long long)a.cells[first - 1] : 0ll, a.nt), end = nn_clamp((long long)a.cells[last], a.nt);
   for (long long k = begin; k < end; ++k) {
     const Rec r = a.sorted[k];
-    if (r.id >= t0 && r.id < t1) nn_take(nn_d2(qx, qy, qz, r.x, r.y, r.z), r.id, best, bestj);
+    if (r.id >= t0 && r.id < t1) keep.take(nn_d2(qx, qy, qz, r.x, r.y, r.z), r.id);
   }
 }
 
-// One query against the built grid.  Writes index[i] and dist2[i].
-NN_HD void nn_query_grid(const NNArgs& a, long long i) {
-  float best = INFINITY;
-  int bestj = -1;
+// One query against the built grid: every candidate that can still matter is offered to `keep`.
+template <class Keep>
+NN_HD void nn_walk_grid(const NNArgs& a, long long i, Keep& keep) {
   const int s = nn_find_scene(a.qstart, a.nscene, a.nq, i);
   if (s >= 0) {
     const long long t0 = nn_clamp(a.tstart[s], a.nt), t1 = nn_clamp(a.tstart[s + 1], a.nt);
@@ -167,11 +213,13 @@ NN_HD void nn_query_grid(const NNArgs& a, long long i) {
         for (int z = z0; z <= z1; ++z)
           for (int y = y0; y <= y1; ++y) {
             const long long row = ((long long)z * G.n[1] + y) * G.n[0];
-            if (z - c[2] == r || c[2] - z == r || y - c[1] == r || c[1] - y == r) {
-              nn_visit(a, cell0, row + xa, row + xb, t0, t1, q[0], q[1], q[2], best, bestj);      // a face of the shell: the whole row
-            } else {                                                                              // inside: the row's two ends
-              if (c[0] - r >= 0) nn_visit(a, cell0, row + c[0] - r, row + c[0] - r, t0, t1, q[0], q[1], q[2], best, bestj);
-              if (c[0] + r < G.n[0]) nn_visit(a, cell0, row + c[0] + r, row + c[0] + r, t0, t1, q[0], q[1], q[2], best, bestj);
+            // a face of the shell: the whole row, one range; inside (r >= 1): the row's two ends.  One visit site for both, so that
+            // what `keep` unrolls is compiled once.
+            const bool face = z - c[2] == r || c[2] - z == r || y - c[1] == r || c[1] - y == r;
+            for (int part = 0; part < (face ? 1 : 2); ++part) {
+              const int x = part == 0 ? c[0] - r : c[0] + r;
+              if (!face && (x < 0 || x >= G.n[0])) continue;
+              nn_visit(a, cell0, row + (face ? xa : x), row + (face ? xb : x), t0, t1, q[0], q[1], q[2], keep);
             }
           }
         // a lower bound of d2 to any point of an unvisited cell: such a cell lies beyond a face of the visited block along some axis
@@ -191,19 +239,24 @@ NN_HD void nn_query_grid(const NNArgs& a, long long i) {
             left = true;
           }
         }
-        if (!left || best < bound * 0.999f) break;
+        if (!left || keep.worst() < bound * 0.999f) break;
       }
     }
   }
-  a.index[i] = bestj;
-  a.dist2[i] = best;
+}
+
+// One query against the built grid.  Writes index[i] and dist2[i].
+NN_HD void nn_query_grid(const NNArgs& a, long long i) {
+  NNOne one;
+  nn_walk_grid(a, i, one);
+  a.index[i] = one.bestj;
+  a.dist2[i] = one.best;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
-__global__ __launch_bounds__(kNNThreads) void brute_kernel(NNArgs a) {
-  __shared__ Rec tile[kTile];
-  __shared__ int span[2];
-  const long long i = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+// The brute scan of one workgroup: thread t's query (row i, dead past nq) against every target of its scene, offered to `keep`.
+template <class Keep>
+__device__ __forceinline__ void nn_brute_scan(const NNArgs& a, Rec* tile, int* span, long long i, Keep& keep) {
   const bool live = i < a.nq;
   const int s = live ? nn_find_scene(a.qstart, a.nscene, a.nq, i) : -1;
   if (threadIdx.x == 0) span[0] = a.nscene, span[1] = -1;
@@ -211,8 +264,7 @@ __global__ __launch_bounds__(kNNThreads) void brute_kernel(NNArgs a) {
   if (s >= 0) atomicMin(&span[0], s), atomicMax(&span[1], s);
   __syncthreads();
   const int s_lo = span[0], s_hi = span[1];      // (uniform: the scenes this workgroup's queries belong to)
-  float qx = 0.f, qy = 0.f, qz = 0.f, best = INFINITY;
-  int bestj = -1;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
   if (live) qx = a.query[i * 3 + 0], qy = a.query[i * 3 + 1], qz = a.query[i * 3 + 2];
   for (int sc = s_lo; sc <= s_hi; ++sc) {
     const long long t0 = nn_clamp(a.tstart[sc], a.nt), t1 = nn_clamp(a.tstart[sc + 1], a.nt);
@@ -227,11 +279,29 @@ __global__ __launch_bounds__(kNNThreads) void brute_kernel(NNArgs a) {
       if (s == sc)
         for (int k = 0; k < m; ++k) {
           const Rec r = tile[k];
-          nn_take(nn_d2(qx, qy, qz, r.x, r.y, r.z), r.id, best, bestj);
+          keep.take(nn_d2(qx, qy, qz, r.x, r.y, r.z), r.id);
         }
     }
   }
-  if (live) a.index[i] = bestj, a.dist2[i] = best;
+}
+
+__global__ __launch_bounds__(kNNThreads) void brute_kernel(NNArgs a) {
+  __shared__ Rec tile[kTile];
+  __shared__ int span[2];
+  const long long i = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+  NNOne one;
+  nn_brute_scan(a, tile, span, i, one);
+  if (i < a.nq) a.index[i] = one.bestj, a.dist2[i] = one.best;
+}
+
+template <int K>
+__global__ __launch_bounds__(kNNThreads) void knn_brute_kernel(NNArgs a) {
+  __shared__ Rec tile[kTile];
+  __shared__ int span[2];
+  const long long i = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+  NNList<K> list(a.k);
+  nn_brute_scan(a, tile, span, i, list);
+  if (i < a.nq) list.write(a, i, a.k);
 }
 
 // keys only decrease: a stale read costs an unnecessary atomic, never a wrong result (fusion.hip: splat_kernel)
@@ -340,6 +410,15 @@ __global__ __launch_bounds__(kNNThreads) void grid_query_kernel(NNArgs a) {
   if (i < a.nq) nn_query_grid(a, i);
 }
 
+template <int K>
+__global__ __launch_bounds__(kNNThreads) void knn_grid_kernel(NNArgs a) {
+  const long long i = (long long)blockIdx.x * kNNThreads + threadIdx.x;
+  if (i >= a.nq) return;
+  NNList<K> list(a.k);
+  nn_walk_grid(a, i, list);
+  list.write(a, i, a.k);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
 struct NNPlan {
   int method, g;              // resolved: MVD_NN_BRUTE or MVD_NN_GRID; cells per axis
@@ -380,10 +459,12 @@ extern "C" size_t mvd_nearest_points_scratch(size_t nt, int nscene, int method, 
   return nn_plan(nt, nscene, method, grid, p) ? p.bytes : 0;
 }
 
-extern "C" int mvd_nearest_points_stages(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,
-                                         size_t nt, int nscene, int method, int grid, int* index, float* dist2, void* scratch,
-                                         size_t scratch_bytes, int stages, mvd_stream_t stream) {
-  const char* fn = stages == MVD_NN_ALL ? "mvd_nearest_points" : "mvd_nearest_points_stages";
+namespace {
+
+// The argument checks the two searches share, the plan and the kernel arguments.  Non-zero: refused, with the reason set.
+static int nn_prepare(const char* fn, const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,
+                      size_t nt, int nscene, int method, int grid, int* index, float* dist2, void* scratch, size_t scratch_bytes, int stages,
+                      NNPlan& p, NNArgs& a) {
   MVD_CHECK_ARG(stages >= 1 && stages <= MVD_NN_ALL, "%s: stages=%d outside [1, %d]", fn, stages, MVD_NN_ALL);
   MVD_CHECK_ARG(method >= MVD_NN_AUTO && method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, method);
   MVD_CHECK_ARG(grid >= 0 && grid <= kMaxGrid, "%s: grid=%d outside [0, %d]", fn, grid, kMaxGrid);
@@ -392,36 +473,99 @@ extern "C" int mvd_nearest_points_stages(const float* query, const int* query_st
   MVD_CHECK_ARG(query_start && target_start, "%s: null query_start or target_start", fn);
   MVD_CHECK_ARG((query && index && dist2) || nq == 0, "%s: null query, index or dist2 with nq=%zu", fn, nq);
   MVD_CHECK_ARG(target || nt == 0, "%s: null target with nt=%zu", fn, nt);
-  NNPlan p;
   MVD_CHECK_ARG(nn_plan(nt, nscene, method, grid, p), "%s: nscene * grid^3 cells beyond 2^31 - 1 (nscene=%d, grid=%d)", fn, nscene, grid);
   MVD_CHECK_ARG(p.bytes == 0 || (scratch && scratch_bytes >= p.bytes && ((uintptr_t)scratch & 15) == 0),
                 "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn, scratch_bytes, p.bytes);
   char* base = (char*)scratch;
-  NNArgs a{query, target, query_start, target_start, index, dist2, nullptr, nullptr, nullptr, nullptr, (long long)nq, (long long)nt, nscene, p.g};
-  const hipStream_t st = (hipStream_t)stream;
+  a = NNArgs{query, target, query_start, target_start, index, dist2, nullptr, nullptr, nullptr, nullptr, (long long)nq, (long long)nt, nscene, p.g, 0};
   if (p.method == MVD_NN_GRID) {
     a.sorted = (Rec*)base;
     a.box = (unsigned*)(base + p.off_box);
     a.cells = (unsigned*)(base + p.off_cells);
     a.blocks = (unsigned*)(base + p.off_blocks);
-    if (stages & MVD_NN_BUILD) {
-      hipError_t e = hipMemsetAsync(a.box, 0xff, (size_t)nscene * 6 * sizeof(unsigned), st);
-      if (e == hipSuccess) e = hipMemsetAsync(a.cells, 0, p.chunks * kChunk * sizeof(unsigned), st);
-      MVD_CHECK_ARG(e == hipSuccess, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
-      const dim3 per_target(cdiv((long)nt, kNNThreads)), threads(kNNThreads);
-      hipLaunchKernelGGL(box_kernel, per_target, threads, 0, st, a);
-      hipLaunchKernelGGL(cell_kernel<0>, per_target, threads, 0, st, a);
-      hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)p.chunks), threads, 0, st, a.cells, a.blocks);
-      hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kCompactThreads), 0, st, a.blocks, (unsigned)p.chunks, a.blocks + p.chunks);
-      hipLaunchKernelGGL(chunk_scan_kernel, dim3((unsigned)p.chunks), threads, 0, st, a.cells, a.blocks);
-      hipLaunchKernelGGL(cell_kernel<1>, per_target, threads, 0, st, a);
-    }
+  }
+  return 0;
+}
+
+// MVD_NN_BUILD of MVD_NN_GRID: box, count, scan, scatter
+static int nn_build(const char* fn, const NNArgs& a, const NNPlan& p, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(a.box, 0xff, (size_t)a.nscene * 6 * sizeof(unsigned), st);
+  if (e == hipSuccess) e = hipMemsetAsync(a.cells, 0, p.chunks * kChunk * sizeof(unsigned), st);
+  MVD_CHECK_ARG(e == hipSuccess, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
+  const dim3 per_target(cdiv((long)a.nt, kNNThreads)), threads(kNNThreads);
+  hipLaunchKernelGGL(box_kernel, per_target, threads, 0, st, a);
+  hipLaunchKernelGGL(cell_kernel<0>, per_target, threads, 0, st, a);
+  hipLaunchKernelGGL(chunk_sum_kernel, dim3((unsigned)p.chunks), threads, 0, st, a.cells, a.blocks);
+  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(kCompactThreads), 0, st, a.blocks, (unsigned)p.chunks, a.blocks + p.chunks);
+  hipLaunchKernelGGL(chunk_scan_kernel, dim3((unsigned)p.chunks), threads, 0, st, a.cells, a.blocks);
+  hipLaunchKernelGGL(cell_kernel<1>, per_target, threads, 0, st, a);
+  return 0;
+}
+
+template <int K>
+static void knn_launch(bool grid, const NNArgs& a, hipStream_t st) {
+  const dim3 blocks(cdiv((long)a.nq, kNNThreads)), threads(kNNThreads);
+  if (grid) hipLaunchKernelGGL(knn_grid_kernel<K>, blocks, threads, 0, st, a);
+  else hipLaunchKernelGGL(knn_brute_kernel<K>, blocks, threads, 0, st, a);
+}
+
+}  // namespace
+
+extern "C" int mvd_nearest_points_stages(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,
+                                         size_t nt, int nscene, int method, int grid, int* index, float* dist2, void* scratch,
+                                         size_t scratch_bytes, int stages, mvd_stream_t stream) {
+  const char* fn = stages == MVD_NN_ALL ? "mvd_nearest_points" : "mvd_nearest_points_stages";
+  NNPlan p;
+  NNArgs a;
+  if (const int rc = nn_prepare(fn, query, query_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, scratch, scratch_bytes,
+                                stages, p, a))
+    return rc;
+  const hipStream_t st = (hipStream_t)stream;
+  if (p.method == MVD_NN_GRID) {
+    if (stages & MVD_NN_BUILD)
+      if (const int rc = nn_build(fn, a, p, st)) return rc;
     if ((stages & MVD_NN_QUERY) && nq > 0) hipLaunchKernelGGL(grid_query_kernel, dim3(cdiv((long)nq, kNNThreads)), dim3(kNNThreads), 0, st, a);
   } else if ((stages & MVD_NN_QUERY) && nq > 0) {
     hipLaunchKernelGGL(brute_kernel, dim3(cdiv((long)nq, kNNThreads)), dim3(kNNThreads), 0, st, a);
   }
   MVD_CHECK_LAUNCH(fn);
   return 0;
+}
+
+extern "C" int mvd_knn_points_stages(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,
+                                     size_t nt, int nscene, int k, int method, int grid, int* index, float* dist2, void* scratch,
+                                     size_t scratch_bytes, int stages, mvd_stream_t stream) {
+  const char* fn = stages == MVD_NN_ALL ? "mvd_knn_points" : "mvd_knn_points_stages";
+  MVD_CHECK_ARG(k >= 1 && k <= MVD_KNN_MAX_K, "%s: k=%d outside [1, %d]", fn, k, MVD_KNN_MAX_K);
+  const uintptr_t low = (uintptr_t)query | (uintptr_t)query_start | (uintptr_t)target | (uintptr_t)target_start | (uintptr_t)index | (uintptr_t)dist2;
+  MVD_CHECK_ARG((low & 3) == 0, "%s: a pointer that is not 4-byte aligned", fn);
+  NNPlan p;
+  NNArgs a;
+  if (const int rc = nn_prepare(fn, query, query_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, scratch, scratch_bytes,
+                                stages, p, a))
+    return rc;
+  a.k = k;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool grid_method = p.method == MVD_NN_GRID;
+  if (grid_method && (stages & MVD_NN_BUILD))
+    if (const int rc = nn_build(fn, a, p, st)) return rc;
+  if ((stages & MVD_NN_QUERY) && nq > 0) {
+    if (k == 1) knn_launch<1>(grid_method, a, st);
+    else if (k == 2) knn_launch<2>(grid_method, a, st);
+    else if (k <= 4) knn_launch<4>(grid_method, a, st);
+    else if (k <= 8) knn_launch<8>(grid_method, a, st);
+    else if (k <= 16) knn_launch<16>(grid_method, a, st);
+    else knn_launch<32>(grid_method, a, st);
+  }
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
+extern "C" int mvd_knn_points(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq, size_t nt,
+                              int nscene, int k, int method, int grid, int* index, float* dist2, void* scratch, size_t scratch_bytes,
+                              mvd_stream_t stream) {
+  return mvd_knn_points_stages(query, query_start, target, target_start, nq, nt, nscene, k, method, grid, index, dist2, scratch, scratch_bytes,
+                               MVD_NN_ALL, stream);
 }
 
 extern "C" int mvd_nearest_points(const float* query, const int* query_start, const float* target, const int* target_start, size_t nq,

@@ -24,11 +24,18 @@ accuracy, completeness, Chamfer distance and precision / recall / F-score per sc
 deterministic surface samples both take.  ``nearest_points`` synchronises nothing; ``compare_geometry`` reads the scene offsets once.
 Nothing of the model is bound here, so there is no ``ViewFusion`` method.
 
+``knn_points`` is the same search returning the k nearest instead of one (include/mvd_hip.h: mvd_knn_points), in ascending (distance,
+row) order, and ``estimate_normals`` turns such neighbour lists into a unit normal and a surface variation per point
+(mvd_point_normals: centre, covariance and a 3 x 3 Jacobi in fp64).  ``sample_normals`` gives surface samples the exact normals of
+their faces; ``write_ply`` saves normals with a cloud.  None of them synchronises.
+
 ``align_geometry`` puts two geometries into one frame first (include/mvd_hip.h: mvd_align_icp): point-to-point ICP on that search, the
 target's grid built once, every iteration an apply, a query, a deterministic reduction of the matched pairs to moment sums and a
 closed-form similarity solve, all enqueued without a host synchronisation.  ``fit_similarity`` is the closed form alone for known
 pairs; both return an ``Alignment`` whose ``apply`` moves a cloud, surface samples or a mesh, so that
 ``compare_geometry(al.apply(cloud), scan)`` measures the reconstruction and not the misalignment.  No ``ViewFusion`` method either.
+``align_to_surface`` is the point-to-plane form of that loop (mvd_plane_icp) on the normals of the target -- what converges on a dense
+smooth surface, where point-to-point slides -- and ``fit_plane_step`` its one linearised step for known pairs.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -736,6 +743,154 @@ def nearest_points(query, target, scenes=1, method="auto", grid=None):
 
 
 @dataclass
+class NeighbourPoints:
+    """What ``knn_points`` returns, per query point: its k nearest targets in ascending (dist2, row) order."""
+    index: torch.Tensor                      # (nq, k) int32: rows of the target, -1 in the slots behind the last neighbour found
+    dist2: torch.Tensor                      # (nq, k) fp32: their squared distances, +inf in those slots
+
+    @property
+    def dist(self):
+        return torch.sqrt(self.dist2)
+
+    @property
+    def hit(self):
+        return self.index >= 0
+
+    @property
+    def count(self):
+        """(nq,) int64: the filled slots of every row."""
+        return (self.index >= 0).sum(dim=1)
+
+
+def _knn(query, query_start, target, target_start, N, k, method, grid):
+    """The enqueues of mvd_knn_points: ``_nearest`` with (nq, k) outputs.  No host synchronisation."""
+    L = hip.lib()
+    dev, nq, nt = query.device, int(query.shape[0]), int(target.shape[0])
+    hip._req(query), hip._req(target), hip._req(query_start, torch.int32), hip._req(target_start, torch.int32)
+    index = torch.empty(nq, k, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(nq, k, dtype=torch.float32, device=dev)
+    nbytes = int(L.mvd_nearest_points_scratch(nt, N, method, grid))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_knn_points(p(query), hip.ptr(query_start), p(target), hip.ptr(target_start), nq, nt, N, k, method, grid, p(index),
+                               p(dist2), p(scratch), nbytes, hip.stream()))
+    return index, dist2
+
+
+def _check_k(k, most, what):
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= most:
+        raise ValueError(f"k = {k}: an integer in [1, {most}] ({what})")
+    return int(k)
+
+
+def knn_points(query, target, k, scenes=1, method="auto", grid=None):
+    """For every point of ``query`` its ``k`` nearest points of ``target`` (include/mvd_hip.h: mvd_knn_points has the rule)
+    -> NeighbourPoints.
+
+    query, target, scenes, method, grid : those of ``nearest_points``, with the same checks.
+    k       : 1 .. hip.KNN_MAX_K neighbours per query.  k = 1 gives the bits of ``nearest_points`` (as (nq, 1) tensors).
+    A row holds the candidates in ascending order of (squared distance in fp32, target row) -- the same bits for every method and from
+    run to run -- and -1 / +inf behind the last one when the query's scene holds fewer than k finite targets.
+    ``query`` may be ``target``: a point is then its own neighbour at distance 0 and STAYS in its list (slot 0, unless a coincident
+    point of a lower row comes first).  There is no exclude flag; ask for k + 1 and drop the first column where that is wanted.
+    Nothing is read back from the device."""
+    N, method, grid = _check_nn(scenes, method, grid)
+    k = _check_k(k, hip.KNN_MAX_K, "hip.KNN_MAX_K")
+    q, q_scene = _points_of(query, "query", N)
+    t, t_scene = _points_of(target, "target", N)
+    dev = q.device
+    q, t = q.float().contiguous(), t.to(dev, torch.float32).contiguous()
+    index, dist2 = _knn(q, _scene_start(q_scene, int(q.shape[0]), N, dev), t, _scene_start(t_scene, int(t.shape[0]), N, dev), N, k, method, grid)
+    return NeighbourPoints(index=index, dist2=dist2)
+
+
+NORMALS_K = 16                               # estimate_normals' default neighbourhood (an INTERFACE default, see its docstring)
+
+
+@dataclass
+class PointNormals:
+    """What ``estimate_normals`` returns, per point."""
+    normal: torch.Tensor                     # (n, 3) fp32 unit normals; (0, 0, 0) where the point is not valid
+    variation: torch.Tensor                  # (n,) fp32: l0 / (l0 + l1 + l2) of the neighbourhood's covariance, 0 on a plane; NaN where not valid
+    valid: torch.Tensor                      # (n,) bool: at least three usable neighbours, neither coincident nor collinear
+    neighbours: NeighbourPoints              # the lists the normals were formed from
+
+
+def _normals(target, index, points, toward):
+    """The enqueue of mvd_point_normals.  target (nt, 3) fp32, index (n, k) int32, points / toward (n, 3) fp32 or None, contiguous on
+    one GPU.  Returns (normal (n, 3), variation (n,)).  No host synchronisation."""
+    L = hip.lib()
+    n, k = int(index.shape[0]), int(index.shape[1])
+    hip._req(target), hip._req(index, torch.int32)
+    if toward is not None:
+        hip._req(points), hip._req(toward)
+    normal = torch.empty(n, 3, dtype=torch.float32, device=target.device)
+    variation = torch.empty(n, dtype=torch.float32, device=target.device)
+    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
+    hip.check(L.mvd_point_normals(p(target), int(target.shape[0]), p(index), n, k, p(points) if toward is not None else None, p(toward), p(normal),
+                                  p(variation), hip.stream()))
+    return normal, variation
+
+
+def estimate_normals(points, k=NORMALS_K, scenes=1, toward=None, neighbours=None, method="auto", grid=None):
+    """A unit normal per point of a cloud from its ``k`` nearest neighbours within the cloud (include/mvd_hip.h: mvd_point_normals has
+    the rule) -> PointNormals.
+
+    points  : what ``nearest_points`` takes.  Every point's neighbourhood is ``knn_points(points, points, k)``: the point itself and
+              its k - 1 nearest others of its scene.
+    k       : 3 .. hip.KNN_MAX_K.  The default 16 is an interface default that nobody has tuned: small k follows noise, large k rounds
+              edges off; choose it for the data.
+    toward  : None -- the sign makes the component of largest magnitude positive (between equal magnitudes the lowest axis), which is
+              deterministic and means nothing; or an (N, 3) viewpoint per scene, or an (n, 3) tensor with a viewpoint per point -- the
+              normal then faces it (normal . (toward - point) >= 0).  With n == N rows the tensor is read per scene.  There is no
+              orientation propagation across the cloud.
+    neighbours : a NeighbourPoints of ``points`` against itself to reuse (any k up to hip.NORMALS_MAX_K columns); k, method and grid
+              are then unused.
+    The normal is the eigenvector of the smallest eigenvalue of the neighbourhood's covariance, all in fp64, rounded to fp32 once;
+    ``variation`` is that eigenvalue over the sum of the three.  A point with fewer than three usable neighbours, or whose neighbours
+    coincide or are collinear, is not ``valid``: zero normal, NaN variation.  Nothing is read back from the device."""
+    N, method, grid = _check_nn(scenes, method, grid)
+    x, scene = _points_of(points, "points", N)
+    dev, n = x.device, int(x.shape[0])
+    x = x.float().contiguous()
+    if toward is not None and (not torch.is_tensor(toward) or toward.dim() != 2 or toward.shape[1] != 3 or int(toward.shape[0]) not in (N, n)):
+        raise ValueError(f"toward: None, an (N = {N}, 3) or an (n = {n}, 3) tensor")
+    if neighbours is None:
+        k = _check_k(k, hip.KNN_MAX_K, "hip.KNN_MAX_K")
+        if k < 3:
+            raise ValueError(f"k = {k}: a normal needs at least 3 neighbours")
+        start = _scene_start(scene, n, N, dev)
+        neighbours = NeighbourPoints(*_knn(x, start, x, start, N, k, method, grid))
+    elif not isinstance(neighbours, NeighbourPoints) or neighbours.index.dim() != 2 or int(neighbours.index.shape[0]) != n or \
+            not 1 <= int(neighbours.index.shape[1]) <= hip.NORMALS_MAX_K or neighbours.index.dtype != torch.int32:
+        raise ValueError(f"neighbours: a NeighbourPoints with an (n = {n}, k <= {hip.NORMALS_MAX_K}) int32 index")
+    if toward is not None:
+        toward = toward.to(dev, torch.float32)
+        if int(toward.shape[0]) == N:
+            toward = toward[scene.to(dev).long()] if scene is not None else toward[:1].expand(n, 3)
+        toward = toward.contiguous()
+    normal, variation = _normals(x, neighbours.index.to(dev).contiguous(), x, toward)
+    return PointNormals(normal=normal, variation=variation, valid=~torch.isnan(variation), neighbours=neighbours)
+
+
+def sample_normals(mesh, samples):
+    """(n, 3) fp32 unit normals of the faces the ``samples`` of ``sample_mesh(mesh, n)`` lie in (``samples.face``): the cross product
+    (v1 - v0) x (v2 - v0) in float64 torch ops, divided by its length, so the winding of the mesh decides the side; zero for a face of
+    zero or non-finite area.  A mesh target gets exact normals this way, without a search."""
+    if not isinstance(mesh, TriangleMesh) or not isinstance(samples, SurfaceSamples):
+        raise ValueError("sample_normals(mesh, samples): a TriangleMesh and the SurfaceSamples of sample_mesh")
+    face = samples.face.long()
+    nf = int(mesh.faces.shape[0])
+    if face.numel() and face.device.type == "cpu" and not 0 <= int(face.min()) <= int(face.max()) < nf:
+        raise ValueError(f"samples.face: rows {int(face.min())} .. {int(face.max())} of a mesh with {nf} faces")
+    tri = mesh.vertices.double()[mesh.faces.long()[face.to(mesh.faces.device)]]          # (n, 3 vertices, 3)
+    cross = torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    length = cross.norm(dim=1, keepdim=True)
+    ok = (length > 0) & torch.isfinite(length)
+    return torch.where(ok, cross / torch.where(ok, length, torch.ones_like(length)), torch.zeros_like(cross)).float()
+
+
+@dataclass
 class GeometryDistance:
     """What ``compare_geometry`` returns.  The metrics are (N,) float64 tensors, one value per scene, NaN for a scene with an empty side."""
     a_to_b: NearestPoints                    # for every point of a its nearest point of b
@@ -1061,19 +1216,186 @@ def align_geometry(source, target, scenes=1, iters=ALIGN_ITERS, scale=False, max
     return _alignment(transform, scale0 * history[-1, :, 2], history, moved, index, dist2)
 
 
-def write_ply(path, cloud):
+def _plane_fit(moved, start, target, normals, index, N, flags, max_d2, transform):
+    """The enqueues of mvd_plane_fit: ``_align_fit`` with the target's normals (nt, 3) fp32.  transform (N, 12) float64 is composed in
+    place unless flags has hip.PLANE_NO_STEP.  Returns the history row (N, 4) float64."""
+    L = hip.lib()
+    dev, n, nt = moved.device, int(moved.shape[0]), int(target.shape[0])
+    hip._req(moved), hip._req(target), hip._req(normals), hip._req(start, torch.int32), hip._req(transform, torch.float64)
+    if index is not None:
+        hip._req(index, torch.int32)
+    row = torch.empty(N, hip.PLANE_HISTORY, dtype=torch.float64, device=dev)
+    nbytes = int(L.mvd_plane_scratch(n, 0, N, hip.NN_BRUTE, 0))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
+    hip.check(L.mvd_plane_fit(p(moved), hip.ptr(start), p(target), p(normals), p(index), None, n, nt, N, flags, max_d2, hip.ptr(transform),
+                              hip.ptr(row), hip.ptr(scratch), nbytes, hip.stream()))
+    return row
+
+
+def _plane_icp(source, source_start, target, target_start, normals, N, method, grid, iters, max_d2, transform):
+    """The enqueues of mvd_plane_icp.  transform (N, 12) float64 holds the start and is overwritten with the result.  Returns
+    (history (iters + 1, N, 4) float64, moved (n, 3) fp32, index (n,) int32, dist2 (n,) fp32).  No host synchronisation."""
+    L = hip.lib()
+    dev, nq, nt = source.device, int(source.shape[0]), int(target.shape[0])
+    hip._req(source), hip._req(target), hip._req(normals), hip._req(source_start, torch.int32), hip._req(target_start, torch.int32)
+    hip._req(transform, torch.float64)
+    history = torch.empty(iters + 1, N, hip.PLANE_HISTORY, dtype=torch.float64, device=dev)
+    moved = torch.empty_like(source)
+    index = torch.empty(nq, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
+    nbytes = int(L.mvd_plane_scratch(nq, nt, N, method, grid))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_plane_icp(p(source), hip.ptr(source_start), p(target), hip.ptr(target_start), p(normals), nq, nt, N, method, grid, iters,
+                              max_d2, hip.ptr(transform), hip.ptr(history), p(moved), p(index), p(dist2), hip.ptr(scratch), nbytes, hip.stream()))
+    return history, moved, index, dist2
+
+
+@dataclass
+class PlaneAlignment(Alignment):
+    """What ``fit_plane_step`` and ``align_to_surface`` return: an ``Alignment`` -- ``apply`` and everything that takes one work
+    unchanged -- whose ``rms`` is the POINT rms of the accepted pairs, so that it compares with ``align_geometry``'s, plus the two rows
+    of the point-to-plane fit."""
+    plane_rms: torch.Tensor = None           # (iters + 1, N) float64: RMS distance of the accepted pairs ALONG the target's normals
+    rank: torch.Tensor = None                # (iters + 1, N) int64: the directions (of 6) the solve of that row's pairs keeps; 0: no step
+
+
+def _plane_alignment(transform, scale, history, xyz, index, dist2):
+    base = _alignment(transform, scale, history[:, :, [2, 1, 0]], xyz, index, dist2)
+    return PlaneAlignment(**{f: getattr(base, f) for f in ("matrix", "rotation", "translation", "scale", "rms", "pairs", "xyz", "nearest")},
+                          plane_rms=history[:, :, 0].clone(), rank=history[:, :, 3].to(torch.int64))
+
+
+def _target_normals(normals, t, t_scene, N, k, method, grid, nt):
+    """(nt, 3) fp32 contiguous on the target's device from the ``normals`` argument of the two plane functions."""
+    if normals is None:
+        start = _scene_start(t_scene, nt, N, t.device)
+        index, _ = _knn(t, start, t, start, N, k, method, grid)
+        return _normals(t, index, t, None)[0]
+    if isinstance(normals, PointNormals):
+        normals = normals.normal
+    if not torch.is_tensor(normals) or tuple(normals.shape) != (nt, 3):
+        raise ValueError(f"normals: None, a PointNormals or an ({nt}, 3) tensor -- one normal per target point")
+    return normals.to(t.device, torch.float32).contiguous()
+
+
+def fit_plane_step(source, target, normals, scenes=1, pairs=None):
+    """ONE linearised point-to-plane step for KNOWN correspondences (include/mvd_hip.h: mvd_plane_fit has the rule) -> PlaneAlignment:
+    the rigid motion x -> R x + t, R = exp([omega]x), that minimises sum ((p + omega x p + t - q) . n)^2 over the pairs (p, q) with n
+    the target's normal at q.  The counterpart of ``fit_similarity``; unlike it this is a step, not a solution -- the error is
+    linearised in the rotation, so a large motion takes several.
+
+    source, target, scenes, pairs : as for ``fit_similarity`` (row i with row i, or with row pairs[i]; -1 skips).
+    normals : an (nt, 3) tensor or the PointNormals of ``estimate_normals(target)``: one normal per target row.  Their sign does not
+              matter; a zero or non-finite normal skips the pair.
+    A direction the pairs do not constrain -- sliding along a plane, turning about a sphere's centre -- is left alone (``rank`` < 6), not
+    blown up.  A scene with fewer than 3 pairs gets the identity.  ``rms``, ``plane_rms``, ``pairs`` and ``rank`` have one row: under the
+    step.  Nothing is read back from the device."""
+    N, _, _ = _check_nn(scenes, "auto", None)
+    s, s_scene = _points_of(source, "source", N)
+    t, t_scene = _points_of(target, "target", N)
+    dev, n, nt = s.device, int(s.shape[0]), int(t.shape[0])
+    if normals is None:
+        raise ValueError("normals: a PointNormals or an (nt, 3) tensor (estimate_normals(target) makes them)")
+    if pairs is None:
+        if n != nt:
+            raise ValueError(f"target: {nt} points for {n} of source -- row i goes with row i; give pairs otherwise")
+    elif not torch.is_tensor(pairs) or tuple(pairs.shape) != (n,) or pairs.dtype != torch.int32:
+        raise ValueError(f"pairs: an ({n},) int32 tensor, one target row (or -1) per source row")
+    s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
+    nrm = _target_normals(normals, t, t_scene, N, NORMALS_K, hip.NN_AUTO, 0, nt)
+    start = _scene_start(s_scene, n, N, dev)
+    index = None if pairs is None else pairs.to(dev).contiguous()
+    transform = _identity_transform(N, dev)
+    _plane_fit(s, start, t, nrm, index, N, 0, float("inf"), transform)
+    moved = _align_apply(s, start, N, transform)
+    last = _plane_fit(moved, start, t, nrm, index, N, hip.PLANE_NO_STEP, float("inf"), transform)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    j = rows if index is None else index
+    has = (j >= 0) & (j < nt) & (rows >= start[0]) & (rows < start[N])
+    d = moved - t[j.long().clamp(0, max(nt - 1, 0))] if nt else torch.full_like(moved, float("nan"))
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]          # (the search's order: every torch op rounds once)
+    has = has & (d2 < float("inf"))
+    return _plane_alignment(transform, torch.ones(N, dtype=torch.float64, device=dev), last[None], moved,
+                            torch.where(has, j, torch.full_like(j, -1)), torch.where(has, d2, torch.full_like(d2, float("inf"))))
+
+
+def align_to_surface(source, target, normals=None, k=NORMALS_K, scenes=1, iters=ALIGN_ITERS, max_distance=None, init=None, method="auto",
+                     grid=None):
+    """Point-to-plane ICP: ``align_geometry``'s loop -- the target's grid built once, every iteration an apply, an exact nearest-point
+    query and a deterministic reduction, nothing read back -- with the distance ALONG THE TARGET'S NORMAL minimised instead of the
+    distance between the points (include/mvd_hip.h: mvd_plane_icp has the rule) -> PlaneAlignment.
+
+    The division of labour: point-to-point has the larger basin -- it pulls matched points together wherever they are -- but on a dense
+    smooth surface against an independent resampling of itself it slides slowly, because the nearest sample is never the same surface
+    point.  Point-to-plane lets the source slide along the surface freely and converges there in a handful of iterations, but its
+    linearisation wants a start within a few degrees.  The recipe is both:
+        ``align_to_surface(source, target, init=align_geometry(source, target, iters=5))``.
+
+    source, target, scenes, iters, max_distance, method, grid : those of ``align_geometry``; ``iters`` and ``max_distance`` are the same
+              untuned interface defaults.
+    normals : one normal per target point: an (nt, 3) tensor, a PointNormals, or None for ``estimate_normals(target, k)`` -- whose sign
+              does not matter to the fit.  A target point without a valid normal takes no part.  For a mesh target,
+              ``sample_normals`` gives exact ones.
+    k       : the neighbourhood of those normals, unused otherwise.
+    init    : where to start: None, an Alignment (a PlaneAlignment is one), an (N, 4, 4) or (4, 4) matrix, or "centroid", as for
+              ``align_geometry``.  The fit is RIGID: a scale in ``init`` is carried through untouched, none is fitted.
+    ``rms`` is the point rms (comparable with ``align_geometry``'s), ``plane_rms`` the rms along the normals, ``rank`` the directions of
+    the six that each row's pairs constrain; rows as in ``Alignment``.  Apart from ``init="centroid"`` nothing synchronises with the
+    host."""
+    N, method, grid = _check_nn(scenes, method, grid)
+    if isinstance(iters, bool) or not isinstance(iters, (int, float)) or int(iters) != iters or not 0 <= iters <= hip.ALIGN_MAX_ITERS:
+        raise ValueError(f"iters = {iters}: an integer in [0, {hip.ALIGN_MAX_ITERS}]")
+    if max_distance is not None and not float(max_distance) >= 0:
+        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    if normals is None:
+        k = _check_k(k, hip.KNN_MAX_K, "hip.KNN_MAX_K")
+        if k < 3:
+            raise ValueError(f"k = {k}: a normal needs at least 3 neighbours")
+    s, s_scene = _points_of(source, "source", N)
+    t, t_scene = _points_of(target, "target", N)
+    dev = s.device
+    s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
+    if isinstance(init, str) and init != "centroid":
+        raise ValueError(f"init = {init!r}: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
+    s_start, t_start = _scene_start(s_scene, int(s.shape[0]), N, dev), _scene_start(t_scene, int(t.shape[0]), N, dev)
+    if init is None:
+        transform, scale0 = _identity_transform(N, dev), torch.ones(N, dtype=torch.float64, device=dev)
+    elif isinstance(init, str):
+        transform, scale0 = _centroid_init(s, s_start, t, t_start, N, False)
+    else:
+        transform, scale0 = _check_init(init, N, dev)
+        transform = transform.clone()          # (the loop writes its result there: never into the caller's init, which a view can alias)
+    nrm = _target_normals(normals, t, t_scene, N, k, method, grid, int(t.shape[0]))
+    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
+    history, moved, index, dist2 = _plane_icp(s, s_start, t, t_start, nrm, N, method, grid, int(iters), max_d2, transform)
+    return _plane_alignment(transform, scale0, history, moved, index, dist2)
+
+
+def write_ply(path, cloud, normals=None):
     """Binary little-endian PLY: float x y z per vertex, and uchar red green blue (round(255 rgb)) when the cloud has colour.  A
-    TriangleMesh is written the same way from its vertices, followed by ``element face`` with ``property list uchar int vertex_indices``."""
+    TriangleMesh is written the same way from its vertices, followed by ``element face`` with ``property list uchar int vertex_indices``.
+    ``normals`` -- an (n, 3) tensor or the PointNormals of ``estimate_normals`` -- adds float nx ny nz behind x y z; without it the file
+    is what it always was."""
     import numpy as np
     mesh = isinstance(cloud, TriangleMesh)
     pos = cloud.vertices if mesh else cloud.xyz
     n = int(pos.shape[0])
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        normals = normals.normal if isinstance(normals, PointNormals) else normals
+        if not torch.is_tensor(normals) or tuple(normals.shape) != (n, 3):
+            raise ValueError(f"normals: an ({n}, 3) tensor or a PointNormals")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if cloud.rgb is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     v = np.zeros(n, dtype=np.dtype(fields))
     xyz = pos.detach().cpu().numpy().astype("<f4")
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        nrm = normals.detach().cpu().numpy().astype("<f4")
+        v["nx"], v["ny"], v["nz"] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if cloud.rgb is not None:
         c = np.rint(np.clip(cloud.rgb.detach().cpu().numpy(), 0.0, 1.0) * 255.0).astype("u1")
         v["red"], v["green"], v["blue"] = c[:, 0], c[:, 1], c[:, 2]

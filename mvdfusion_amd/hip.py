@@ -54,9 +54,14 @@ RENDER_FILL, RENDER_SPLAT, RENDER_RESOLVE, RENDER_ALL = 1, 2, 4, 7      # stages
 NN_AUTO, NN_BRUTE, NN_GRID = 0, 1, 2                       # method of mvd_nearest_points
 NN_BUILD, NN_QUERY, NN_ALL = 1, 2, 3                       # stages of mvd_nearest_points_stages
 NN_MAX_GRID = 256                                          # the largest `grid` of mvd_nearest_points
+KNN_MAX_K = 32                                             # MVD_KNN_MAX_K: the largest k of mvd_knn_points
+NORMALS_MAX_K, NORMALS_SWEEPS = 256, 10                    # mvd_point_normals: the longest neighbour row; Jacobi sweeps of its 3 x 3 solve
 ALIGN_SCALE, ALIGN_NO_STEP = 1, 2                          # flags of mvd_align_fit (mvd_align_icp, mvd_align_solve: ALIGN_SCALE only)
 ALIGN_CHUNK = 1024                                         # MVD_ALIGN_CHUNK: the rows one workgroup of the moment sums reduces
 ALIGN_SUMS, ALIGN_HISTORY = 19, 3                          # doubles per scene: the moment sums; a history row (rms, pairs, step scale)
+PLANE_NO_STEP = 2                                          # flag of mvd_plane_fit
+PLANE_SUMS, PLANE_HISTORY = 30, 4                          # doubles per scene: the point-to-plane sums; a history row (plane rms, pairs, point rms, rank)
+PLANE_EPS_RANK = 1e-9                                      # MVD_PLANE_EPS_RANK: a direction is kept above this share of the largest eigenvalue
 ALIGN_MAX_ITERS = 1024                                     # the largest `iters` of mvd_align_icp
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -177,11 +182,18 @@ SIGNATURES = {
     "mvd_nearest_points_scratch": (_sz, [_sz, _i, _i, _i]),
     "mvd_nearest_points": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mvd_nearest_points_stages": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]),
+    "mvd_knn_points": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_knn_points_stages": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]),
+    "mvd_point_normals": (_i, [_vp, _sz, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp]),
     "mvd_align_scratch": (_sz, [_sz, _sz, _i, _i, _i]),
     "mvd_align_solve": (_i, [_vp, _i, _vp, _vp]),
     "mvd_align_apply": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _vp]),
     "mvd_align_fit": (_i, [_vp] * 5 + [_sz, _sz, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "mvd_align_icp": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _i, _i, _i, _f] + [_vp] * 6 + [_sz, _vp]),
+    "mvd_plane_scratch": (_sz, [_sz, _sz, _i, _i, _i]),
+    "mvd_plane_solve": (_i, [_vp, _vp, _vp]),
+    "mvd_plane_fit": (_i, [_vp] * 6 + [_sz, _sz, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_plane_icp": (_i, [_vp] * 5 + [_sz, _sz, _i, _i, _i, _i, _f] + [_vp] * 6 + [_sz, _vp]),
     "mvd_tsdf_integrate": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _vp]),
     "mvd_mesh_scratch": (_sz, [_i, _i]),
     "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
