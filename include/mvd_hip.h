@@ -896,6 +896,96 @@ int mvd_plane_icp(const float* source, const int* source_start, const float* tar
                   float* moved, int* index, float* dist2, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Distance to a surface: the exact closest point of a triangle mesh for every query point, and point-to-plane ICP whose target is the
+ * mesh itself (csrc/meshdist.hip, csrc/align.hip; host: mvdfusion_amd/fusion.py nearest_on_mesh, compare_geometry(exact=True),
+ * align_to_mesh).  Not in the reference either.  The distance to the nearest SAMPLE of a mesh is an upper bound with a floor of the
+ * sample spacing; this is the distance to the triangles.
+ *
+ * mvd_nearest_on_mesh:
+ *   query (nq, 3) fp32; vertices (nv, 3) fp32; faces (nf, 3) int32 GLOBAL rows of vertices; query_start, face_start: nscene + 1 int32
+ *   DEVICE values each, non-decreasing, clamped to [0, nq] or [0, nf] before they index anything.
+ *   Scenes    : those of mvd_nearest_points: query i of scene s searches the faces f with face_start[s] <= f < face_start[s + 1].
+ *   Candidates: a face whose three ids lie in [0, nv) and whose nine coordinates are finite.  A query with a non-finite coordinate, a
+ *               query of no scene, or one whose scene holds no candidate gets face = -1, dist2 = +inf, point = NaN, bary = 0,
+ *               region = -1, normal = 0.
+ *   Per pair  : fp64 throughout, on the exact conversions of the fp32 inputs, every operation rounded once (compiled without
+ *               contraction), only + - * / and comparisons.  dot(u, v) = (u_x v_x + u_y v_y) + u_z v_z; a cross product component is one
+ *               subtraction of two products (n_x = ab_y ac_z - ab_z ac_y, ...).  With p the query and A, B, C the face's vertices:
+ *                 ab = B - A, ac = C - A, n = ab x ac.  If n_x, n_y, n_z are all exactly 0 go to DEGENERATE.
+ *                 ap = p - A, d1 = dot(ab, ap), d2 = dot(ac, ap).      d1 <= 0 and d2 <= 0                : region 0, b = (1, 0, 0)
+ *                 bp = p - B, d3 = dot(ab, bp), d4 = dot(ac, bp).      d3 >= 0 and d4 <= d3               : region 1, b = (0, 1, 0)
+ *                 vc = d1 d4 - d3 d2.        vc <= 0, d1 >= 0, d3 <= 0 : region 3 (edge AB), v = d1 / (d1 - d3),     b = (1 - v, v, 0)
+ *                 cp = p - C, d5 = dot(ab, cp), d6 = dot(ac, cp).      d6 >= 0 and d5 <= d6               : region 2, b = (0, 0, 1)
+ *                 vb = d5 d2 - d1 d6.        vb <= 0, d2 >= 0, d6 <= 0 : region 5 (edge CA), w = d2 / (d2 - d6),     b = (1 - w, 0, w)
+ *                 va = d3 d6 - d5 d4, e = d4 - d3, f = d5 - d6.
+ *                                            va <= 0, e >= 0, f >= 0   : region 4 (edge BC), w = e / (e + f),        b = (0, 1 - w, w)
+ *                 den = (va + vb) + vc;      den != 0                  : region 6 (interior), v = vb / den, w = vc / den,
+ *                                                                        b = ((1 - v) - w, v, w);   den == 0: go to DEGENERATE.
+ *               The tests are made in this order and the first that holds decides (Ericson, Real-Time Collision Detection, 5.1.5).  An
+ *               edge denominator that is exactly 0 is not divided by: the parameter is 0.
+ *               DEGENERATE (collinear or coincident vertices): the three segments A -> B, B -> C, C -> A in this order, each S -> E with
+ *               se = E - S, sp = p - S, len2 = dot(se, se), t = dot(sp, se) / len2 (t = 0 when len2 == 0: the segment is its first end
+ *               point), t raised to 0 unless t > 0 and lowered to 1 where t > 1; b has 1 - t at S and t at E; region = the vertex code of S
+ *               when t == 0, of E when t == 1, else the edge code (3, 4, 5 in segment order).  The first segment stands; a later one
+ *               replaces it only with a strictly smaller d2.
+ *               Then, for every path: c_k = (b0 A_k + b1 B_k) + b2 C_k per axis k, and d2 = (dx dx + dy dy) + dz dz with d = p - c.
+ *               A numpy float64 restatement in this order gives the same bits (tests/meshdist_f64.py).
+ *   Selection : per query the minimum of (d2 in fp64, face row) in that lexicographic order, a total order: between equal d2 the lowest
+ *               row wins, and the result cannot depend on the order the faces are met in or on how often one is met.
+ *   Outputs   : each optional -- a NULL is not written; every element [0, nq) of the others is.
+ *               face (nq,) int32 the chosen row; dist2 (nq,) fp32 the fp64 d2 rounded once (+inf when it overflows fp32: the face is
+ *               still reported); point (nq, 3) fp32 c; bary (nq, 3) fp32 b; region (nq,) int32 0..2 a vertex (A, B, C), 3..5 an edge
+ *               (AB, BC, CA), 6 the interior; normal (nq, 3) fp32: the fp64 (B - A) x (C - A) divided by its length sqrt((n_x n_x +
+ *               n_y n_y) + n_z n_z), rounded once; 0 where that length is 0 or not finite.  It is the normal mvdfusion_amd/fusion.py
+ *               sample_normals gives for the face (to the rounding of its norm).
+ *   method    : MVD_NN_BRUTE -- every query of a scene against every face of the scene, staged through LDS as resolved 48-byte records.
+ *               MVD_NN_GRID -- the grid of mvd_nearest_points (its box keys, cell side, cell function, shell walk and stop rule: one
+ *               copy of the code, csrc/nn_grid.hpp) over the box of the vertices of the scene's candidate faces.  A face is referenced
+ *               from every cell the axis-aligned box of its three vertices overlaps.  A face whose box spans more than MVD_MESH_SPAN
+ *               cells along an axis goes to the scene's OVERSIZE list instead, which every query of the scene scans in full before its
+ *               walk; every other face has at most MVD_MESH_SPAN^3 references.  The search is exact for any input -- face, region and
+ *               every output are the bits MVD_NN_BRUTE gives; a mesh of huge faces only degrades to a brute scan.  Build: box, count,
+ *               scan, fill, with integer atomics only; the order of the references differs run to run and the selection does not see it.
+ *               MVD_NN_AUTO -- chosen from nf / nscene on the host (csrc/meshdist.hip: kMDGridMinFaces, an interface default).
+ *   grid      : cells per axis of MVD_NN_GRID, 1 .. 256, or 0 for the library's choice, a host computation from nf / nscene.
+ *   Bounded whatever the data, as mvd_nearest_points is: the shell loop ends at r = grid; ranges and counts read back from the scratch
+ *   are clamped, a reference counts only inside the scene's face range, and every face is validated where it is evaluated.
+ *   nq, nv, nf <= 2^31 - 1; 1 <= nscene <= 65535; for MVD_NN_GRID nscene * grid^3 <= 2^31 - 1 and nf * MVD_MESH_SPAN^3 <= 2^31 - 1.
+ *   nq = 0 and nf = 0 are valid calls (query may be NULL with nq = 0, faces with nf = 0, vertices with nv = 0).  All pointers 4-byte
+ *   aligned.
+ *   scratch   : mvd_nearest_on_mesh_scratch(nf, nscene, method, grid) bytes, 16-byte aligned -- a function of these four alone; 0 bytes
+ *               (NULL allowed) for MVD_NN_BRUTE; the function returns 0 for an argument out of range.
+ *   Enqueued on the caller's stream with no host synchronisation and no allocation; every argument is checked before anything is
+ *   enqueued, a refused call writes nothing; every scratch word that is read is written earlier in the same call.
+ * mvd_nearest_on_mesh_stages: the same call restricted to `stages` (MVD_NN_BUILD -- nothing for MVD_NN_BRUTE --, MVD_NN_QUERY), for
+ *   timing the two or for several query sets against one built grid (same vertices, faces, face_start, nf, nscene, method, grid).
+ *
+ * mvd_mesh_icp: mvd_plane_icp's loop with this search as its correspondence.  MVD_NN_BUILD once over the mesh; iters times { apply
+ *   transform to the ORIGINAL source -> moved; MVD_NN_QUERY of moved -> face, dist2, point, normal; the fit of mvd_plane_fit on the pairs
+ *   (moved[i], point[i], normal[i]) -- target = point, normals = normal, index == NULL, this dist2 --; history row k }; then a last
+ *   apply, query and row (iters) without a step.  No arithmetic is added: the sums, the solve, the gate max_dist2, the row layout
+ *   (MVD_PLANE_HISTORY) and the refusal of a zero normal (a degenerate face takes no part) are mvd_plane_fit's, so the result equals,
+ *   bit for bit, the same sequence issued by the caller through mvd_align_apply, mvd_nearest_on_mesh_stages and mvd_plane_fit.
+ *   transform (nscene, 12) holds the start on entry and the result on return; history is (iters + 1, nscene, 4); moved (nq, 3), face
+ *   (nq,), dist2 (nq,), point (nq, 3), normal (nq, 3) are all required with nq > 0 and are left as the last pass wrote them.
+ *   0 <= iters <= MVD_ALIGN_MAX_ITERS.  scratch: mvd_mesh_icp_scratch(nq, nf, nscene, method, grid) bytes, 16-byte aligned (0 for an
+ *   argument out of range).  Enqueue-only, checked before the first enqueue, as the sections above. */
+#define MVD_MESH_SPAN 3
+size_t mvd_nearest_on_mesh_scratch(size_t nf, int nscene, int method, int grid);
+int mvd_nearest_on_mesh(const float* query, const int* query_start, const float* vertices, const int* faces, const int* face_start, size_t nq,
+                        size_t nv, size_t nf, int nscene, int method, int grid, int* face, float* dist2, float* point, float* bary,
+                        int* region, float* normal, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+int mvd_nearest_on_mesh_stages(const float* query, const int* query_start, const float* vertices, const int* faces, const int* face_start,
+                               size_t nq, size_t nv, size_t nf, int nscene, int method, int grid, int* face, float* dist2, float* point,
+                               float* bary, int* region, float* normal, void* scratch, size_t scratch_bytes, int stages,
+                               mvd_stream_t stream);
+size_t mvd_mesh_icp_scratch(size_t nq, size_t nf, int nscene, int method, int grid);
+int mvd_mesh_icp(const float* source, const int* source_start, const float* vertices, const int* faces, const int* face_start, size_t nq,
+                 size_t nv, size_t nf, int nscene, int method, int grid, int iters, float max_dist2, double* transform, double* history,
+                 float* moved, int* face, float* dist2, float* point, float* normal, void* scratch, size_t scratch_bytes,
+                 mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Volumetric fusion: the sampled RGB-D views integrated into a truncated signed distance volume (TSDF), and a watertight indexed triangle
  * mesh with vertex colours extracted from it by marching tetrahedra (csrc/tsdf.hip, csrc/tsdf_mesh.hpp; host: mvdfusion_amd/fusion.py
  * integrate_tsdf, extract_mesh).  Not in the reference either.  Cameras, projection, depth map and depth lookup are those of the point

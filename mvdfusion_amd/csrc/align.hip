@@ -17,6 +17,8 @@
 // another thing summed per pair and another solve.  accumulate_kernel and solve_kernel are templates over the fit -- PointFit: the
 // nineteen moments and Horn's solve; PlaneFit: the thirty sums of the linearised point-to-plane error and a 6 x 6 Jacobi with the
 // unconstrained directions left out (pl_solve, which mvd_plane_solve runs on the host).
+// MESH TARGET (mvd_mesh_icp): the plane loop with mvd_nearest_on_mesh_stages (meshdist.hip) as its search -- the closest point of the
+// mesh and its face's normal ARE the pair, so PlaneFit runs with target = point, normals = normal and index == NULL.  No new arithmetic.
 //
 // Not tried: apply fused into the query's head or the accumulate's tail, a tree over the partials.
 #include "fusion_common.hpp"
@@ -459,16 +461,18 @@ struct AlignPlan {
 static size_t al_up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // false: an argument is out of range
-static bool al_plan(size_t nq, size_t nt, int nscene, int method, int grid, AlignPlan& p, int sums = kAlSums) {
+static bool al_plan(size_t nq, size_t nt, int nscene, int method, int grid, AlignPlan& p, int sums = kAlSums, bool mesh = false) {
   p = AlignPlan{};
   if (nscene < 1 || nscene > 65535 || nq > 0x7fffffffull || nt > 0x7fffffffull || method < MVD_NN_AUTO || method > MVD_NN_GRID || grid < 0 ||
       grid > 256)
     return false;
   if (method != MVD_NN_BRUTE && (unsigned long long)nscene * grid * grid * grid > 0x7fffffffull) return false;
+  // (the limit of mvd_nearest_on_mesh's grid; MVD_NN_AUTO takes the grid at such a size whatever nscene)
+  if (mesh && method != MVD_NN_BRUTE && (unsigned long long)nt * MVD_MESH_SPAN * MVD_MESH_SPAN * MVD_MESH_SPAN > 0x7fffffffull) return false;
   p.nwg = (unsigned)((nq + kAlChunk - 1) / kAlChunk) + (unsigned)nscene;
   p.off_partial = al_up16((size_t)(nscene + 1) * sizeof(unsigned));
   p.off_nn = p.off_partial + al_up16((size_t)p.nwg * sums * sizeof(double));
-  p.nn_bytes = mvd_nearest_points_scratch(nt, nscene, method, grid);
+  p.nn_bytes = mesh ? mvd_nearest_on_mesh_scratch(nt, nscene, method, grid) : mvd_nearest_points_scratch(nt, nscene, method, grid);      // (nt: nf)
   p.bytes = p.off_nn + p.nn_bytes;
   return true;
 }
@@ -658,6 +662,61 @@ extern "C" int mvd_plane_icp(const float* source, const int* source_start, const
     al_launch_apply(source, source_start, nq, nscene, transform, moved, st);
     rc = mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, p.nn_bytes,
                                    MVD_NN_QUERY, stream);
+    if (rc != 0) break;
+    al_launch_fit<PlaneFit>(a, k < iters ? 0 : MVD_PLANE_NO_STEP, transform, history + (size_t)k * row, nullptr, st);
+  }
+  if (rc != 0) {
+    char why[400];
+    snprintf(why, sizeof(why), "%s", mvd_last_error());
+    mvd_set_error("%s: %s", fn, why);
+    return rc;
+  }
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- mesh target: entries
+extern "C" size_t mvd_mesh_icp_scratch(size_t nq, size_t nf, int nscene, int method, int grid) {
+  AlignPlan p;
+  return al_plan(nq, nf, nscene, method, grid, p, kPlSums, true) ? p.bytes : 0;
+}
+
+extern "C" int mvd_mesh_icp(const float* source, const int* source_start, const float* vertices, const int* faces, const int* face_start,
+                            size_t nq, size_t nv, size_t nf, int nscene, int method, int grid, int iters, float max_dist2, double* transform,
+                            double* history, float* moved, int* face, float* dist2, float* point, float* normal, void* scratch,
+                            size_t scratch_bytes, mvd_stream_t stream) {
+  const char* fn = "mvd_mesh_icp";
+  MVD_CHECK_ARG(method >= MVD_NN_AUTO && method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, method);
+  MVD_CHECK_ARG(grid >= 0 && grid <= 256, "%s: grid=%d outside [0, 256]", fn, grid);
+  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
+  MVD_CHECK_ARG(iters >= 0 && iters <= MVD_ALIGN_MAX_ITERS, "%s: iters=%d outside [0, %d]", fn, iters, MVD_ALIGN_MAX_ITERS);
+  MVD_CHECK_ARG(nq <= 0x7fffffffull && nv <= 0x7fffffffull && nf <= 0x7fffffffull, "%s: nq=%zu, nv=%zu, nf=%zu beyond 2^31 - 1", fn, nq, nv, nf);
+  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
+  MVD_CHECK_ARG(source_start && face_start, "%s: null source_start or face_start", fn);
+  MVD_CHECK_ARG(transform && history && al_aligned(transform, 8) && al_aligned(history, 8), "%s: null or misaligned transform or history", fn);
+  MVD_CHECK_ARG((source && moved && face && dist2 && point && normal) || nq == 0, "%s: null source, moved, face, dist2, point or normal with nq=%zu",
+                fn, nq);
+  MVD_CHECK_ARG(faces || nf == 0, "%s: null faces with nf=%zu", fn, nf);
+  MVD_CHECK_ARG(vertices || nv == 0, "%s: null vertices with nv=%zu", fn, nv);
+  AlignPlan p;
+  MVD_CHECK_ARG(al_plan(nq, nf, nscene, method, grid, p, kPlSums, true),
+                "%s: nscene * grid^3 cells or nf * %d references beyond 2^31 - 1 (nscene=%d, grid=%d, nf=%zu)", fn,
+                MVD_MESH_SPAN * MVD_MESH_SPAN * MVD_MESH_SPAN, nscene, grid, nf);
+  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
+                scratch_bytes, p.bytes);
+  const hipStream_t st = (hipStream_t)stream;
+  void* nn = p.nn_bytes ? (void*)((char*)scratch + p.off_nn) : nullptr;
+  // the pairs of the plane fit: row i of moved with row i of point and normal
+  const FitArgs a = al_args(p, scratch, moved, source_start, point, nullptr, dist2, nq, nq, nscene, max_dist2, normal);
+  // (the search checks its own arguments before it enqueues anything, so a refusal here has written nothing either)
+  int rc = mvd_nearest_on_mesh_stages(moved, source_start, vertices, faces, face_start, nq, nv, nf, nscene, method, grid, face, dist2, point,
+                                      nullptr, nullptr, normal, nn, p.nn_bytes, MVD_NN_BUILD, stream);
+  if (rc == 0) al_launch_map(a, st);
+  const size_t row = (size_t)nscene * MVD_PLANE_HISTORY;
+  for (int k = 0; k <= iters && rc == 0; ++k) {      // row k: the pairs under the transform before step k; the last row has no step
+    al_launch_apply(source, source_start, nq, nscene, transform, moved, st);
+    rc = mvd_nearest_on_mesh_stages(moved, source_start, vertices, faces, face_start, nq, nv, nf, nscene, method, grid, face, dist2, point,
+                                    nullptr, nullptr, normal, nn, p.nn_bytes, MVD_NN_QUERY, stream);
     if (rc != 0) break;
     al_launch_fit<PlaneFit>(a, k < iters ? 0 : MVD_PLANE_NO_STEP, transform, history + (size_t)k * row, nullptr, st);
   }

@@ -683,7 +683,8 @@ def _nearest(query, query_start, target, target_start, N, method, grid):
 def _points_of(side, name, scenes):
     """(xyz (n, 3), sorted scene ids (n,) or None for one scene) of an argument of ``nearest_points``, checked."""
     if isinstance(side, TriangleMesh):
-        raise ValueError(f"{name}: a TriangleMesh has no points to search -- pass sample_mesh(mesh, n)")
+        raise ValueError(f"{name}: a TriangleMesh has no points to search -- pass sample_mesh(mesh, n), or use nearest_on_mesh for the "
+                         f"distance to its triangles")
     if torch.is_tensor(side):
         xyz, scene = side, None
     elif hasattr(side, "xyz") and hasattr(side, "scene"):
@@ -740,6 +741,88 @@ def nearest_points(query, target, scenes=1, method="auto", grid=None):
     q, t = q.float().contiguous(), t.to(dev, torch.float32).contiguous()
     index, dist2 = _nearest(q, _scene_start(q_scene, int(q.shape[0]), N, dev), t, _scene_start(t_scene, int(t.shape[0]), N, dev), N, method, grid)
     return NearestPoints(index=index, dist2=dist2)
+
+
+@dataclass
+class NearestOnMesh:
+    """What ``nearest_on_mesh`` returns, per query point: the closest point of the mesh's triangles."""
+    face: torch.Tensor                       # (nq,) int32: the row of mesh.faces the closest point lies in, or -1 without one
+    dist2: torch.Tensor                      # (nq,) fp32: the squared distance to it (formed in fp64, rounded once), or +inf
+    point: torch.Tensor                      # (nq, 3) fp32: the closest point; NaN without one
+    bary: torch.Tensor                       # (nq, 3) fp32: its barycentrics on that face's three vertices; 0 without one
+    region: torch.Tensor                     # (nq,) int32: 0..2 a vertex of the face, 3..5 an edge (AB, BC, CA), 6 its interior; -1
+    normal: torch.Tensor                     # (nq, 3) fp32: the face's unit normal (the winding decides the side); 0 for a degenerate face
+
+    @property
+    def dist(self):
+        return torch.sqrt(self.dist2)
+
+    @property
+    def hit(self):
+        return self.face >= 0
+
+    def rgb(self, mesh):
+        """(nq, 3) fp32: the vertex colours of ``mesh`` mixed by ``bary`` (float64, rounded once); NaN where nothing was found."""
+        if not isinstance(mesh, TriangleMesh) or mesh.rgb is None:
+            raise ValueError("rgb(mesh): a TriangleMesh with vertex colours")
+        dev = self.face.device
+        ids = mesh.faces.to(dev).long()[self.face.long().clamp(min=0)]                       # (nq, 3)
+        mixed = (self.bary.double()[:, :, None] * mesh.rgb.to(dev).double()[ids]).sum(1).float()
+        return torch.where(self.hit[:, None], mixed, torch.full_like(mixed, float("nan")))
+
+
+def _mesh_arrays(mesh, N, dev):
+    """(vertices (nv, 3) fp32, faces (nf, 3) int32, face_start (N + 1) int32) of a TriangleMesh, contiguous on ``dev``.  A mesh of fewer
+    scenes than N has its remaining scenes empty; one of more is refused."""
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a TriangleMesh")
+    vertices, faces = mesh.vertices, mesh.faces
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh: vertices of shape {tuple(vertices.shape)}, faces of shape {tuple(faces.shape)}, need (n, 3) and (m, 3)")
+    start = [int(v) for v in mesh.face_start.tolist()]
+    if len(start) < 2 or start[0] < 0 or start[-1] > faces.shape[0] or any(a > b for a, b in zip(start, start[1:])):
+        raise ValueError(f"mesh: face_start = {start} for {faces.shape[0]} faces")
+    if len(start) - 1 > N:
+        raise ValueError(f"mesh: a mesh of {len(start) - 1} scenes with scenes = {N}")
+    start = start + [start[-1]] * (N + 1 - len(start))
+    return (vertices.to(dev, torch.float32).contiguous(), faces.to(dev, torch.int32).contiguous(),
+            torch.tensor(start, dtype=torch.int32).to(dev))
+
+
+def _nearest_on_mesh(query, query_start, vertices, faces, face_start, N, method, grid):
+    """The enqueues of mvd_nearest_on_mesh, every output asked for -> NearestOnMesh.  No host synchronisation."""
+    L = hip.lib()
+    dev, nq, nv, nf = query.device, int(query.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
+    hip._req(query), hip._req(vertices), hip._req(faces, torch.int32), hip._req(query_start, torch.int32), hip._req(face_start, torch.int32)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+    out = NearestOnMesh(face=i32(nq), dist2=f32(nq), point=f32(nq, 3), bary=f32(nq, 3), region=i32(nq), normal=f32(nq, 3))
+    nbytes = int(L.mvd_nearest_on_mesh_scratch(nf, N, method, grid))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_nearest_on_mesh(p(query), hip.ptr(query_start), p(vertices), p(faces), hip.ptr(face_start), nq, nv, nf, N, method, grid,
+                                    p(out.face), p(out.dist2), p(out.point), p(out.bary), p(out.region), p(out.normal), p(scratch), nbytes,
+                                    hip.stream()))
+    return out
+
+
+def nearest_on_mesh(query, mesh, scenes=1, method="auto", grid=None):
+    """For every point of ``query`` the exact closest point of the TRIANGLES of ``mesh`` (include/mvd_hip.h: mvd_nearest_on_mesh has the
+    rule) -> NearestOnMesh.  Where ``nearest_points(query, sample_mesh(mesh, n))`` gives the distance to the nearest sample -- an upper
+    bound with a floor of the sample spacing -- this is the distance to the surface: 0 for a point on it.
+
+    query   : what ``nearest_points`` takes: an (n, 3) tensor (scene 0) or anything with ``.xyz`` and a sorted ``.scene``.
+    mesh    : a TriangleMesh; a point searches the faces of its own scene only.  Its host ``face_start`` goes to the device.  A mesh of
+              more scenes than ``scenes`` is refused.
+    scenes, method, grid : as for ``nearest_points``; all three methods return the same bits.
+    A face with an id outside the vertices or a non-finite coordinate is no candidate; a degenerate face (collinear or coincident
+    vertices) is searched as its three segments and has a zero ``normal``.  Nothing is read back from the device."""
+    N, method, grid = _check_nn(scenes, method, grid)
+    q, q_scene = _points_of(query, "query", N)
+    dev = q.device
+    vertices, faces, face_start = _mesh_arrays(mesh, N, dev)
+    q = q.float().contiguous()
+    return _nearest_on_mesh(q, _scene_start(q_scene, int(q.shape[0]), N, dev), vertices, faces, face_start, N, method, grid)
 
 
 @dataclass
@@ -893,7 +976,7 @@ def sample_normals(mesh, samples):
 @dataclass
 class GeometryDistance:
     """What ``compare_geometry`` returns.  The metrics are (N,) float64 tensors, one value per scene, NaN for a scene with an empty side."""
-    a_to_b: NearestPoints                    # for every point of a its nearest point of b
+    a_to_b: NearestPoints                    # for every point of a its nearest point of b (a NearestOnMesh where exact=True met a mesh)
     b_to_a: NearestPoints
     accuracy: torch.Tensor                   # mean distance from a to b
     completeness: torch.Tensor               # mean distance from b to a
@@ -935,7 +1018,7 @@ def geometry_metrics(a_dist2, a_scene, b_dist2, b_scene, scenes, threshold):
     return out
 
 
-def compare_geometry(a, b, threshold=0.02, scenes=1, samples=None, method="auto"):
+def compare_geometry(a, b, threshold=0.02, scenes=1, samples=None, method="auto", exact=False):
     """Distances between two geometries, scene by scene -> GeometryDistance: accuracy (mean distance from a to b), completeness (from
     b to a), their sum the Chamfer distance, its squared form, and precision / recall / F-score at ``threshold``.  With a the
     reconstruction and b the ground truth these are the usual names; any two clouds, rigs or settings can be compared.
@@ -945,6 +1028,10 @@ def compare_geometry(a, b, threshold=0.02, scenes=1, samples=None, method="auto"
     threshold : in world units, the distance up to which a point counts as matched.  An INTERFACE default: no trained checkpoint was
               available when this was written, so nobody has tuned it on real samples -- expect to.
     scenes, method : as for ``nearest_points``.
+    exact   : False -- the distance TO a mesh is the distance to its nearest sample: an upper bound with a floor of about the sample
+              spacing, which moves with ``samples``.  True -- the distance to a side that is a TriangleMesh is ``nearest_on_mesh`` to
+              its triangles (0 for a point on it, independent of ``samples``), and ``a_to_b`` / ``b_to_a`` are then NearestOnMesh; the
+              points taken FROM that side are still its samples.  A side that is not a mesh is searched as before.
     The only host synchronisation is the read of the scene offsets (and, for a mesh, the per-scene areas in ``sample_mesh``)."""
     N, _, _ = _check_nn(scenes, method, None)
     threshold = float(threshold)
@@ -952,16 +1039,19 @@ def compare_geometry(a, b, threshold=0.02, scenes=1, samples=None, method="auto"
         raise ValueError(f"threshold = {threshold}: >= 0")
     if samples is not None and (isinstance(samples, bool) or int(samples) != samples or samples < 1):
         raise ValueError(f"samples = {samples}: None or an integer >= 1")
-    sides = []
+    sides, meshes = [], []
     for name, side in (("a", a), ("b", b)):
+        meshes.append(side if exact and isinstance(side, TriangleMesh) else None)
         if isinstance(side, TriangleMesh):
             if int(side.face_start.numel()) - 1 > N:
                 raise ValueError(f"{name}: a mesh of {int(side.face_start.numel()) - 1} scenes with scenes = {N}")
             side = sample_mesh(side, COMPARE_SAMPLES if samples is None else int(samples))
         _points_of(side, name, N)
         sides.append(side)
-    ab = nearest_points(sides[0], sides[1], scenes=N, method=method)
-    ba = nearest_points(sides[1], sides[0], scenes=N, method=method)
+    to = lambda source, target, mesh: (nearest_points(source, target, scenes=N, method=method) if mesh is None else
+                                       nearest_on_mesh(source, mesh, scenes=N, method=method))
+    ab = to(sides[0], sides[1], meshes[1])
+    ba = to(sides[1], sides[0], meshes[0])
     scene_of = lambda side: None if torch.is_tensor(side) else side.scene
     m = geometry_metrics(ab.dist2, scene_of(sides[0]), ba.dist2, scene_of(sides[1]), N, threshold)
     return GeometryDistance(a_to_b=ab, b_to_a=ba, **m)
@@ -1371,6 +1461,67 @@ def align_to_surface(source, target, normals=None, k=NORMALS_K, scenes=1, iters=
     max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
     history, moved, index, dist2 = _plane_icp(s, s_start, t, t_start, nrm, N, method, grid, int(iters), max_d2, transform)
     return _plane_alignment(transform, scale0, history, moved, index, dist2)
+
+
+def _mesh_icp(source, source_start, vertices, faces, face_start, N, method, grid, iters, max_d2, transform):
+    """The enqueues of mvd_mesh_icp.  transform (N, 12) float64 holds the start and is overwritten with the result.  Returns
+    (history (iters + 1, N, 4) float64, moved (n, 3) fp32, face (n,) int32, dist2 (n,) fp32).  No host synchronisation."""
+    L = hip.lib()
+    dev, nq, nv, nf = source.device, int(source.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
+    hip._req(source), hip._req(vertices), hip._req(faces, torch.int32), hip._req(source_start, torch.int32), hip._req(face_start, torch.int32)
+    hip._req(transform, torch.float64)
+    history = torch.empty(iters + 1, N, hip.PLANE_HISTORY, dtype=torch.float64, device=dev)
+    moved, point, normal = torch.empty_like(source), torch.empty_like(source), torch.empty_like(source)
+    face = torch.empty(nq, dtype=torch.int32, device=dev)
+    dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
+    nbytes = int(L.mvd_mesh_icp_scratch(nq, nf, N, method, grid))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_mesh_icp(p(source), hip.ptr(source_start), p(vertices), p(faces), hip.ptr(face_start), nq, nv, nf, N, method, grid, iters,
+                             max_d2, hip.ptr(transform), hip.ptr(history), p(moved), p(face), p(dist2), p(point), p(normal), hip.ptr(scratch),
+                             nbytes, hip.stream()))
+    return history, moved, face, dist2
+
+
+def align_to_mesh(source, mesh, scenes=1, iters=ALIGN_ITERS, max_distance=None, init=None, method="auto", grid=None):
+    """Point-to-plane ICP whose target is the mesh ITSELF (include/mvd_hip.h: mvd_mesh_icp has the rule) -> PlaneAlignment.
+    ``align_to_surface(source, sample_mesh(mesh, n), sample_normals(...))`` pairs a source point with the nearest SAMPLE, and its
+    residual falls with the sampling density; here the pair is the exact closest point of the triangles with that face's normal, so
+    nothing depends on a sampling of the target.  The loop, the fit, the gate and the rank rule are ``align_to_surface``'s.
+
+    source, scenes, iters, max_distance, init, method, grid : as for ``align_to_surface`` (``init`` is copied, never written into; the
+              fit is rigid and carries a scale in ``init`` through untouched); ``iters`` and ``max_distance`` are the same untuned
+              interface defaults.
+    mesh    : a TriangleMesh of at most ``scenes`` scenes; a degenerate face pairs with nothing (its normal is zero).
+    ``nearest`` is the NearestOnMesh of the moved source against the mesh (the final correspondences).  Apart from
+    ``init="centroid"`` -- which centres on the mesh's VERTICES -- nothing synchronises with the host."""
+    import dataclasses
+    N, method, grid = _check_nn(scenes, method, grid)
+    if isinstance(iters, bool) or not isinstance(iters, (int, float)) or int(iters) != iters or not 0 <= iters <= hip.ALIGN_MAX_ITERS:
+        raise ValueError(f"iters = {iters}: an integer in [0, {hip.ALIGN_MAX_ITERS}]")
+    if max_distance is not None and not float(max_distance) >= 0:
+        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    s, s_scene = _points_of(source, "source", N)
+    dev = s.device
+    s = s.float().contiguous()
+    vertices, faces, face_start = _mesh_arrays(mesh, N, dev)
+    if isinstance(init, str) and init != "centroid":
+        raise ValueError(f"init = {init!r}: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
+    s_start = _scene_start(s_scene, int(s.shape[0]), N, dev)
+    if init is None:
+        transform, scale0 = _identity_transform(N, dev), torch.ones(N, dtype=torch.float64, device=dev)
+    elif isinstance(init, str):
+        v_start = [int(v) for v in mesh.vertex_start.tolist()]
+        v_start = torch.tensor(v_start + [v_start[-1]] * (N + 1 - len(v_start)), dtype=torch.int32).to(dev)
+        transform, scale0 = _centroid_init(s, s_start, vertices, v_start, N, False)
+    else:
+        transform, scale0 = _check_init(init, N, dev)
+        transform = transform.clone()          # (the loop writes its result there: never into the caller's init, which a view can alias)
+    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
+    history, moved, face, dist2 = _mesh_icp(s, s_start, vertices, faces, face_start, N, method, grid, int(iters), max_d2, transform)
+    out = _plane_alignment(transform, scale0, history, moved, face, dist2)
+    # every field of the final correspondences (the loop keeps face, dist2, point and normal only): the same search once more
+    return dataclasses.replace(out, nearest=_nearest_on_mesh(moved, s_start, vertices, faces, face_start, N, method, grid))
 
 
 def write_ply(path, cloud, normals=None):

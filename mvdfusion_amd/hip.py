@@ -63,6 +63,7 @@ PLANE_NO_STEP = 2                                          # flag of mvd_plane_f
 PLANE_SUMS, PLANE_HISTORY = 30, 4                          # doubles per scene: the point-to-plane sums; a history row (plane rms, pairs, point rms, rank)
 PLANE_EPS_RANK = 1e-9                                      # MVD_PLANE_EPS_RANK: a direction is kept above this share of the largest eigenvalue
 ALIGN_MAX_ITERS = 1024                                     # the largest `iters` of mvd_align_icp
+MESH_SPAN = 3                                              # MVD_MESH_SPAN: cells per axis a face may span before it joins its scene's oversize list
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -194,6 +195,11 @@ SIGNATURES = {
     "mvd_plane_solve": (_i, [_vp, _vp, _vp]),
     "mvd_plane_fit": (_i, [_vp] * 6 + [_sz, _sz, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "mvd_plane_icp": (_i, [_vp] * 5 + [_sz, _sz, _i, _i, _i, _i, _f] + [_vp] * 6 + [_sz, _vp]),
+    "mvd_nearest_on_mesh_scratch": (_sz, [_sz, _i, _i, _i]),
+    "mvd_nearest_on_mesh": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i] + [_vp] * 7 + [_sz, _vp]),
+    "mvd_nearest_on_mesh_stages": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i] + [_vp] * 7 + [_sz, _i, _vp]),
+    "mvd_mesh_icp_scratch": (_sz, [_sz, _sz, _i, _i, _i]),
+    "mvd_mesh_icp": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i, _i, _f] + [_vp] * 8 + [_sz, _vp]),
     "mvd_tsdf_integrate": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _vp]),
     "mvd_mesh_scratch": (_sz, [_i, _i]),
     "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
