@@ -986,6 +986,54 @@ int mvd_mesh_icp(const float* source, const int* source_start, const float* vert
                  mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Global registration: the start ICP needs.  H pose hypotheses per scene are scored by the truncated squared distance of a sample of the
+ * source to its nearest target points, and K distinct best are picked for refinement (csrc/register.hip; host: mvdfusion_amd/fusion.py
+ * register_geometry, rotation_grid).  Not in the reference either.
+ *
+ * mvd_register_score:
+ *   sample (ns, 3) fp32 with sample_start, target (nt, 3) fp32 with target_start: scenes as in mvd_nearest_points (nscene + 1 int32 DEVICE
+ *   offsets, clamped before they index anything).  hyp (nscene, H, 12) fp64: per scene and hypothesis a transform in mvd_align_apply's
+ *   layout.  Per (scene s, hypothesis h, sample row i of the scene):
+ *     p  = sample[i] under hyp[s][h] by THE apply rule of mvd_align_apply: fp64 in its operation order, one cast to fp32.
+ *     d2 = dist2 of mvd_nearest_points for the query p among the scene's targets: the least (dx * dx + dy * dy) + dz * dz in fp32 under
+ *          the strict comparison, +inf when nothing is found (no target in the scene, a non-finite p).
+ *     The row is an INLIER when d2 <= trunc2, compared in fp32 (a NaN compares false); its cost c is d2 for an inlier, else trunc2.
+ *   score[s][h] = sum (double)c over the rows of scene s, reduced exactly as MVD_ALIGN_SUMS are: chunks of MVD_ALIGN_CHUNK rows counted from
+ *   the scene's first row, thread t of a workgroup its rows t, t + 256, .. in order, the lanes of a wavefront in an xor butterfly, the four
+ *   wavefronts as (w0 + w1) + (w2 + w3), the chunk sums added in ascending chunk order.  No float atomics: the same bits run to run, and
+ *   for a scene alone and inside a batch.  inliers[s][h]: the count, int32.  A row of no scene contributes nothing; a scene without rows
+ *   scores 0.  Nothing per row is written: there is no H x ns array.
+ *   method, grid: those of mvd_nearest_points, resolved by the same host rule from nt / nscene.  MVD_NN_GRID walks the grid that
+ *   mvd_nearest_points_stages(.., MVD_NN_BUILD) left in the HEAD of `scratch` -- call it with this scratch pointer and the same target,
+ *   target_start, nt, nscene, method and grid before the first score; any number of scores may follow one build.  The walk holds
+ *   min(best, trunc2) against its bound, so it ends as soon as no unvisited cell can hold a target within the truncation; c and the
+ *   inlier bit are those of the full search (csrc/register.hip has the argument).  MVD_NN_BRUTE scans the scene's targets through LDS
+ *   and gives the same bits.
+ *   trunc2 finite and > 0.  1 <= H <= MVD_REGISTER_MAX_H.  ns, nt <= 2^31 - 1.
+ *   scratch: mvd_register_scratch(ns, nt, nscene, H, method, grid) bytes, 16-byte aligned; its first
+ *   mvd_nearest_points_scratch(nt, nscene, method, grid) bytes are the search's scratch, whatever ns and H.  0 for an argument out of range.
+ *
+ * mvd_register_select: per scene, K <= MVD_REGISTER_MAX_K distinct best of H hypotheses.  score (nscene, H) fp64; quat (H, 4) fp64 unit
+ *   quaternions, shared by all scenes.  K rounds: (1) take the live h with the lowest (score, h): the lower score, between equal scores
+ *   the lower h; a NaN score is never live, +inf is.  (2) kill h and every h' with |q_h . q_h'| >= cos_half, the product formed in fp64 as
+ *   ((q0 q0' + q1 q1') + q2 q2') + q3 q3' without contraction.  cos_half = cos(angle / 2) suppresses the rotations within `angle` of a
+ *   winner; cos_half > 1 suppresses nothing and the result is the plain top K.  top (nscene, K) int32: h, or -1 once nothing is live;
+ *   top_score (nscene, K) fp64: its score, +inf for -1.  One workgroup per scene; H <= MVD_REGISTER_MAX_H.
+ *
+ * Both are enqueued on the caller's stream with no host synchronisation and no allocation.  Every argument is checked before anything is
+ * enqueued -- a NULL pointer, a misaligned one (8 bytes for fp64, 4 otherwise, 16 for the scratch), an argument out of range, a scratch
+ * too small, a trunc2 that is not finite and positive, a NaN cos_half -- and a refused call returns non-zero with its name in
+ * mvd_last_error() and writes nothing. */
+#define MVD_REGISTER_MAX_H 16384
+#define MVD_REGISTER_MAX_K 32
+size_t mvd_register_scratch(size_t ns, size_t nt, int nscene, int H, int method, int grid);
+int mvd_register_score(const float* sample, const int* sample_start, const float* target, const int* target_start, size_t ns, size_t nt,
+                       int nscene, int H, const double* hyp, float trunc2, int method, int grid, double* score, int* inliers, void* scratch,
+                       size_t scratch_bytes, mvd_stream_t stream);
+int mvd_register_select(const double* score, const double* quat, int nscene, int H, int K, double cos_half, int* top, double* top_score,
+                        mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Volumetric fusion: the sampled RGB-D views integrated into a truncated signed distance volume (TSDF), and a watertight indexed triangle
  * mesh with vertex colours extracted from it by marching tetrahedra (csrc/tsdf.hip, csrc/tsdf_mesh.hpp; host: mvdfusion_amd/fusion.py
  * integrate_tsdf, extract_mesh).  Not in the reference either.  Cameras, projection, depth map and depth lookup are those of the point

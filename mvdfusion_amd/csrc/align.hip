@@ -21,14 +21,10 @@
 // mesh and its face's normal ARE the pair, so PlaneFit runs with target = point, normals = normal and index == NULL.  No new arithmetic.
 //
 // Not tried: apply fused into the query's head or the accumulate's tail, a tree over the partials.
-#include "fusion_common.hpp"
+#include "align_common.hpp"
 
 namespace {
 
-#define AL_HD __host__ __device__ __forceinline__
-
-constexpr int kAlThreads = 256;
-constexpr int kAlChunk = MVD_ALIGN_CHUNK;             // rows one workgroup reduces: kAlChunk / kAlThreads per thread
 constexpr int kAlSums = MVD_ALIGN_SUMS;
 constexpr int kSolveTile = 128;                       // chunk sums the solve stages through LDS at a time (19 KB)
 constexpr int kAlSweeps = 12;                         // cyclic Jacobi sweeps of the 4 x 4 solve (converged after 5 or 6; the rest skip)
@@ -36,27 +32,6 @@ constexpr double kAlThetaBig = 1e150;                 // above it theta^2 + 1 ==
 constexpr int kPlSums = MVD_PLANE_SUMS;
 constexpr int kPlSweeps = 16;                         // cyclic Jacobi sweeps of the 6 x 6 solve (converged after 6 or 7; the rest skip)
 constexpr double kPlSmallAngle = 1e-4;                // below it the quaternion of the step comes from the series (next term: angle^6 / 645120)
-static_assert(kAlChunk % kAlThreads == 0, "whole rows per thread");
-
-AL_HD long long al_clamp(long long v, long long n) { return v < 0 ? 0 : (v > n ? n : v); }
-
-// The scene s with start[s] <= i < start[s + 1] (values clamped to [0, n]), or -1: mvd_nearest_points' membership rule.
-AL_HD int al_find_scene(const int* start, int nscene, long long n, long long i) {
-  if (i < al_clamp(start[0], n)) return -1;
-  int lo = 0, hi = nscene;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (al_clamp(start[mid], n) <= i) lo = mid;
-    else hi = mid;
-  }
-  return i < al_clamp(start[lo + 1], n) ? lo : -1;
-}
-
-// THE apply rule of the header, in its order
-AL_HD void al_apply(const double* m, float x, float y, float z, float* out) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r) out[r] = (float)(((m[r * 4 + 0] * (double)x + m[r * 4 + 1] * (double)y) + m[r * 4 + 2] * (double)z) + m[r * 4 + 3]);
-}
 
 // mvd_nearest_points' distance, in its order
 AL_HD float al_d2(const float* p, const float* q) {
@@ -386,9 +361,7 @@ __global__ __launch_bounds__(kAlThreads) void apply_kernel(const float* __restri
 
 __global__ __launch_bounds__(kAlThreads) void chunk_count_kernel(const int* __restrict__ start, int nscene, long long n, unsigned* __restrict__ first) {
   const int s = blockIdx.x * kAlThreads + threadIdx.x;
-  if (s >= nscene) return;
-  const long long len = al_clamp(start[s + 1], n) - al_clamp(start[s], n);
-  first[s] = len > 0 ? (unsigned)((len + kAlChunk - 1) / kAlChunk) : 0u;
+  if (s < nscene) first[s] = al_chunks_of(start, s, n);
 }
 
 template <class Fit>
@@ -458,8 +431,6 @@ struct AlignPlan {
   size_t off_partial, off_nn, nn_bytes, bytes;
 };
 
-static size_t al_up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // false: an argument is out of range
 static bool al_plan(size_t nq, size_t nt, int nscene, int method, int grid, AlignPlan& p, int sums = kAlSums, bool mesh = false) {
   p = AlignPlan{};
@@ -500,8 +471,6 @@ static void al_launch_fit(const FitArgs& a, int flags, double* transform, double
 static void al_launch_apply(const float* src, const int* start, size_t n, int nscene, const double* transform, float* out, hipStream_t st) {
   if (n > 0) hipLaunchKernelGGL(apply_kernel, dim3(cdiv((long)n, kAlThreads)), dim3(kAlThreads), 0, st, src, start, (long long)n, nscene, transform, out);
 }
-
-static bool al_aligned(const void* p, size_t to) { return ((uintptr_t)p & (to - 1)) == 0; }
 
 }  // namespace
 

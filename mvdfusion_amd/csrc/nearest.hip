@@ -17,10 +17,12 @@
 // the list stays in registers: a runtime-indexed array would go to scratch memory.  Resource usage of the two K = 32 kernels and why not LDS: DESIGN.md section 6.00000000000000000.
 //
 // The keys, the grid of a scene, the cell function, the shell walk and the chunk scan live in nn_grid.hpp, which meshdist.hip (the nearest
-// FACE of a mesh) includes too: one copy.
+// FACE of a mesh) includes too: one copy.  The record, the arguments, the distance, the single best and the visit of a range of cells
+// live in nn_points.hpp, which register.hip (the truncated cost of a pose hypothesis) includes too; nn_points_layout tells it the plan.
 //
 // Not tried: sorting the queries by cell, one wavefront per query cell, a hashed grid.
 #include "nn_grid.hpp"
+#include "nn_points.hpp"
 
 namespace {
 
@@ -30,45 +32,9 @@ constexpr int kMaxGrid = 256;
 // (DESIGN.md section 6.000000000000000 has the sweeps both come from)
 constexpr long long kGridMinTargets = 1024;
 constexpr float kGridDivisor = 16.f;
-
-struct alignas(16) Rec {
-  float x, y, z;
-  int id;
-};
-
-struct NNArgs {
-  const float *query, *target;
-  const int *qstart, *tstart;
-  int* index;
-  float* dist2;
-  Rec* sorted;                                        // nt records, cell after cell
-  unsigned* box;                                      // per scene: keys of min x, y, z, then ~keys of max x, y, z (both under atomicMin)
-  unsigned* cells;                                    // nscene * g^3 words padded to kChunk: counts -> begins -> ends
-  unsigned* blocks;                                   // one word per chunk, and the total behind them
-  long long nq, nt;
-  int nscene, g;
-  int k;                                              // mvd_knn_points: neighbours per query (index, dist2 are (nq, k)); unused by the others
-};
-
-// THE distance of the header, in its order
-NN_HD float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
-  const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
-// THE selection rule of the header
-NN_HD void nn_take(float d2, int j, float& best, int& bestj) {
-  if (d2 < best || (d2 == best && j < bestj)) best = d2, bestj = j;      // (bestj = -1 with best = +inf: an infinite d2 never wins)
-}
 // the same comparison as a predicate: candidate (d2, j) comes before entry (e2, ej) in the order of the header
 NN_HD bool nn_before(float d2, int j, float e2, int ej) { return d2 < e2 || (d2 == e2 && j < ej); }
 
-// What a search keeps per query.  take() offers a candidate; worst() is the distance the shell walk holds against its bound.
-struct NNOne {
-  float best = INFINITY;
-  int bestj = -1;
-  NN_HD void take(float d2, int j) { nn_take(d2, j, best, bestj); }
-  NN_HD float worst() const { return best; }
-};
 // The k best in ascending (d2, j) order in the LAST k of K slots, empty slots (+inf, -1) behind the ones found.  The K - k slots in
 // front hold (-inf, -1), which no candidate comes before, so the last slot is always the k-th best and nothing depends on k but the
 // initial fill and the final write.  Every loop has a compile-time trip count and every subscript is a constant after unrolling (picking
@@ -100,18 +66,6 @@ struct NNList {
       if (s >= K - k) a.index[i * k + (s - (K - k))] = j[s], a.dist2[i * k + (s - (K - k))] = d[s];
   }
 };
-
-// The records of the cells [ca, cb] of scene s (local ids, ca <= cb: consecutive cells own consecutive records) against the query.
-template <class Keep>
-NN_HD void nn_visit(const NNArgs& a, long long scene_cell0, long long ca, long long cb, long long t0, long long t1, float qx, float qy, float qz,
-                    Keep& keep) {
-  const long long first = scene_cell0 + ca, last = scene_cell0 + cb;
-  const long long begin = nn_clamp(first > 0 ? (long long)a.cells[first - 1] : 0ll, a.nt), end = nn_clamp((long long)a.cells[last], a.nt);
-  for (long long k = begin; k < end; ++k) {
-    const Rec r = a.sorted[k];
-    if (r.id >= t0 && r.id < t1) keep.take(nn_d2(qx, qy, qz, r.x, r.y, r.z), r.id);
-  }
-}
 
 // One query against the built grid.  Writes index[i] and dist2[i].
 NN_HD void nn_query_grid(const NNArgs& a, long long i) {
@@ -266,6 +220,13 @@ static bool nn_plan(size_t nt, int nscene, int method, int grid, NNPlan& p) {
 }
 
 }  // namespace
+
+bool nn_points_layout(size_t nt, int nscene, int method, int grid, NNLayout* out) {
+  NNPlan p;
+  if (!nn_plan(nt, nscene, method, grid, p)) return false;
+  *out = NNLayout{p.method, p.g, p.off_box, p.off_cells, p.bytes};
+  return true;
+}
 
 extern "C" size_t mvd_nearest_points_scratch(size_t nt, int nscene, int method, int grid) {
   NNPlan p;

@@ -37,6 +37,7 @@ pairs; both return an ``Alignment`` whose ``apply`` moves a cloud, surface sampl
 ``align_to_surface`` is the point-to-plane form of that loop (mvd_plane_icp) on the normals of the target -- what converges on a dense
 smooth surface, where point-to-point slides -- and ``fit_plane_step`` its one linearised step for known pairs.
 """
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -1276,7 +1277,7 @@ def align_geometry(source, target, scenes=1, iters=ALIGN_ITERS, scale=False, max
               reflection or a NaN there is taken as given, and its scale as |det|^(1/3)), or
               "centroid" -- the source's per-scene centroid mapped onto the target's and, with ``scale``, the RMS radii matched
               (float64 torch ops per scene slice; reads the scene offsets once).  ICP converges to the nearest local optimum: it needs
-              a start in its basin -- there is no global registration here.
+              a start in its basin -- ``register_geometry`` finds one from an arbitrary pose, and its result is a valid ``init``.
     method, grid : those of ``nearest_points``.
     ``iters`` and ``max_distance`` are INTERFACE defaults: no trained checkpoint or scan was available when this was written, so
     nobody has tuned them on real data -- expect to.  A scene with fewer than 3 accepted pairs keeps its transform.  Apart from
@@ -1522,6 +1523,256 @@ def align_to_mesh(source, mesh, scenes=1, iters=ALIGN_ITERS, max_distance=None, 
     out = _plane_alignment(transform, scale0, history, moved, face, dist2)
     # every field of the final correspondences (the loop keeps face, dist2, point and normal only): the same search once more
     return dataclasses.replace(out, nearest=_nearest_on_mesh(moved, s_start, vertices, faces, face_start, N, method, grid))
+
+
+# ------------------------------------------------------------------------------------------------ global registration
+REGISTER_ROTATIONS = 4096                    # register_geometry's defaults: rotations scored, sample rows per scene, candidates refined.
+REGISTER_SAMPLES = 256                       # INTERFACE defaults: the cheapest setting at which the float64 oracle recovers every pose of
+REGISTER_CANDIDATES = 4                      # the test table (DESIGN.md has the sweep); nobody has tuned them on real data
+_SF_PHI, _SF_PSI = 2.0 ** 0.5, 1.533751168755204288118041      # the two constants of the super-Fibonacci spiral
+
+
+def rotation_grid(n):
+    """(n, 4) float64 unit quaternions (w, x, y, z) that cover the rotations evenly: the super-Fibonacci spiral (Alexa, CVPR 2022).
+    With s = i + 1/2 and t = s / n, point i is (sqrt(t) sin a, sqrt(t) cos a, sqrt(1 - t) sin b, sqrt(1 - t) cos b), a = 2 pi s / sqrt(2),
+    b = 2 pi s / 1.533751168755204288118041.  Formed in numpy float64 on the host: the same n gives the same bits.  The covering
+    radius -- the largest angle from any rotation to the nearest of the grid -- is about 35 degrees at n = 256, 20 at 1 024, 13 at
+    4 096."""
+    import numpy as np
+    if isinstance(n, bool) or not isinstance(n, (int, float)) or int(n) != n or not 1 <= n <= hip.REGISTER_MAX_H:
+        raise ValueError(f"rotation_grid: n = {n}: an integer in [1, {hip.REGISTER_MAX_H}]")
+    n = int(n)
+    s = np.arange(n, dtype=np.float64) + 0.5
+    t = s / float(n)
+    r, big = np.sqrt(t), np.sqrt(1.0 - t)
+    a, b = 2.0 * np.pi * s / _SF_PHI, 2.0 * np.pi * s / _SF_PSI
+    return torch.from_numpy(np.stack([r * np.sin(a), r * np.cos(a), big * np.sin(b), big * np.cos(b)], axis=1))
+
+
+def _quat_matrix(q):
+    """(H, 4) unit (w, x, y, z) float64 -> (H, 3, 3), the formula of the solve (include/mvd_hip.h: mvd_align_fit)."""
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    rows = [1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+            2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+            2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]
+    return torch.stack(rows, dim=1).reshape(-1, 3, 3)
+
+
+def _matrix_quat(R):
+    """(H, 3, 3) rotations float64 (host) -> (H, 4) unit (w, x, y, z): the dominant eigenvector of the symmetric 4 x 4 form, which has
+    no branch at 180 degrees."""
+    m = lambda a, b: R[:, a, b]
+    K = torch.stack([m(0, 0) + m(1, 1) + m(2, 2), m(2, 1) - m(1, 2), m(0, 2) - m(2, 0), m(1, 0) - m(0, 1),
+                     m(2, 1) - m(1, 2), m(0, 0) - m(1, 1) - m(2, 2), m(0, 1) + m(1, 0), m(0, 2) + m(2, 0),
+                     m(0, 2) - m(2, 0), m(0, 1) + m(1, 0), m(1, 1) - m(0, 0) - m(2, 2), m(1, 2) + m(2, 1),
+                     m(1, 0) - m(0, 1), m(0, 2) + m(2, 0), m(1, 2) + m(2, 1), m(2, 2) - m(0, 0) - m(1, 1)], dim=1).reshape(-1, 4, 4)
+    return torch.linalg.eigh(K)[1][:, :, -1].contiguous()
+
+
+def _check_rotations(rotations):
+    """(quat (H, 4), R (H, 3, 3)) float64 in host memory, of a count, an (H, 4) or an (H, 3, 3) tensor."""
+    if not torch.is_tensor(rotations):
+        q = rotation_grid(rotations)
+        return q, _quat_matrix(q)
+    if rotations.dim() not in (2, 3) or tuple(rotations.shape[1:]) not in ((4,), (3, 3)) or not 1 <= rotations.shape[0] <= hip.REGISTER_MAX_H:
+        raise ValueError(f"rotations: a count, or an (H, 4) or (H, 3, 3) tensor with 1 <= H <= {hip.REGISTER_MAX_H}; got {tuple(rotations.shape)}")
+    r = rotations.detach().to("cpu", torch.float64)
+    if not bool(torch.isfinite(r).all()):
+        raise ValueError("rotations: a non-finite entry")
+    if r.dim() == 2:
+        norm = r.norm(dim=1, keepdim=True)
+        if not bool((norm > 0).all()):
+            raise ValueError("rotations: a zero quaternion")
+        q = r / norm
+        return q, _quat_matrix(q)
+    if not bool((torch.linalg.det(r) > 0).all()):
+        raise ValueError("rotations: a matrix with a non-positive determinant (rotations, not reflections)")
+    return _matrix_quat(r), r
+
+
+def _register_scratch(n_rows, nt, N, H, method, grid):
+    return int(hip.lib().mvd_register_scratch(n_rows, nt, N, H, method, grid))
+
+
+def _register_build(target, target_start, N, method, grid, scratch, nbytes):
+    """MVD_NN_BUILD of mvd_nearest_points_stages into the head of ``scratch``: the grid every following score walks."""
+    L = hip.lib()
+    nt = int(target.shape[0])
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_nearest_points_stages(None, hip.ptr(target_start), p(target), hip.ptr(target_start), 0, nt, N, method, grid, None, None,
+                                          p(scratch), nbytes, hip.NN_BUILD, hip.stream()))
+
+
+def _register_score(points, start, target, target_start, N, hyp, trunc2, method, grid, scratch, nbytes):
+    """The enqueues of mvd_register_score against the grid ``_register_build`` left in ``scratch``: points (n, 3) fp32, hyp (N, H, 12)
+    float64 -> (score (N, H) float64, inliers (N, H) int32).  No host synchronisation."""
+    L = hip.lib()
+    dev, n, nt, H = points.device, int(points.shape[0]), int(target.shape[0]), int(hyp.shape[1])
+    hip._req(points), hip._req(target), hip._req(start, torch.int32), hip._req(target_start, torch.int32), hip._req(hyp, torch.float64)
+    score = torch.empty(N, H, dtype=torch.float64, device=dev)
+    inliers = torch.empty(N, H, dtype=torch.int32, device=dev)
+    p = lambda t: hip.ptr(t) if t.numel() else None
+    hip.check(L.mvd_register_score(p(points), hip.ptr(start), p(target), hip.ptr(target_start), n, nt, N, H, hip.ptr(hyp), trunc2, method, grid,
+                                   hip.ptr(score), hip.ptr(inliers), hip.ptr(scratch), nbytes, hip.stream()))
+    return score, inliers
+
+
+def _register_select(score, quat, K, cos_half):
+    """The enqueue of mvd_register_select: score (N, H) float64, quat (H, 4) float64 -> (top (N, K) int32, top_score (N, K) float64)."""
+    L = hip.lib()
+    N, H = int(score.shape[0]), int(score.shape[1])
+    hip._req(score, torch.float64), hip._req(quat, torch.float64)
+    top = torch.empty(N, K, dtype=torch.int32, device=score.device)
+    top_score = torch.empty(N, K, dtype=torch.float64, device=score.device)
+    hip.check(L.mvd_register_select(hip.ptr(score), hip.ptr(quat), N, H, K, cos_half, hip.ptr(top), hip.ptr(top_score), hip.stream()))
+    return top, top_score
+
+
+@dataclass
+class Registration(Alignment):
+    """What ``register_geometry`` returns: the Alignment of the chosen candidate after its last ICP iterations (``rms`` / ``pairs`` are
+    the history of those), and what the choice was made from.  An object with a symmetry shows as two candidates with (nearly) equal
+    scores: the data cannot tell them apart, and ``chosen`` is then the lower row."""
+    candidates: torch.Tensor                 # (N, K, 4, 4) float64: the K refined transforms
+    candidate_score: torch.Tensor            # (N, K) float64: their truncated cost on the full source; +inf for a slot without a candidate
+    candidate_inliers: torch.Tensor          # (N, K) int32: source points within `trunc` of the target under each
+    chosen: torch.Tensor                     # (N,) int64: the row of `candidates` the result was polished from
+    grid_score: torch.Tensor                 # (N, H) float64: the truncated cost of the sample under every rotation of the grid
+
+
+def _scene_moments(pts, starts, N):
+    """Per scene (ok (N,) bool, centroid (N, 3), mean squared radius (N,)) of the finite rows: ``_centroid_init``'s float64 torch ops."""
+    ok, cen, r2 = [], [], []
+    for k in range(N):
+        part = pts[starts[k]:starts[k + 1]].double()
+        fin = torch.isfinite(part).all(1, keepdim=True)
+        cnt = fin.sum().double()
+        c = torch.where(fin, part, torch.zeros_like(part)).sum(0) / cnt
+        ok.append(cnt > 0), cen.append(c), r2.append(torch.where(fin, (part - c) ** 2, torch.zeros_like(part)).sum() / cnt)
+    return torch.stack(ok), torch.stack(cen), torch.stack(r2)
+
+
+def _check_count(value, name, lo, hi):
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or int(value) != value or not lo <= value <= hi:
+        raise ValueError(f"{name} = {value}: an integer in [{lo}, {hi}]")
+    return int(value)
+
+
+def _register_inputs(s, s_start, t, t_start, N, R, scale, samples, trunc):
+    """What ``register_geometry`` scores: (hyp (N, H, 12) float64, the scale k of the hypotheses (N,), the sample (m, 3) fp32, its offsets
+    (N + 1,) int32, trunc2 as the fp32 value the kernel compares with).  R (H, 3, 3) float64 in host memory.  Reads the scene offsets
+    once and, with ``trunc`` None, the target's radii."""
+    dev, H = s.device, int(R.shape[0])
+    starts = torch.stack([s_start, t_start]).tolist()                       # the host read
+    (ok_s, c_s, r_s), (ok_t, c_t, r_t) = _scene_moments(s, starts[0], N), _scene_moments(t, starts[1], N)
+    if trunc is None:
+        radii = [math.sqrt(v) for v in r_t.tolist() if 0 < v < float("inf")]
+        if not radii:
+            raise ValueError("trunc = None: no scene of the target has two distinct finite points to take a radius from")
+        trunc = 0.1 * min(radii)
+    trunc2 = _fl32_square(float(trunc))
+    if not 0 < trunc2 < float("inf"):
+        raise ValueError(f"trunc = {trunc}: its square is not a positive finite fp32 value")
+    # hypotheses: k R_h, t = c_t - k R_h c_s
+    k_ = torch.sqrt(r_t / r_s) if scale else torch.ones(N, dtype=torch.float64, device=dev)
+    ok = ok_s & ok_t & torch.isfinite(k_) & (k_ > 0)
+    k_ = torch.where(ok, k_, torch.ones_like(k_))
+    A = k_[:, None, None, None] * R.to(dev)[None]                            # (N, H, 3, 3)
+    turned = (A * c_s[:, None, None, :]).sum(-1)                             # (N, H, 3)
+    shift = torch.where(ok[:, None, None], c_t[:, None, :] - turned, torch.zeros_like(turned))
+    hyp = torch.cat([A, shift[..., None]], dim=-1).reshape(N, H, 12).contiguous()
+    # the sample: every step-th row of each scene
+    rows, sample_start = [], [0]
+    for k in range(N):
+        a, b = starts[0][k], starts[0][k + 1]
+        rows.append(torch.arange(a, b, max(-(-(b - a) // samples), 1), dtype=torch.int64))
+        sample_start.append(sample_start[-1] + int(rows[-1].numel()))
+    sample = s[torch.cat(rows).to(dev)].contiguous()
+    sample_start = torch.tensor(sample_start, dtype=torch.int32).to(dev)
+    return hyp, k_, sample, sample_start, trunc2
+
+
+def register_geometry(source, target, scenes=1, rotations=REGISTER_ROTATIONS, samples=REGISTER_SAMPLES, candidates=REGISTER_CANDIDATES,
+                      separation=30.0, trunc=None, scale=False, refine_iters=20, iters=ALIGN_ITERS, max_distance=None, method="auto",
+                      grid=None):
+    """Global registration: the start ICP needs, found without one -> Registration, an Alignment (so a valid ``init=`` of
+    ``align_geometry``, ``align_to_surface`` and ``align_to_mesh``, with ``.apply``).  A grid of rotations is scored on a sample of the
+    source, the best few distinct ones are refined by point-to-point ICP, and the best AFTER refinement is polished (include/mvd_hip.h:
+    mvd_register_score and mvd_register_select have the rules).
+
+    source, target : what ``nearest_points`` takes; a TriangleMesh is refused with the same message -- for a mesh target,
+              ``align_to_mesh(s, mesh, init=register_geometry(s, sample_mesh(mesh, n)))``.
+    scenes  : N; every scene is registered on its own.
+    rotations : H, the size of ``rotation_grid`` (at most hip.REGISTER_MAX_H), or the rotations themselves as an (H, 4) tensor of
+              (w, x, y, z) quaternions or an (H, 3, 3) tensor of matrices -- a known symmetry group, or the identity alone.
+    Hypotheses : per scene and rotation R_h, x -> k R_h x + t with the source's centroid mapped onto the target's and, with ``scale``,
+              k the ratio of the RMS radii (else 1): ``init="centroid"`` turned by R_h.  float64 torch ops; they read the scene offsets
+              once.  The translation comes from the centroids, so the two sides must show the same part of the object: partial
+              overlap is out of scope.
+    samples : the grid is scored on every ceil(n / samples)-th row of each scene, counted from the scene's first row.
+    trunc   : a sample point costs min(d2, fl32(trunc)^2), d2 its squared distance to the nearest target point, so a point without a
+              partner costs a constant instead of dominating the sum.  None: 0.1 x the RMS radius of the target (the smallest over the
+              scenes; one more host read).
+    candidates, separation : K <= hip.REGISTER_MAX_K rotations are refined: greedily the lowest score, then the lowest among those more
+              than ``separation`` degrees from every one taken (0: plain top K).
+    refine_iters : ICP iterations (``align_geometry``'s, on the FULL source, with ``scale`` and ``max_distance``) from each candidate.
+              The refined candidates are scored on the full source and the lowest is chosen -- after refinement the true basin scores
+              about 0, while a flipped basin of a nearly symmetric shape still scores high; before, their scores overlap.
+    iters   : further ICP iterations from the chosen candidate; ``rms`` and ``pairs`` are their history.
+    max_distance, method, grid : those of ``align_geometry``.
+    ``rotations``, ``samples``, ``candidates``, ``separation``, ``trunc``, ``refine_iters`` and ``iters`` are INTERFACE defaults: chosen on a
+    synthetic shape (DESIGN.md has the sweep), never tuned on real data -- expect to.  An object with a symmetry has several equally good
+    answers; ``candidates`` / ``candidate_score`` show them.  The target's grid is built once for the two scores and once more inside
+    each of the K + 1 ICP calls.  After the hypotheses everything is enqueued: no host read."""
+    N, method, grid = _check_nn(scenes, method, grid)
+    samples = _check_count(samples, "samples", 1, 2 ** 31 - 1)
+    K = _check_count(candidates, "candidates", 1, hip.REGISTER_MAX_K)
+    refine_iters = _check_count(refine_iters, "refine_iters", 0, hip.ALIGN_MAX_ITERS)
+    iters = _check_count(iters, "iters", 0, hip.ALIGN_MAX_ITERS)
+    if not isinstance(scale, bool):
+        raise ValueError(f"scale = {scale!r}: True or False")
+    if isinstance(separation, bool) or not 0 <= float(separation) <= 180:
+        raise ValueError(f"separation = {separation}: degrees in [0, 180]")
+    if trunc is not None and not 0 < float(trunc) < float("inf"):
+        raise ValueError(f"trunc = {trunc}: None or a finite distance > 0")
+    if max_distance is not None and not float(max_distance) >= 0:
+        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    if not torch.is_tensor(rotations):
+        _check_count(rotations, "rotations", 1, hip.REGISTER_MAX_H)
+    s, s_scene = _points_of(source, "source", N)
+    t, t_scene = _points_of(target, "target", N)
+    quat, R = _check_rotations(rotations)
+    H = int(quat.shape[0])
+    dev = s.device
+    s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
+    n, nt = int(s.shape[0]), int(t.shape[0])
+    s_start, t_start = _scene_start(s_scene, n, N, dev), _scene_start(t_scene, nt, N, dev)
+    hyp, k_, sample, sample_start, trunc2 = _register_inputs(s, s_start, t, t_start, N, R, scale, samples, trunc)
+    nbytes = max(_register_scratch(int(sample.shape[0]), nt, N, H, method, grid), _register_scratch(n, nt, N, K, method, grid))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    _register_build(t, t_start, N, method, grid, scratch, nbytes)
+    grid_score, _ = _register_score(sample, sample_start, t, t_start, N, hyp, trunc2, method, grid, scratch, nbytes)
+    cos_half = math.cos(math.radians(float(separation)) / 2.0) if float(separation) > 0 else 2.0
+    top, _ = _register_select(grid_score, quat.to(dev).contiguous(), K, cos_half)
+    flags = hip.ALIGN_SCALE if scale else 0
+    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
+    scene_ids = torch.arange(N, device=dev)
+    refined, refined_scale = [], []
+    for k in range(K):
+        tr = hyp[scene_ids, top[:, k].clamp(min=0).long()].clone()           # (a slot without a candidate refines hypothesis 0; it is never chosen)
+        history, _, _, _ = _align_icp(s, s_start, t, t_start, N, method, grid, refine_iters, flags, max_d2, tr)
+        refined.append(tr), refined_scale.append(k_ * history[-1, :, 2])
+    refined, refined_scale = torch.stack(refined, dim=1).contiguous(), torch.stack(refined_scale, dim=1)
+    cand_score, cand_inliers = _register_score(s, s_start, t, t_start, N, refined, trunc2, method, grid, scratch, nbytes)
+    cand_score = torch.where(top >= 0, cand_score, torch.full_like(cand_score, float("inf")))
+    chosen, _ = _register_select(cand_score, torch.zeros(K, 4, dtype=torch.float64, device=dev), 1, 2.0)
+    chosen = chosen[:, 0].clamp(min=0).long()
+    transform = refined[scene_ids, chosen].clone()
+    history, moved, index, dist2 = _align_icp(s, s_start, t, t_start, N, method, grid, iters, flags, max_d2, transform)
+    out = _alignment(transform, refined_scale[scene_ids, chosen] * history[-1, :, 2], history, moved, index, dist2)
+    bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=dev).expand(N, K, 1, 4)
+    return Registration(**{f: getattr(out, f) for f in out.__dataclass_fields__}, candidates=torch.cat([refined.reshape(N, K, 3, 4), bottom], dim=2),
+                        candidate_score=cand_score, candidate_inliers=cand_inliers, chosen=chosen, grid_score=grid_score)
 
 
 def write_ply(path, cloud, normals=None):

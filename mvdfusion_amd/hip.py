@@ -63,6 +63,7 @@ PLANE_NO_STEP = 2                                          # flag of mvd_plane_f
 PLANE_SUMS, PLANE_HISTORY = 30, 4                          # doubles per scene: the point-to-plane sums; a history row (plane rms, pairs, point rms, rank)
 PLANE_EPS_RANK = 1e-9                                      # MVD_PLANE_EPS_RANK: a direction is kept above this share of the largest eigenvalue
 ALIGN_MAX_ITERS = 1024                                     # the largest `iters` of mvd_align_icp
+REGISTER_MAX_H, REGISTER_MAX_K = 16384, 32                 # MVD_REGISTER_MAX_H, _MAX_K: the most hypotheses mvd_register_score / _select take; the most picked
 MESH_SPAN = 3                                              # MVD_MESH_SPAN: cells per axis a face may span before it joins its scene's oversize list
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
@@ -200,6 +201,9 @@ SIGNATURES = {
     "mvd_nearest_on_mesh_stages": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i] + [_vp] * 7 + [_sz, _i, _vp]),
     "mvd_mesh_icp_scratch": (_sz, [_sz, _sz, _i, _i, _i]),
     "mvd_mesh_icp": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i, _i, _f] + [_vp] * 8 + [_sz, _vp]),
+    "mvd_register_scratch": (_sz, [_sz, _sz, _i, _i, _i, _i]),
+    "mvd_register_score": (_i, [_vp] * 4 + [_sz, _sz, _i, _i, _vp, _f, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_register_select": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
     "mvd_tsdf_integrate": (_i, [_vp] * 7 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _vp]),
     "mvd_mesh_scratch": (_sz, [_i, _i]),
     "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
