@@ -1104,6 +1104,110 @@ int mvd_mesh_emit(const float* tsdf, const uint8_t* weight, const float* color, 
                   const void* scratch, size_t scratch_bytes, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh topology: what lies between extracting a mesh and handing it on -- the vertex -> face incidence table, connected components, a
+ * topology report, a face filter (the floater remover), area-weighted vertex normals and Taubin smoothing (csrc/meshtopo.hip; host:
+ * mvdfusion_amd/fusion.py mesh_components, mesh_topology, filter_mesh, keep_components, vertex_normals, smooth_mesh).  Not in the
+ * reference either.
+ *
+ * The mesh is that of mvd_mesh_emit / mvd_render_mesh / mvd_nearest_on_mesh: vertices (nv, 3) fp32, faces (nf, 3) int32 GLOBAL ids,
+ * vertex_start and face_start nscene + 1 int32 DEVICE values each, non-decreasing, clamped to [0, nv] or [0, nf] before they index
+ * anything.  Face f belongs to the scene s with face_start[s] <= f < face_start[s + 1].
+ *   Face classes: INVALID -- a face of no scene, or one with an id outside [vertex_start[s], vertex_start[s + 1]) of its own scene; it
+ *               takes no part in anything, is counted, and has the face label -1.  REPEATED -- a valid face with two equal ids; it
+ *               joins its vertices into one component and is counted, but has no edges, no incidence entries, no normal and no umbrella
+ *               contribution.  REGULAR -- every other face; a zero-area face with three distinct ids (the marcher emits them at
+ *               tsdf == 0) is regular.  No entry reads a coordinate to classify a face.
+ *
+ * mvd_mesh_incidence: the CSR table vertex -> (face, corner) of the REGULAR faces.  inc_start (nv + 1) int32: the list of vertex v is
+ *   inc[inc_start[v] .. inc_start[v + 1]); inc (3 nf) int32: entries face * 3 + corner in ASCENDING order within a list, that is in
+ *   ascending (face, corner) order; inc_start[nv] entries are written, the rest of inc is not touched.  Count (an integer atomic per
+ *   corner), the exclusive scan of the searches' grids (csrc/nn_grid.hpp around the single-workgroup scan of the point compaction), fill
+ *   (an integer atomic hands out the slot) and an insertion sort of every list in place by one thread: the sorted table does not depend
+ *   on the arrival order, so it has the same bits run to run.  A list has no bound but 3 nf; the sort costs O(d^2) for a vertex of
+ *   valence d.
+ * mvd_mesh_label: connected components.  Two valid faces are connected when they share a vertex id, transitively; a scene's faces name
+ *   only its own vertices, so a component never crosses scenes.  Per vertex the LABEL is the smallest vertex id of its component -- a
+ *   unique answer, so no race can change it.  A component is NUMBERED iff it has a face, and its compact id is the rank of its label among
+ *   the labels of the numbered components: components are numbered scene after scene, in the order of their smallest vertex.
+ *     vertex_component (nv,) int32: the compact id, -1 for a vertex no valid face uses.  face_component (nf,) int32: the compact id, -1
+ *     for an invalid face.  component_start (nscene + 1) int32: scene s owns the ids [component_start[s], component_start[s + 1]).
+ *   Lock-free union-find: parent[v] = v, one thread per face hooks the larger root under the smaller by atomicCAS and halves paths by
+ *   atomicMin, a flatten pass, a scan of the root flags.  BOUNDS: parent[v] <= v holds from initialisation and across every write and a
+ *   word only decreases, so a find is a strictly descending walk of at most nv steps whatever the memory holds; a hook is retried only
+ *   after ANOTHER thread lowered the same word and goes on from the lower value, so the larger of its two roots strictly decreases: at
+ *   most nv attempts.  Both loops also carry nv as an explicit cap.  No thread waits for another, nothing is persistent or cooperative,
+ *   and the host issues a fixed sequence of launches.
+ * mvd_mesh_component_table: after the host read component_start[nscene] = ncomp: root (ncomp,) int32 the label, faces (ncomp,) and
+ *   vertices (ncomp,) int32 the valid faces and used vertices per component.  Integer atomics (counts and a minimum); ids outside
+ *   [0, ncomp) are not counted.
+ * mvd_mesh_topology: takes the table of mvd_mesh_incidence and vertex_component, component_start of mvd_mesh_label for the same mesh.
+ *   An EDGE is an unordered pair of ids that a regular face has at consecutive corners (corner 2 is followed by corner 0); its USERS are
+ *   the regular faces that contain both ids.  Per face and edge the incidence list of the endpoint with the shorter list (the edge's
+ *   first id between equal lengths) is walked; the user with the lowest (face, edge number) owns the edge, and only the owner adds to the
+ *   totals.  totals (nscene, MVD_TOPO_TOTALS) int32 per scene, in this order:
+ *     0 vertices_used (vertex_component >= 0), 1 unreferenced (the scene's other vertices), 2 faces_regular, 3 faces_repeated,
+ *     4 faces_invalid (a face of no scene is counted nowhere), 5 edges, 6 boundary_edges (one user), 7 nonmanifold_edges (more than two),
+ *     8 misoriented_edges (two users that run along the edge in the same direction), 9 components,
+ *     10 euler = vertices_used - edges + faces_regular.
+ *   vertex_flags (nv,) uint8: MVD_TOPO_FLAG_BOUNDARY -- on a boundary edge; MVD_TOPO_FLAG_NONMANIFOLD -- on a non-manifold edge.  The bits
+ *   are gathered by integer atomicOr on 32-bit words of the scratch and narrowed by the thread that owns the vertex: no byte is read,
+ *   modified and written back.  Integer atomics only: the same bits run to run.  A vertex of valence d costs O(d^2) here: fine for a
+ *   marched mesh (d <= 14 or so), a limit for a caller's mesh with a huge fan.
+ * mvd_mesh_filter_count / _emit: the faces f with keep[f] != 0 (keep (nf,) uint8) that are not invalid survive, in their order; the
+ *   vertices they name survive, in their order; ids are rebased.  The count call flags (plain stores of one value), scans twice and
+ *   writes new_vertex_start and new_face_start ((nscene + 1) int32 each, DEVICE); the host reads those 2 (nscene + 1) values, allocates,
+ *   and the emit call -- same nv, nf and scratch -- writes out_vertices (nvo, 3), out_rgb (nvo, 3) (with rgb non-NULL; both NULL: no
+ *   colour) bit for bit, out_faces (nfo, 3), and the old rows vertex_index (nvo,), face_index (nfo,); rows beyond nvo / nfo are not
+ *   written.
+ * mvd_mesh_vertex_normals: per vertex the fp64 sum, over its incidence list in list order, of the raw cross products n = ab x ac of the
+ *   faces (ab = B - A, ac = C - A from the face's own corner order; each component one subtraction of two products, n_x = ab_y ac_z -
+ *   ab_z ac_y, ... as mvd_nearest_on_mesh forms its normal) -- area weighting -- divided by its length sqrt((s_x s_x + s_y s_y) + s_z s_z)
+ *   and rounded once to fp32; 0 where that length is 0 or not finite or the list is empty.  normals (nv, 3) fp32.
+ * mvd_mesh_smooth: `passes` umbrella passes whose factor f alternates lam, mu, lam, .. (Taubin).  Per vertex and pass, from the
+ *   positions x of the previous pass: S = the fp64 sum per axis, over the incidence list in list order, of the two OTHER vertices of the
+ *   face, the next corner and then the previous one (so an interior neighbour is met twice and a boundary neighbour once: the stated
+ *   rule); c = the number of terms; x' = fp32(x + f * (S / c - x)) in fp64 in exactly this order, without contraction.  The vertex is
+ *   copied unchanged when c == 0, when a coordinate it would read (its own or a neighbour's) is not finite, or when
+ *   vertex_flags[v] & pin_mask != 0 (pin_mask 0: nothing is pinned and vertex_flags may be NULL).  Positions go back and forth between
+ *   `out` and `tmp` ((nv, 3) fp32 each, distinct from `vertices`, which is only read) such that the last pass writes `out`; passes == 0
+ *   copies; tmp may be NULL for passes < 2.  0 <= passes <= MVD_SMOOTH_MAX_PASSES; lam and mu finite.
+ *
+ * For all of them: nv <= 2^31 - 1 - 4096, 3 nf <= 2^31 - 1, 1 <= nscene <= 65535; nv = 0 and nf = 0 are valid calls (a pointer to an
+ * array without elements may be NULL).  Pointers 4-byte aligned (uint8 arrays: any), the scratch 16-byte aligned.  Every index read
+ * back from inc_start, inc or the scratch is clamped or range-checked before it addresses anything.  Scratch sizes: mvd_mesh_*_scratch(nv,
+ * nf) bytes, 0 for an argument out of range, never 0 otherwise; mvd_mesh_filter_scratch serves both filter calls;
+ * mvd_mesh_component_table, mvd_mesh_vertex_normals and mvd_mesh_smooth take no scratch.  Enqueued on the caller's stream with no host
+ * synchronisation and no allocation; every argument is checked before anything is enqueued, a refused call returns non-zero with its name
+ * in mvd_last_error() and writes nothing; every scratch word that is read is written earlier in the same call (the emit call reads what
+ * the count call wrote). */
+#define MVD_TOPO_TOTALS 11
+#define MVD_TOPO_FLAG_BOUNDARY 1
+#define MVD_TOPO_FLAG_NONMANIFOLD 2
+#define MVD_SMOOTH_MAX_PASSES 2000
+size_t mvd_mesh_incidence_scratch(size_t nv, size_t nf);
+int mvd_mesh_incidence(const int* faces, const int* vertex_start, const int* face_start, size_t nv, size_t nf, int nscene, int* inc_start,
+                       int* inc, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+size_t mvd_mesh_label_scratch(size_t nv, size_t nf);
+int mvd_mesh_label(const int* faces, const int* vertex_start, const int* face_start, size_t nv, size_t nf, int nscene, int* vertex_component,
+                   int* face_component, int* component_start, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+int mvd_mesh_component_table(const int* vertex_component, const int* face_component, size_t nv, size_t nf, size_t ncomp, int* root, int* faces,
+                             int* vertices, mvd_stream_t stream);
+size_t mvd_mesh_topology_scratch(size_t nv, size_t nf);
+int mvd_mesh_topology(const int* faces, const int* vertex_start, const int* face_start, size_t nv, size_t nf, int nscene, const int* inc_start,
+                      const int* inc, const int* vertex_component, const int* component_start, int* totals, uint8_t* vertex_flags,
+                      void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+size_t mvd_mesh_filter_scratch(size_t nv, size_t nf);
+int mvd_mesh_filter_count(const int* faces, const uint8_t* keep, const int* vertex_start, const int* face_start, size_t nv, size_t nf,
+                          int nscene, int* new_vertex_start, int* new_face_start, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+int mvd_mesh_filter_emit(const float* vertices, const float* rgb, const int* faces, size_t nv, size_t nf, float* out_vertices, float* out_rgb,
+                         int* out_faces, int* vertex_index, int* face_index, size_t nvo, size_t nfo, const void* scratch,
+                         size_t scratch_bytes, mvd_stream_t stream);
+int mvd_mesh_vertex_normals(const float* vertices, const int* faces, const int* inc_start, const int* inc, size_t nv, size_t nf,
+                            float* normals, mvd_stream_t stream);
+int mvd_mesh_smooth(const float* vertices, const int* faces, const int* inc_start, const int* inc, const uint8_t* vertex_flags, size_t nv,
+                    size_t nf, int passes, double lam, double mu, int pin_mask, float* out, float* tmp, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

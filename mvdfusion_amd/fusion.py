@@ -36,6 +36,13 @@ pairs; both return an ``Alignment`` whose ``apply`` moves a cloud, surface sampl
 ``compare_geometry(al.apply(cloud), scan)`` measures the reconstruction and not the misalignment.  No ``ViewFusion`` method either.
 ``align_to_surface`` is the point-to-plane form of that loop (mvd_plane_icp) on the normals of the target -- what converges on a dense
 smooth surface, where point-to-point slides -- and ``fit_plane_step`` its one linearised step for known pairs.
+
+``mesh_components``, ``mesh_topology``, ``filter_mesh``, ``keep_components``, ``vertex_normals`` and ``smooth_mesh`` work on the mesh
+itself (include/mvd_hip.h: the mesh topology section): connected components by a lock-free union-find, a report of boundary,
+non-manifold and misoriented edges with the Euler characteristic, a face filter that rebases ids -- together the floater remover --,
+area-weighted vertex normals for ``write_ply``, and Taubin smoothing.  All of them rest on one deterministic vertex -> face incidence
+table built on the device; each reads back at most one small table of counts.  ``ViewFusion.mesh`` forwards ``largest``, ``min_faces``
+and ``smooth``.
 """
 import math
 from dataclasses import dataclass
@@ -1773,6 +1780,284 @@ def register_geometry(source, target, scenes=1, rotations=REGISTER_ROTATIONS, sa
     bottom = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=dev).expand(N, K, 1, 4)
     return Registration(**{f: getattr(out, f) for f in out.__dataclass_fields__}, candidates=torch.cat([refined.reshape(N, K, 3, 4), bottom], dim=2),
                         candidate_score=cand_score, candidate_inliers=cand_inliers, chosen=chosen, grid_score=grid_score)
+
+
+# ------------------------------------------------------------------------------------------------ mesh topology
+@dataclass
+class MeshComponents:
+    """What ``mesh_components`` returns.  Compact ids are the rank of a component's smallest vertex id, so components are numbered scene
+    after scene; only components with a face are numbered."""
+    vertex_component: torch.Tensor           # (nv,) int32: the compact id, -1 for a vertex no valid face uses
+    face_component: torch.Tensor             # (nf,) int32: the compact id, -1 for an invalid face
+    component_start: torch.Tensor            # (N + 1,) int32, host: scene s owns the ids [component_start[s], component_start[s + 1])
+    root: torch.Tensor                       # (ncomp,) int32: the component's smallest vertex id
+    faces: torch.Tensor                      # (ncomp,) int32: its valid faces
+    vertices: torch.Tensor                   # (ncomp,) int32: its vertices
+
+    def __len__(self):
+        return int(self.root.shape[0])
+
+    def _scene(self):
+        """(ncomp,) int64 on the device: the scene of every component."""
+        cs = self.component_start.to(self.root.device).long()
+        return torch.repeat_interleave(torch.arange(cs.numel() - 1, device=cs.device), cs[1:] - cs[:-1])
+
+    def _rank(self):
+        """(ncomp,) int64: a component's position among its scene's components ordered by faces, most first, the lower id first
+        between equal counts."""
+        n, dev = len(self), self.root.device
+        by_faces = torch.sort(-self.faces.long(), stable=True).indices
+        order = by_faces[torch.sort(self._scene()[by_faces], stable=True).indices]      # scene after scene, within a scene as above
+        pos = torch.arange(n, device=dev) - self.component_start.to(dev).long()[self._scene()[order]]
+        return torch.empty(n, dtype=torch.long, device=dev).scatter_(0, order, pos)
+
+    def select(self, keep):
+        """(ncomp,) bool per component -> (nf,) bool per face (False for an invalid face)."""
+        fc = self.face_component.long()
+        if len(self) == 0:
+            return torch.zeros_like(fc, dtype=torch.bool)
+        return (fc >= 0) & keep[fc.clamp(min=0)]
+
+    def largest(self, k=1):
+        """(nf,) bool: the faces of each scene's ``k`` components with the most faces; between equal counts the lower id wins."""
+        if int(k) != k or k < 1:
+            raise ValueError(f"k = {k}: an integer >= 1")
+        return self.select(self._rank() < int(k))
+
+
+@dataclass
+class MeshTopology:
+    """What ``mesh_topology`` returns: (N,) int32 host tensors, one value per scene, and the per-vertex bits on the mesh's device."""
+    vertices_used: torch.Tensor
+    unreferenced: torch.Tensor
+    faces_regular: torch.Tensor
+    faces_repeated: torch.Tensor
+    faces_invalid: torch.Tensor
+    edges: torch.Tensor
+    boundary_edges: torch.Tensor             # edges with one face
+    nonmanifold_edges: torch.Tensor          # edges with more than two faces
+    misoriented_edges: torch.Tensor          # edges whose two faces run along them in the same direction
+    components: torch.Tensor
+    euler: torch.Tensor                      # vertices_used - edges + faces_regular
+    vertex_flags: torch.Tensor               # (nv,) uint8: hip.TOPO_FLAG_BOUNDARY, hip.TOPO_FLAG_NONMANIFOLD
+
+    @property
+    def closed(self):
+        return self.boundary_edges == 0
+
+    @property
+    def manifold(self):
+        return self.nonmanifold_edges == 0
+
+    @property
+    def oriented(self):
+        return self.misoriented_edges == 0
+
+    @property
+    def watertight(self):
+        return self.closed & self.manifold & self.oriented
+
+
+def _topo_arrays(mesh):
+    """(vertices, faces, rgb or None, vertex_start, face_start, N) of a TriangleMesh: contiguous on the device of its vertices, the two
+    offset tables as int32 DEVICE tensors."""
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a TriangleMesh")
+    vertices, faces, rgb = mesh.vertices, mesh.faces, mesh.rgb
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"mesh: vertices of shape {tuple(vertices.shape)}, faces of shape {tuple(faces.shape)}, need (n, 3) and (m, 3)")
+    if rgb is not None and tuple(rgb.shape) != tuple(vertices.shape):
+        raise ValueError(f"mesh: rgb of shape {tuple(rgb.shape)} for vertices of shape {tuple(vertices.shape)}")
+    starts = []
+    for name, table, n in (("vertex_start", mesh.vertex_start, vertices.shape[0]), ("face_start", mesh.face_start, faces.shape[0])):
+        start = [int(v) for v in table.tolist()]
+        if len(start) < 2 or start[0] < 0 or start[-1] > n or any(a > b for a, b in zip(start, start[1:])):
+            raise ValueError(f"mesh: {name} = {start} for {n} rows")
+        starts.append(start)
+    if len(starts[0]) != len(starts[1]):
+        raise ValueError(f"mesh: vertex_start of {len(starts[0]) - 1} scenes, face_start of {len(starts[1]) - 1}")
+    dev = vertices.device
+    to_dev = lambda s: torch.tensor(s, dtype=torch.int32).to(dev)
+    return (vertices.to(dev, torch.float32).contiguous(), faces.to(dev, torch.int32).contiguous(),
+            None if rgb is None else rgb.to(dev, torch.float32).contiguous(), to_dev(starts[0]), to_dev(starts[1]), len(starts[0]) - 1)
+
+
+def _scratch(nbytes, dev):
+    return torch.empty((int(nbytes) + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def _p(t):
+    return hip.ptr(t) if t is not None and t.numel() else None
+
+
+def _incidence(faces, vertex_start, face_start, nv, N):
+    """The enqueues of mvd_mesh_incidence -> (inc_start (nv + 1,), inc (3 nf,)) int32.  No host synchronisation."""
+    L = hip.lib()
+    dev, nf = faces.device, int(faces.shape[0])
+    inc_start = torch.empty(nv + 1, dtype=torch.int32, device=dev)
+    inc = torch.empty(3 * nf, dtype=torch.int32, device=dev)
+    nbytes = int(L.mvd_mesh_incidence_scratch(nv, nf))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_mesh_incidence(_p(faces), hip.ptr(vertex_start), hip.ptr(face_start), nv, nf, N, hip.ptr(inc_start), _p(inc),
+                                   hip.ptr(scratch), nbytes, hip.stream()))
+    return inc_start, inc
+
+
+def _label(faces, vertex_start, face_start, nv, N):
+    """The enqueues of mvd_mesh_label -> (vertex_component, face_component, component_start), all on the device.  No host
+    synchronisation."""
+    L = hip.lib()
+    dev, nf = faces.device, int(faces.shape[0])
+    vc = torch.empty(nv, dtype=torch.int32, device=dev)
+    fc = torch.empty(nf, dtype=torch.int32, device=dev)
+    cs = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    nbytes = int(L.mvd_mesh_label_scratch(nv, nf))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_mesh_label(_p(faces), hip.ptr(vertex_start), hip.ptr(face_start), nv, nf, N, _p(vc), _p(fc), hip.ptr(cs), hip.ptr(scratch),
+                               nbytes, hip.stream()))
+    return vc, fc, cs
+
+
+def _topology(faces, vertex_start, face_start, nv, N, table=None):
+    """The enqueues of mvd_mesh_incidence, mvd_mesh_label and mvd_mesh_topology -> (totals (N, hip.TOPO_TOTALS) int32, vertex_flags
+    (nv,) uint8, the incidence table), on the device.  No host synchronisation."""
+    L = hip.lib()
+    dev, nf = faces.device, int(faces.shape[0])
+    inc_start, inc = table if table is not None else _incidence(faces, vertex_start, face_start, nv, N)
+    vc, _, cs = _label(faces, vertex_start, face_start, nv, N)
+    totals = torch.empty(N, hip.TOPO_TOTALS, dtype=torch.int32, device=dev)
+    flags = torch.empty(nv, dtype=torch.uint8, device=dev)
+    nbytes = int(L.mvd_mesh_topology_scratch(nv, nf))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_mesh_topology(_p(faces), hip.ptr(vertex_start), hip.ptr(face_start), nv, nf, N, hip.ptr(inc_start), _p(inc), _p(vc),
+                                  hip.ptr(cs), hip.ptr(totals), _p(flags), hip.ptr(scratch), nbytes, hip.stream()))
+    return totals, flags, (inc_start, inc)
+
+
+def mesh_components(mesh):
+    """The connected components of a TriangleMesh (include/mvd_hip.h: mvd_mesh_label has the rule) -> MeshComponents.  Two faces are
+    connected when they share a vertex id; a face with an id outside its own scene's vertices is invalid and belongs to nothing.  The
+    label of a component is its smallest vertex id, found by a lock-free union-find on the GPU; the result has the same bits run to run,
+    and a scene has the same components alone and inside a batch (only the compact ids shift).  One host read: ``component_start``."""
+    vertices, faces, _, vs, fs, N = _topo_arrays(mesh)
+    L = hip.lib()
+    dev, nv, nf = vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    vc, fc, cs = _label(faces, vs, fs, nv, N)
+    cs = cs.cpu()                                                  # the one host synchronisation
+    ncomp = int(cs[N])
+    root, nfaces, nverts = (torch.empty(ncomp, dtype=torch.int32, device=dev) for _ in range(3))
+    hip.check(L.mvd_mesh_component_table(_p(vc), _p(fc), nv, nf, ncomp, _p(root), _p(nfaces), _p(nverts), hip.stream()))
+    return MeshComponents(vertex_component=vc, face_component=fc, component_start=cs, root=root, faces=nfaces, vertices=nverts)
+
+
+def mesh_topology(mesh):
+    """What a TriangleMesh is (include/mvd_hip.h: mvd_mesh_topology has the rule) -> MeshTopology: per scene the vertices used and
+    unreferenced, the faces by class, the edges, those on a boundary (one face), non-manifold (more than two) and misoriented (two
+    faces wound alike across them), the components and the Euler characteristic; per vertex whether it lies on a boundary or a
+    non-manifold edge.  ``closed``, ``manifold``, ``oriented`` and ``watertight`` (all three) are (N,) bool.  A vertex of valence d
+    costs O(d^2): fine for a marched mesh, a limit for a caller's mesh with a huge fan.  One host read: the (N, 11) totals."""
+    vertices, faces, _, vs, fs, N = _topo_arrays(mesh)
+    totals, flags, _ = _topology(faces, vs, fs, int(vertices.shape[0]), N)
+    totals = totals.cpu()                                          # the one host synchronisation
+    return MeshTopology(**{name: totals[:, k].clone() for k, name in enumerate(hip.TOPO_FIELDS)}, vertex_flags=flags)
+
+
+def filter_mesh(mesh, keep_faces, return_index=False):
+    """The sub-mesh of the faces with ``keep_faces`` set (include/mvd_hip.h: mvd_mesh_filter_count, mvd_mesh_filter_emit): kept faces
+    and the vertices they name stay in their order, ids are rebased, ``rgb`` is carried bit for bit, the offset tables are rewritten;
+    an invalid face is never kept.  keep_faces: (nf,) bool or uint8.  With ``return_index`` also the old rows: (mesh, vertex_index,
+    face_index), int32 on the device.  One host read: the 2 (N + 1) new offsets."""
+    vertices, faces, rgb, vs, fs, N = _topo_arrays(mesh)
+    dev, nv, nf = vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    if not torch.is_tensor(keep_faces) or tuple(keep_faces.shape) != (nf,) or keep_faces.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"keep_faces: an ({nf},) bool or uint8 tensor")
+    L = hip.lib()
+    keep = keep_faces.to(dev).to(torch.uint8).contiguous()
+    nbytes = int(L.mvd_mesh_filter_scratch(nv, nf))
+    scratch = _scratch(nbytes, dev)
+    starts = torch.empty(2, N + 1, dtype=torch.int32, device=dev)
+    hip.check(L.mvd_mesh_filter_count(_p(faces), _p(keep), hip.ptr(vs), hip.ptr(fs), nv, nf, N, hip.ptr(starts[0]), hip.ptr(starts[1]),
+                                      hip.ptr(scratch), nbytes, hip.stream()))
+    starts = starts.cpu()                                          # the one host synchronisation
+    nvo, nfo = int(starts[0, N]), int(starts[1, N])
+    out_v = torch.empty(nvo, 3, dtype=torch.float32, device=dev)
+    out_c = torch.empty(nvo, 3, dtype=torch.float32, device=dev) if rgb is not None else None
+    out_f = torch.empty(nfo, 3, dtype=torch.int32, device=dev)
+    vi, fi = torch.empty(nvo, dtype=torch.int32, device=dev), torch.empty(nfo, dtype=torch.int32, device=dev)
+    hip.check(L.mvd_mesh_filter_emit(_p(vertices), _p(rgb), _p(faces), nv, nf, _p(out_v), _p(out_c), _p(out_f), _p(vi), _p(fi), nvo, nfo,
+                                     hip.ptr(scratch), nbytes, hip.stream()))
+    out = TriangleMesh(vertices=out_v, faces=out_f, rgb=out_c, vertex_start=starts[0].clone(), face_start=starts[1].clone())
+    return (out, vi, fi) if return_index else out
+
+
+def keep_components(mesh, largest=None, min_faces=None, min_fraction=None, return_index=False):
+    """The floater remover: ``mesh_components`` then ``filter_mesh``.  A component survives when it meets EVERY criterion given (at least
+    one is required):
+    largest      : it is among its scene's ``largest`` components by faces (between equal counts the lower id), an integer >= 1;
+    min_faces    : it has at least this many faces;
+    min_fraction : it has at least this fraction of its scene's valid faces, in [0, 1].
+    Returns what ``filter_mesh`` returns.  Two host reads, one per composed call."""
+    if largest is None and min_faces is None and min_fraction is None:
+        raise ValueError("keep_components: give at least one of largest, min_faces, min_fraction")
+    if largest is not None and (int(largest) != largest or largest < 1):
+        raise ValueError(f"largest = {largest}: an integer >= 1")
+    if min_faces is not None and (int(min_faces) != min_faces or min_faces < 0):
+        raise ValueError(f"min_faces = {min_faces}: an integer >= 0")
+    if min_fraction is not None and not 0.0 <= float(min_fraction) <= 1.0:
+        raise ValueError(f"min_fraction = {min_fraction}: in [0, 1]")
+    comp = mesh_components(mesh)
+    keep = torch.ones(len(comp), dtype=torch.bool, device=comp.root.device)
+    if len(comp):
+        if largest is not None:
+            keep &= comp._rank() < int(largest)
+        if min_faces is not None:
+            keep &= comp.faces >= int(min_faces)
+        if min_fraction is not None:
+            scene = comp._scene()
+            per_scene = torch.zeros(comp.component_start.numel() - 1, dtype=torch.long, device=keep.device).index_add_(0, scene, comp.faces.long())
+            keep &= comp.faces.double() >= float(min_fraction) * per_scene[scene].double()
+    return filter_mesh(mesh, comp.select(keep), return_index=return_index)
+
+
+def vertex_normals(mesh):
+    """(n, 3) fp32 unit normals per vertex of a TriangleMesh (include/mvd_hip.h: mvd_mesh_vertex_normals): the area-weighted mean of
+    the normals of the faces round the vertex -- the fp64 sum of their raw cross products in face order, divided by its length, rounded
+    once; zero for a vertex of no regular face or of zero or non-finite total area.  The winding decides the side, as for
+    ``sample_normals``.  A plain tensor, not a PointNormals: there is no neighbourhood, so ``variation`` and ``neighbours`` would mean
+    nothing.  ``write_ply(path, mesh, vertex_normals(mesh))`` saves them.  Nothing is read back from the device."""
+    vertices, faces, _, vs, fs, N = _topo_arrays(mesh)
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    inc_start, inc = _incidence(faces, vs, fs, nv, N)
+    normals = torch.empty(nv, 3, dtype=torch.float32, device=vertices.device)
+    hip.check(hip.lib().mvd_mesh_vertex_normals(_p(vertices), _p(faces), hip.ptr(inc_start), _p(inc), nv, nf, _p(normals), hip.stream()))
+    return normals
+
+
+def smooth_mesh(mesh, iters=10, lam=0.5, mu=-0.53, pin_boundary=True):
+    """Taubin smoothing of a TriangleMesh (include/mvd_hip.h: mvd_mesh_smooth has the rule) -> a TriangleMesh with new vertices and the
+    same faces, rgb and offsets.  ``iters`` pairs of umbrella passes, the first of a pair with the factor ``lam`` (it shrinks), the second
+    with ``mu`` < -lam (it inflates), 2 * iters passes in all: the staircase of a marched surface goes, the shape does not shrink as it
+    would under lam alone.  A vertex moves towards the mean of the other two vertices of every face round it (an interior neighbour counts
+    twice, a boundary neighbour once).  pin_boundary: vertices on a boundary edge stay where they are.  A vertex of no regular face, or
+    one that would read a non-finite coordinate, stays too.
+
+    iters, lam and mu are INTERFACE defaults: the usual Taubin values (pass band about 0.1), which nobody has tuned on this project's
+    meshes -- expect to.  iters in [0, 1000]; lam, mu finite.  The same bits run to run.  Nothing is read back from the device."""
+    if int(iters) != iters or not 0 <= iters <= 1000:
+        raise ValueError(f"iters = {iters}: an integer in [0, 1000]")
+    lam, mu = float(lam), float(mu)
+    if not (math.isfinite(lam) and math.isfinite(mu)):
+        raise ValueError(f"lam = {lam}, mu = {mu}: finite")
+    vertices, faces, rgb, vs, fs, N = _topo_arrays(mesh)
+    dev, nv, nf = vertices.device, int(vertices.shape[0]), int(faces.shape[0])
+    if pin_boundary:
+        _, flags, (inc_start, inc) = _topology(faces, vs, fs, nv, N)
+    else:
+        flags, (inc_start, inc) = None, _incidence(faces, vs, fs, nv, N)
+    out, tmp = torch.empty_like(vertices), torch.empty_like(vertices)
+    hip.check(hip.lib().mvd_mesh_smooth(_p(vertices), _p(faces), hip.ptr(inc_start), _p(inc), _p(flags), nv, nf, 2 * int(iters), lam, mu,
+                                        hip.TOPO_FLAG_BOUNDARY if pin_boundary else 0, _p(out), _p(tmp), hip.stream()))
+    return TriangleMesh(vertices=out, faces=mesh.faces, rgb=mesh.rgb, vertex_start=mesh.vertex_start, face_start=mesh.face_start)
 
 
 def write_ply(path, cloud, normals=None):

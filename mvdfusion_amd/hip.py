@@ -65,6 +65,11 @@ PLANE_EPS_RANK = 1e-9                                      # MVD_PLANE_EPS_RANK:
 ALIGN_MAX_ITERS = 1024                                     # the largest `iters` of mvd_align_icp
 REGISTER_MAX_H, REGISTER_MAX_K = 16384, 32                 # MVD_REGISTER_MAX_H, _MAX_K: the most hypotheses mvd_register_score / _select take; the most picked
 MESH_SPAN = 3                                              # MVD_MESH_SPAN: cells per axis a face may span before it joins its scene's oversize list
+TOPO_TOTALS = 11                                           # MVD_TOPO_TOTALS: int32 per scene that mvd_mesh_topology writes, in TOPO_FIELDS order
+TOPO_FIELDS = ("vertices_used", "unreferenced", "faces_regular", "faces_repeated", "faces_invalid", "edges", "boundary_edges",
+               "nonmanifold_edges", "misoriented_edges", "components", "euler")
+TOPO_FLAG_BOUNDARY, TOPO_FLAG_NONMANIFOLD = 1, 2           # bits of mvd_mesh_topology's vertex_flags
+SMOOTH_MAX_PASSES = 2000                                   # MVD_SMOOTH_MAX_PASSES: the most passes of mvd_mesh_smooth
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -208,6 +213,18 @@ SIGNATURES = {
     "mvd_mesh_scratch": (_sz, [_i, _i]),
     "mvd_mesh_count": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mvd_mesh_emit": (_i, [_vp] * 4 + [_i, _i, _f, _f, _f, _f, C.POINTER(_f), _vp, _vp, _vp, _sz, _sz, _vp, _sz, _vp]),
+    "mvd_mesh_incidence_scratch": (_sz, [_sz, _sz]),
+    "mvd_mesh_incidence": (_i, [_vp] * 3 + [_sz, _sz, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_mesh_label_scratch": (_sz, [_sz, _sz]),
+    "mvd_mesh_label": (_i, [_vp] * 3 + [_sz, _sz, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_mesh_component_table": (_i, [_vp, _vp, _sz, _sz, _sz, _vp, _vp, _vp, _vp]),
+    "mvd_mesh_topology_scratch": (_sz, [_sz, _sz]),
+    "mvd_mesh_topology": (_i, [_vp] * 3 + [_sz, _sz, _i] + [_vp] * 7 + [_sz, _vp]),
+    "mvd_mesh_filter_scratch": (_sz, [_sz, _sz]),
+    "mvd_mesh_filter_count": (_i, [_vp] * 4 + [_sz, _sz, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_mesh_filter_emit": (_i, [_vp] * 3 + [_sz, _sz] + [_vp] * 5 + [_sz, _sz, _vp, _sz, _vp]),
+    "mvd_mesh_vertex_normals": (_i, [_vp] * 4 + [_sz, _sz, _vp, _vp]),
+    "mvd_mesh_smooth": (_i, [_vp] * 5 + [_sz, _sz, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),

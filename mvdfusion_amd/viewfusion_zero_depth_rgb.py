@@ -674,18 +674,25 @@ class ViewFusion(nn.Module):
         return img.reshape(*latents.shape[:-3], 3, img.shape[-2], img.shape[-1])
 
     @torch.no_grad()
-    def mesh(self, latents, batch_cameras, grid=128, up=8, decode=True, **kw):
+    def mesh(self, latents, batch_cameras, grid=128, up=8, decode=True, largest=None, min_faces=None, smooth=0, **kw):
         """The sampled views as a closed triangle mesh with vertex colours: fusion.integrate_tsdf with this model's depth_scale /
         depth_shift, then fusion.extract_mesh.  latents and cameras as ``fuse`` takes them; decode: colour from ``self.decode``
         (8 S pixels per side, so up <= 8), otherwise pass ``rgb=`` or get an uncoloured mesh.  Other keywords: center, half_extent, trunc,
-        carve, foreground (integrate_tsdf) and fill (extract_mesh)."""
-        from .fusion import extract_mesh, integrate_tsdf
+        carve, foreground (integrate_tsdf) and fill (extract_mesh).
+        largest, min_faces: when either is given, fusion.keep_components drops the floaters of the extracted mesh; smooth: when > 0,
+        fusion.smooth_mesh(iters=smooth) follows.  With the defaults neither is called and the mesh is extract_mesh's own."""
+        from .fusion import extract_mesh, integrate_tsdf, keep_components, smooth_mesh
         if decode:
             kw["rgb"] = self._decoded(latents)
         fill = {"fill": kw.pop("fill")} if "fill" in kw else {}
         vol = integrate_tsdf(latents, batch_cameras, grid=grid, up=up, depth_scale=self.view_attn.depth_scale,
                              depth_shift=self.view_attn.depth_shift, **kw)
-        return extract_mesh(vol, **fill)
+        mesh = extract_mesh(vol, **fill)
+        if largest is not None or min_faces is not None:
+            mesh = keep_components(mesh, largest=largest, min_faces=min_faces)
+        if smooth:
+            mesh = smooth_mesh(mesh, iters=smooth)
+        return mesh
 
     @torch.no_grad()
     def render(self, cloud, cameras, size=256, radius=1, **kw):
