@@ -1208,6 +1208,88 @@ int mvd_mesh_smooth(const float* vertices, const int* faces, const int* inc_star
                     size_t nf, int passes, double lam, double mu, int pin_mask, float* out, float* tmp, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mesh simplification: vertex clustering (Rossignac-Borrel) with Lindstrom's quadric placement (csrc/meshsimplify.hip; host:
+ * mvdfusion_amd/fusion.py simplify_mesh).  Every vertex of a cubic cell becomes one vertex; a face survives when its three vertices
+ * fall into three cells.  Data-parallel, with a unique answer.  Not in the reference either.
+ *
+ * The mesh arrays, the face classes and the conventions are those of the mesh topology section above.  The call sequence is
+ *   mvd_mesh_incidence(faces) -> mvd_mesh_cluster_count -> host reads cluster_start[nscene] = nc -> mvd_mesh_cluster_emit ->
+ *   mvd_mesh_incidence(mapped_faces, cluster_start as the vertex offsets, nv = nc) -> mvd_mesh_cluster_dedupe ->
+ *   mvd_mesh_filter_count / _emit(out_vertices, out_rgb, mapped_faces, the second keep mask, cluster_start, nv = nc),
+ * and the filter pair drops the clusters no surviving face names and rebases the ids.
+ *
+ * mvd_mesh_cluster_count.  A MEMBER is a vertex of a scene with three finite coordinates and a non-empty list in the table of
+ *   mvd_mesh_incidence (inc_start (nv + 1) is an input; only the list lengths are read).
+ *   Box     : per scene lo_a, hi_a = the least and the greatest fp32 coordinate of its members per axis (integer atomicMin on the
+ *             order-preserving keys of the searches' grids, the greatest as the minimum of the complemented key).
+ *   Grid    : fp64 from here on.  extent_a = hi_a - lo_a; h = (the greatest extent_a) / cells.  With h > 0: n_a = clamp(floor(extent_a /
+ *             h) + 1, 1, cells) and a member's cell along axis a is i_a = clamp(floor((x_a - lo_a) / h), 0, n_a - 1), in exactly this
+ *             order, without contraction; with h == 0 (or in a scene without a member) n_a = 1 and every member has the cell 0.  The
+ *             linear id is (i_z n_y + i_y) n_x + i_x.
+ *   Clusters: occupied cells are flagged by plain stores of one value into a dense table of cells^3 words per scene (nscene * cells^3
+ *             <= 2^28), the table is scanned (the exclusive scan of the searches' grids), and a cluster's id is the rank of its
+ *             (scene, linear id): clusters are numbered scene after scene, in cell order.
+ *   vertex_cluster (nv,) int32: the id, -1 for a vertex that is no member.  cluster_start (nscene + 1) int32 DEVICE: scene s owns the
+ *   ids [cluster_start[s], cluster_start[s + 1]); the host reads cluster_start[nscene] = nc.  The call also counts the members per
+ *   cluster (an integer atomic each) and scans the counts: box, nc and these list offsets stay in the scratch for the emit call.
+ * mvd_mesh_cluster_emit: same nv, nf, nscene, cells and scratch as the count call, vertex_cluster as it wrote it, inc_start and inc of
+ *   the same mesh.
+ *   Lists   : the cluster -> member lists, ASCENDING by vertex id.  Fill (an integer atomic hands out the slot), then a rank pass: every
+ *             member counts the smaller ids of its own list and stores itself at that position.  COST: a member of a list of length L
+ *             reads L words, so a list costs L^2 reads spread over L threads, O(L) per thread; no thread is quadratic (the insertion
+ *             sort of mvd_mesh_incidence would be: a cluster of a 128^3 mesh at cells = 8 holds thousands of vertices).
+ *   Vertex  : per member (one thread, fp64, incidence-list order), over the faces of its list that name only finite vertices: the raw
+ *             cross product n = ab x ac formed exactly as mvd_mesh_vertex_normals forms it; l = sqrt((n_x n_x + n_y n_y) + n_z n_z); a
+ *             face with l == 0 or l not finite is skipped; u = n / l per component, w = l / 2, d = (u_x a_x + u_y a_y) + u_z a_z with a
+ *             the face's first corner.  Sums, one add per face each: A_v = sum (w u_r) u_c for (r, c) = xx xy xz yy yz zz and
+ *             g_v = sum (w u_r) d.
+ *   Cluster : per cluster (one thread, ascending members): c = the count; m = (sum x) / c per axis; rgb = (sum rgb) / c rounded once
+ *             to fp32; A = sum A_v, g = sum g_v; b_r = ((A_rx m_x + A_ry m_y) + A_rz m_z) - g_r, the gradient of the quadric at m up to
+ *             a factor of 2.
+ *             placement MVD_SIMPLIFY_MEAN: x = fp32(m), rank = 0, placed = MVD_SIMPLIFY_PLACED_MEAN.
+ *             placement MVD_SIMPLIFY_QUADRIC: the cyclic Jacobi of mvd_point_normals (MVD_NORMALS_SWEEPS sweeps, csrc/jacobi3.hpp) on
+ *             A gives lambda_i and e_i (column i); rank = the number of i with lambda_i > MVD_SIMPLIFY_RANK_RATIO * lambda_max
+ *             (Lindstrom's threshold; 0 when lambda_max is not positive and finite); y = m, then for i = 0, 1, 2 if kept:
+ *             t = ((e_ix b_x + e_iy b_y) + e_iz b_z) / lambda_i, y_a = y_a - t e_ia.  y is ACCEPTED when rank > 0, it is finite and
+ *             (lo_a + i_a h) - h / MVD_SIMPLIFY_BOX_SLACK_DIV <= y_a <= (lo_a + (i_a + 1) h) + h / MVD_SIMPLIFY_BOX_SLACK_DIV on every
+ *             axis, i the cluster's cell (a corner of the scene's box lies exactly on its cell's outer face and the solve lands 1e-16
+ *             beside it: hence the slack).  Accepted: x = fp32(y), placed = MVD_SIMPLIFY_PLACED_QUADRIC; otherwise x = fp32(m),
+ *             placed = MVD_SIMPLIFY_PLACED_FALLBACK.
+ *   Faces   : mapped_faces (nf, 3) int32: the cluster ids of the face's vertices (ids of the OUTPUT, global), -1 for a vertex that is no
+ *             member and for every id of an invalid face; keep (nf,) uint8: 1 iff the face is regular, its three vertices are members
+ *             and its three cluster ids are distinct.
+ *   out_vertices (nc, 3) fp32, out_rgb (nc, 3) fp32 (with rgb non-NULL; both NULL: no colour), size, rank, placed (nc,) int32.
+ *   nc is compared ON THE DEVICE with the count the count call left in the scratch: when they differ, no kernel of the call writes
+ *   anything, neither outputs nor scratch.  The host cannot know without a synchronisation, so that call returns 0.
+ * mvd_mesh_cluster_dedupe: takes mvd_mesh_incidence of mapped_faces.  A kept face walks the list of its smallest id and loses its
+ *   keep when a LOWER face row with keep set names the same unordered id set: the lowest row of a set survives (Open3D's rule; a sheet
+ *   thinner than a cell loses one of its two sides).  The rule depends on the emit call's keep only, which is read; the result goes to
+ *   keep_out (nf,) uint8, a second buffer.
+ *
+ * 1 <= cells <= MVD_SIMPLIFY_MAX_CELLS.  Scratch: mvd_mesh_cluster_scratch(nv, nf, nscene, cells) bytes serve the count and the emit
+ * call, 16-byte aligned; 0 for an argument out of range, never 0 otherwise.  Everything else as for the mesh topology section: sizes,
+ * alignment, empty meshes, clamped reads, no host synchronisation, every argument checked before anything is enqueued, a refused call
+ * writes nothing and names itself in mvd_last_error(), every scratch word that is read is written earlier in the same call (the emit
+ * call reads what the count call wrote).  Integer atomics only: the same bits run to run, and for a scene alone or in a batch. */
+#define MVD_SIMPLIFY_MAX_CELLS 256
+#define MVD_SIMPLIFY_MEAN 0
+#define MVD_SIMPLIFY_QUADRIC 1
+#define MVD_SIMPLIFY_PLACED_MEAN 0
+#define MVD_SIMPLIFY_PLACED_QUADRIC 1
+#define MVD_SIMPLIFY_PLACED_FALLBACK 2
+#define MVD_SIMPLIFY_RANK_RATIO 1e-3
+#define MVD_SIMPLIFY_BOX_SLACK_DIV 1024
+size_t mvd_mesh_cluster_scratch(size_t nv, size_t nf, int nscene, int cells);
+int mvd_mesh_cluster_count(const float* vertices, const int* vertex_start, const int* inc_start, size_t nv, size_t nf, int nscene, int cells,
+                           int* vertex_cluster, int* cluster_start, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+int mvd_mesh_cluster_emit(const float* vertices, const float* rgb, const int* faces, const int* vertex_start, const int* face_start,
+                          const int* inc_start, const int* inc, const int* vertex_cluster, size_t nv, size_t nf, int nscene, int cells,
+                          int placement, size_t nc, float* out_vertices, float* out_rgb, int* size, int* rank, int* placed, int* mapped_faces,
+                          uint8_t* keep, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+int mvd_mesh_cluster_dedupe(const int* mapped_faces, const uint8_t* keep, const int* inc_start, const int* inc, size_t nc, size_t nf,
+                            uint8_t* keep_out, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

@@ -11,7 +11,8 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ["api.hip", "gemm.hip", "gemm_plain_t0.hip", "gemm_plain_t1.hip", "gemm_plain_t2.hip", "gemm_plain_t3.hip", "gemm_plain_t4.hip",
            "gemm_ws.hip", "gemm_patch.hip", "norm.hip", "attention.hip", "elementwise.hip", "gridattn.hip", "gridattn_fused.hip", "backward.hip",
-           "fusion.hip", "tsdf.hip", "raster.hip", "nearest.hip", "align.hip", "normals.hip", "meshdist.hip", "register.hip", "meshtopo.hip"]
+           "fusion.hip", "tsdf.hip", "raster.hip", "nearest.hip", "align.hip", "normals.hip", "meshdist.hip", "register.hip", "meshtopo.hip",
+           "meshsimplify.hip"]
 LIB = os.path.join(HERE, "libmvd_hip.so")            # fp16 MFMA operands (default)
 LIB_BF16 = os.path.join(HERE, "libmvd_hip_bf16.so")  # bf16 MFMA operands (-DMVD_OPERAND_BF16)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
@@ -26,7 +27,7 @@ def _stale(out, deps):
 
 def build(force=False, verbose=True):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    common = [os.path.join(HERE, h) for h in ("common.hpp", "gridattn_common.hpp", "fusion_common.hpp", "tsdf_mesh.hpp", "nn_grid.hpp", "nn_points.hpp", "align_common.hpp")] + \
+    common = [os.path.join(HERE, h) for h in ("common.hpp", "gridattn_common.hpp", "fusion_common.hpp", "tsdf_mesh.hpp", "nn_grid.hpp", "nn_points.hpp", "align_common.hpp", "jacobi3.hpp", "mesh_common.hpp")] + \
         [os.path.join(HERE, "..", "..", "include", "mvd_hip.h")]
     gemm_hdrs = [os.path.join(HERE, h) for h in ("gemm_common.hpp", "gemm_device.hpp", "gemm_plain.hpp")]      # (the GEMM units only)
     flavours = [("", [], LIB), ("_bf16", ["-DMVD_OPERAND_BF16"], LIB_BF16)]

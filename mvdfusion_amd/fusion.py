@@ -2060,6 +2060,96 @@ def smooth_mesh(mesh, iters=10, lam=0.5, mu=-0.53, pin_boundary=True):
     return TriangleMesh(vertices=out, faces=mesh.faces, rgb=mesh.rgb, vertex_start=mesh.vertex_start, face_start=mesh.face_start)
 
 
+# ------------------------------------------------------------------------------------------------ mesh simplification
+SIMPLIFY_CELLS = 64                          # simplify_mesh's default resolution (an INTERFACE default, see its docstring)
+SIMPLIFY_PLACEMENTS = {"mean": hip.SIMPLIFY_MEAN, "quadric": hip.SIMPLIFY_QUADRIC}
+
+
+@dataclass
+class MeshClusters:
+    """What ``simplify_mesh(..., return_index=True)`` tells about every vertex of its result, int32 on the device."""
+    size: torch.Tensor                       # (n,) the input vertices that went into it
+    rank: torch.Tensor                       # (n,) the eigenvalues of its quadric above hip.SIMPLIFY_RANK_RATIO of the largest; 0 with placement "mean"
+    placed: torch.Tensor                     # (n,) hip.SIMPLIFY_PLACED_MEAN, _QUADRIC, or _FALLBACK: the quadric point was refused, the mean stands
+
+    def __len__(self):
+        return int(self.size.shape[0])
+
+
+def _check_cells(cells, N):
+    if isinstance(cells, bool) or int(cells) != cells or not 1 <= cells <= hip.SIMPLIFY_MAX_CELLS:
+        raise ValueError(f"cells = {cells}: an integer in [1, {hip.SIMPLIFY_MAX_CELLS}]")
+    if N * int(cells) ** 3 > hip.SIMPLIFY_MAX_TABLE:
+        raise ValueError(f"cells = {cells} for {N} scenes: scenes * cells^3 beyond 2^28")
+    return int(cells)
+
+
+def _cluster(vertices, rgb, faces, vs, fs, nv, N, cells, placement):
+    """The enqueues of mvd_mesh_incidence, mvd_mesh_cluster_count / _emit, mvd_mesh_incidence of the mapped faces and
+    mvd_mesh_cluster_dedupe -> a dict of device tensors and the host's cluster_start.  One host read: cluster_start."""
+    L = hip.lib()
+    dev, nf = vertices.device, int(faces.shape[0])
+    i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=dev)
+    inc_start, inc = _incidence(faces, vs, fs, nv, N)
+    vc, cs = i32(nv), i32(N + 1)
+    nbytes = int(L.mvd_mesh_cluster_scratch(nv, nf, N, cells))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_mesh_cluster_count(_p(vertices), hip.ptr(vs), hip.ptr(inc_start), nv, nf, N, cells, _p(vc), hip.ptr(cs), hip.ptr(scratch),
+                                       nbytes, hip.stream()))
+    cs_host = cs.cpu()                                             # the one host synchronisation
+    nc = int(cs_host[N])
+    out_v = torch.empty(nc, 3, dtype=torch.float32, device=dev)
+    out_c = torch.empty(nc, 3, dtype=torch.float32, device=dev) if rgb is not None else None
+    size, rank, placed, mapped = i32(nc), i32(nc), i32(nc), i32(nf, 3)
+    keep, keep2 = torch.empty(nf, dtype=torch.uint8, device=dev), torch.empty(nf, dtype=torch.uint8, device=dev)
+    hip.check(L.mvd_mesh_cluster_emit(_p(vertices), _p(rgb), _p(faces), hip.ptr(vs), hip.ptr(fs), hip.ptr(inc_start), _p(inc), _p(vc), nv, nf, N,
+                                      cells, placement, nc, _p(out_v), _p(out_c), _p(size), _p(rank), _p(placed), _p(mapped), _p(keep),
+                                      hip.ptr(scratch), nbytes, hip.stream()))
+    cinc_start, cinc = _incidence(mapped, cs, fs, nc, N)
+    hip.check(L.mvd_mesh_cluster_dedupe(_p(mapped), _p(keep), hip.ptr(cinc_start), _p(cinc), nc, nf, _p(keep2), hip.stream()))
+    return dict(vertex_cluster=vc, cluster_start=cs_host, vertices=out_v, rgb=out_c, size=size, rank=rank, placed=placed, mapped_faces=mapped,
+                keep=keep, keep_deduped=keep2)
+
+
+def simplify_mesh(mesh, cells=SIMPLIFY_CELLS, placement="quadric", return_index=False):
+    """Vertex clustering of a TriangleMesh (include/mvd_hip.h: the mesh simplification section has every rule) -> a TriangleMesh with
+    fewer vertices and faces.  Each scene's box is cut into cubic cells, ``cells`` along its longest axis; the vertices of a cell become
+    one vertex with their mean colour; a face survives when its three vertices fall into three cells, and of several faces on the same
+    three vertices the first (so a sheet thinner than a cell loses one of its two sides).  A vertex that no face uses, one with a
+    non-finite coordinate, and every face that names one, vanish.
+    placement: "quadric" puts the vertex where the planes of the faces round its members meet (Lindstrom), as far as they determine it,
+    and at the members' mean along the rest, so corners and creases stay where "mean" -- the plain mean of the members -- rounds them
+    off; a quadric point outside its own cell falls back to the mean.  On smooth regions the quadric point is no closer to the surface
+    than the mean: a UV sphere of radius 0.45 has a worst radius error of 0.0128 / 0.0030 / 0.0011 at cells = 4 / 8 / 16 either way.
+    return_index: also (mesh, vertex_cluster, face_index, clusters) -- vertex_cluster (nv,) int32 the output vertex every input vertex
+    went to, -1 for none; face_index int32 the input rows of the output faces; clusters a MeshClusters per output vertex.
+
+    ``cells`` = 64 is an INTERFACE default nobody has tuned on this project's meshes -- expect to; an integer in [1, 256] with
+    scenes * cells^3 <= 2^28.  NOT promised: clustering preserves neither manifoldness nor closedness --
+    ``mesh_topology(simplify_mesh(m))`` is how a caller finds out.  No edge collapse, no target face count, no texture or UV handling, no
+    boundary-preserving weights.  The same bits run to run, and for a scene alone or in a batch.  Two host reads: the cluster count and
+    the filter's offsets."""
+    if placement not in SIMPLIFY_PLACEMENTS:
+        raise ValueError(f"placement = {placement!r}: one of {sorted(SIMPLIFY_PLACEMENTS)}")
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a TriangleMesh")
+    cells = _check_cells(cells, int(mesh.vertex_start.numel()) - 1)
+    vertices, faces, rgb, vs, fs, N = _topo_arrays(mesh)
+    nv = int(vertices.shape[0])
+    c = _cluster(vertices, rgb, faces, vs, fs, nv, N, cells, SIMPLIFY_PLACEMENTS[placement])
+    coarse = TriangleMesh(vertices=c["vertices"], faces=c["mapped_faces"], rgb=c["rgb"], vertex_start=c["cluster_start"], face_start=mesh.face_start)
+    out, vi, fi = filter_mesh(coarse, c["keep_deduped"], return_index=True)
+    if not return_index:
+        return out
+    nc = int(c["vertices"].shape[0])
+    new_id = torch.full((nc + 1,), -1, dtype=torch.int32, device=vertices.device)      # (the spare row takes the non-members)
+    new_id[vi.long()] = torch.arange(vi.numel(), dtype=torch.int32, device=vertices.device)
+    vc = c["vertex_cluster"].long()
+    vertex_cluster = new_id[torch.where(vc >= 0, vc, torch.full_like(vc, nc))]
+    pick = lambda t: t[vi.long()]
+    return out, vertex_cluster, fi, MeshClusters(size=pick(c["size"]), rank=pick(c["rank"]), placed=pick(c["placed"]))
+
+
 def write_ply(path, cloud, normals=None):
     """Binary little-endian PLY: float x y z per vertex, and uchar red green blue (round(255 rgb)) when the cloud has colour.  A
     TriangleMesh is written the same way from its vertices, followed by ``element face`` with ``property list uchar int vertex_indices``.

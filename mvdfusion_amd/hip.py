@@ -70,6 +70,12 @@ TOPO_FIELDS = ("vertices_used", "unreferenced", "faces_regular", "faces_repeated
                "nonmanifold_edges", "misoriented_edges", "components", "euler")
 TOPO_FLAG_BOUNDARY, TOPO_FLAG_NONMANIFOLD = 1, 2           # bits of mvd_mesh_topology's vertex_flags
 SMOOTH_MAX_PASSES = 2000                                   # MVD_SMOOTH_MAX_PASSES: the most passes of mvd_mesh_smooth
+SIMPLIFY_MAX_CELLS = 256                                   # MVD_SIMPLIFY_MAX_CELLS: the most cells per axis of mvd_mesh_cluster_count
+SIMPLIFY_MEAN, SIMPLIFY_QUADRIC = 0, 1                     # `placement` of mvd_mesh_cluster_emit
+SIMPLIFY_PLACED_MEAN, SIMPLIFY_PLACED_QUADRIC, SIMPLIFY_PLACED_FALLBACK = 0, 1, 2      # its `placed` codes
+SIMPLIFY_RANK_RATIO = 1e-3                                 # MVD_SIMPLIFY_RANK_RATIO: an eigenvalue is kept above this share of the largest
+SIMPLIFY_BOX_SLACK_DIV = 1024                              # MVD_SIMPLIFY_BOX_SLACK_DIV: a cell's box is grown by h / this on each side
+SIMPLIFY_MAX_TABLE = 2 ** 28                               # the most words nscene * cells^3 of the dense cell table
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -225,6 +231,10 @@ SIGNATURES = {
     "mvd_mesh_filter_emit": (_i, [_vp] * 3 + [_sz, _sz] + [_vp] * 5 + [_sz, _sz, _vp, _sz, _vp]),
     "mvd_mesh_vertex_normals": (_i, [_vp] * 4 + [_sz, _sz, _vp, _vp]),
     "mvd_mesh_smooth": (_i, [_vp] * 5 + [_sz, _sz, _i, C.c_double, C.c_double, _i, _vp, _vp, _vp]),
+    "mvd_mesh_cluster_scratch": (_sz, [_sz, _sz, _i, _i]),
+    "mvd_mesh_cluster_count": (_i, [_vp] * 3 + [_sz, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_mesh_cluster_emit": (_i, [_vp] * 8 + [_sz, _sz, _i, _i, _i, _sz] + [_vp] * 8 + [_sz, _vp]),
+    "mvd_mesh_cluster_dedupe": (_i, [_vp] * 4 + [_sz, _sz, _vp, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),

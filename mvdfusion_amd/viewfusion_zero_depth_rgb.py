@@ -674,14 +674,15 @@ class ViewFusion(nn.Module):
         return img.reshape(*latents.shape[:-3], 3, img.shape[-2], img.shape[-1])
 
     @torch.no_grad()
-    def mesh(self, latents, batch_cameras, grid=128, up=8, decode=True, largest=None, min_faces=None, smooth=0, **kw):
+    def mesh(self, latents, batch_cameras, grid=128, up=8, decode=True, largest=None, min_faces=None, smooth=0, simplify=None, **kw):
         """The sampled views as a closed triangle mesh with vertex colours: fusion.integrate_tsdf with this model's depth_scale /
         depth_shift, then fusion.extract_mesh.  latents and cameras as ``fuse`` takes them; decode: colour from ``self.decode``
         (8 S pixels per side, so up <= 8), otherwise pass ``rgb=`` or get an uncoloured mesh.  Other keywords: center, half_extent, trunc,
         carve, foreground (integrate_tsdf) and fill (extract_mesh).
         largest, min_faces: when either is given, fusion.keep_components drops the floaters of the extracted mesh; smooth: when > 0,
-        fusion.smooth_mesh(iters=smooth) follows.  With the defaults neither is called and the mesh is extract_mesh's own."""
-        from .fusion import extract_mesh, integrate_tsdf, keep_components, smooth_mesh
+        fusion.smooth_mesh(iters=smooth) follows; simplify: when given, fusion.simplify_mesh(cells=simplify) comes last, after floater
+        removal and smoothing.  With the defaults none is called and the mesh is extract_mesh's own."""
+        from .fusion import extract_mesh, integrate_tsdf, keep_components, simplify_mesh, smooth_mesh
         if decode:
             kw["rgb"] = self._decoded(latents)
         fill = {"fill": kw.pop("fill")} if "fill" in kw else {}
@@ -692,6 +693,8 @@ class ViewFusion(nn.Module):
             mesh = keep_components(mesh, largest=largest, min_faces=min_faces)
         if smooth:
             mesh = smooth_mesh(mesh, iters=smooth)
+        if simplify is not None:
+            mesh = simplify_mesh(mesh, cells=simplify)
         return mesh
 
     @torch.no_grad()
