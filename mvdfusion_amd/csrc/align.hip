@@ -431,25 +431,25 @@ struct AlignPlan {
   size_t off_partial, off_nn, nn_bytes, bytes;
 };
 
-// false: an argument is out of range
-static bool al_plan(size_t nq, size_t nt, int nscene, int method, int grid, AlignPlan& p, int sums = kAlSums, bool mesh = false) {
-  p = AlignPlan{};
+// bytes == 0: an argument is out of range
+static AlignPlan al_plan(size_t nq, size_t nt, int nscene, int method, int grid, int sums, bool mesh) {
+  AlignPlan p{};
   if (nscene < 1 || nscene > 65535 || nq > 0x7fffffffull || nt > 0x7fffffffull || method < MVD_NN_AUTO || method > MVD_NN_GRID || grid < 0 ||
       grid > 256)
-    return false;
-  if (method != MVD_NN_BRUTE && (unsigned long long)nscene * grid * grid * grid > 0x7fffffffull) return false;
+    return p;
+  if (method != MVD_NN_BRUTE && (unsigned long long)nscene * grid * grid * grid > 0x7fffffffull) return p;
   // (the limit of mvd_nearest_on_mesh's grid; MVD_NN_AUTO takes the grid at such a size whatever nscene)
-  if (mesh && method != MVD_NN_BRUTE && (unsigned long long)nt * MVD_MESH_SPAN * MVD_MESH_SPAN * MVD_MESH_SPAN > 0x7fffffffull) return false;
+  if (mesh && method != MVD_NN_BRUTE && (unsigned long long)nt * MVD_MESH_SPAN * MVD_MESH_SPAN * MVD_MESH_SPAN > 0x7fffffffull) return p;
   p.nwg = (unsigned)((nq + kAlChunk - 1) / kAlChunk) + (unsigned)nscene;
   p.off_partial = al_up16((size_t)(nscene + 1) * sizeof(unsigned));
   p.off_nn = p.off_partial + al_up16((size_t)p.nwg * sums * sizeof(double));
   p.nn_bytes = mesh ? mvd_nearest_on_mesh_scratch(nt, nscene, method, grid) : mvd_nearest_points_scratch(nt, nscene, method, grid);      // (nt: nf)
   p.bytes = p.off_nn + p.nn_bytes;
-  return true;
+  return p;
 }
 
 static FitArgs al_args(const AlignPlan& p, void* scratch, const float* moved, const int* start, const float* target, const int* index,
-                       const float* dist2, size_t n, size_t nt, int nscene, float max_d2, const float* normals = nullptr) {
+                       const float* dist2, size_t n, size_t nt, int nscene, float max_d2, const float* normals) {
   char* base = (char*)scratch;
   return FitArgs{moved, target, start, index, dist2, (unsigned*)base, (double*)(base + p.off_partial), (long long)n, (long long)nt, nscene, p.nwg, max_d2,
                  normals};
@@ -462,7 +462,7 @@ static void al_launch_map(const FitArgs& a, hipStream_t st) {
 }
 
 // previous: the history row before this one (its scale is carried on), or NULL for the first
-template <class Fit = PointFit>
+template <class Fit>
 static void al_launch_fit(const FitArgs& a, int flags, double* transform, double* history, const double* previous, hipStream_t st) {
   hipLaunchKernelGGL(accumulate_kernel<Fit>, dim3(a.nwg), dim3(kAlThreads), 0, st, a);
   hipLaunchKernelGGL(solve_kernel<Fit>, dim3(a.nscene), dim3(kAlThreads), 0, st, a, flags, transform, history, previous);
@@ -472,11 +472,138 @@ static void al_launch_apply(const float* src, const int* start, size_t n, int ns
   if (n > 0) hipLaunchKernelGGL(apply_kernel, dim3(cdiv((long)n, kAlThreads)), dim3(kAlThreads), 0, st, src, start, (long long)n, nscene, transform, out);
 }
 
+// One fit of given pairs: mvd_align_fit (normals == NULL) and mvd_plane_fit.  flags_are: the flags the entry takes, in its message's words.
+template <class Fit>
+static int al_fit(const char* fn, int allowed_flags, const char* flags_are, const float* moved, const int* start, const float* target,
+                  const float* normals, const int* index, const float* dist2, size_t n, size_t nt, int nscene, int flags, float max_dist2,
+                  double* transform, double* history_row, void* scratch, size_t scratch_bytes, mvd_stream_t stream) {
+  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
+  MVD_CHECK_ARG(n <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: n=%zu, nt=%zu beyond 2^31 - 1", fn, n, nt);
+  MVD_CHECK_ARG((flags & ~allowed_flags) == 0, "%s: flags=%d (%s)", fn, flags, flags_are);
+  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
+  MVD_CHECK_ARG(start && transform && history_row && al_aligned(transform, 8) && al_aligned(history_row, 8),
+                "%s: null start, null or misaligned transform or history_row", fn);
+  MVD_CHECK_ARG(moved || n == 0, "%s: null moved with n=%zu", fn, n);
+  if (std::is_same<Fit, PlaneFit>::value) MVD_CHECK_ARG((target && normals) || nt == 0, "%s: null target or normals with nt=%zu", fn, nt);
+  else MVD_CHECK_ARG(target || nt == 0, "%s: null target with nt=%zu", fn, nt);
+  const AlignPlan p = al_plan(n, 0, nscene, MVD_NN_BRUTE, 0, Fit::kSums, false);
+  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
+                scratch_bytes, p.bytes);
+  const FitArgs a = al_args(p, scratch, moved, start, target, index, dist2, n, nt, nscene, max_dist2, normals);
+  al_launch_map(a, (hipStream_t)stream);
+  al_launch_fit<Fit>(a, flags, transform, history_row, nullptr, (hipStream_t)stream);
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
+// What an ICP loop searches: the moved source, the target's arrays, the checks that name them, and the exported search of one against the
+// other (BUILD once, QUERY per row).  nn: the search's part of the scratch, placed by al_icp.
+struct PointSearch {
+  static constexpr bool kMesh = false;
+  float* moved;
+  const int* source_start;
+  const float* target;
+  const int* target_start;
+  size_t nq, nt;
+  int nscene, method, grid, *index;
+  float* dist2;
+  mvd_stream_t stream;
+  void* nn;
+  size_t nn_bytes;
+  size_t size() const { return nt; }
+  int check(const char* fn, const float* source) const {
+    MVD_CHECK_ARG(nq <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: nq=%zu, nt=%zu beyond 2^31 - 1", fn, nq, nt);
+    MVD_CHECK_ARG(source_start && target_start, "%s: null source_start or target_start", fn);
+    MVD_CHECK_ARG((source && moved && index && dist2) || nq == 0, "%s: null source, moved, index or dist2 with nq=%zu", fn, nq);
+    return 0;
+  }
+  void too_large(const char* fn) const { mvd_set_error("%s: nscene * grid^3 cells beyond 2^31 - 1 (nscene=%d, grid=%d)", fn, nscene, grid); }
+  int operator()(int stages) const {
+    return mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, nn_bytes, stages,
+                                     stream);
+  }
+};
+
+struct MeshSearch {
+  static constexpr bool kMesh = true;
+  float* moved;
+  const int* source_start;
+  const float* vertices;
+  const int *faces, *face_start;
+  size_t nq, nv, nf;
+  int nscene, method, grid, *face;
+  float *dist2, *point, *normal;
+  mvd_stream_t stream;
+  void* nn;
+  size_t nn_bytes;
+  size_t size() const { return nf; }
+  int check(const char* fn, const float* source) const {
+    MVD_CHECK_ARG(nq <= 0x7fffffffull && nv <= 0x7fffffffull && nf <= 0x7fffffffull, "%s: nq=%zu, nv=%zu, nf=%zu beyond 2^31 - 1", fn, nq, nv, nf);
+    MVD_CHECK_ARG(source_start && face_start, "%s: null source_start or face_start", fn);
+    MVD_CHECK_ARG((source && moved && face && dist2 && point && normal) || nq == 0, "%s: null source, moved, face, dist2, point or normal with nq=%zu",
+                  fn, nq);
+    MVD_CHECK_ARG(faces || nf == 0, "%s: null faces with nf=%zu", fn, nf);
+    MVD_CHECK_ARG(vertices || nv == 0, "%s: null vertices with nv=%zu", fn, nv);
+    return 0;
+  }
+  void too_large(const char* fn) const {
+    mvd_set_error("%s: nscene * grid^3 cells or nf * %d references beyond 2^31 - 1 (nscene=%d, grid=%d, nf=%zu)", fn,
+                  MVD_MESH_SPAN * MVD_MESH_SPAN * MVD_MESH_SPAN, nscene, grid, nf);
+  }
+  // (the search checks its own arguments before it enqueues anything, so a refusal of its own has written nothing either)
+  int operator()(int stages) const {
+    return mvd_nearest_on_mesh_stages(moved, source_start, vertices, faces, face_start, nq, nv, nf, nscene, method, grid, face, dist2, point,
+                                      nullptr, nullptr, normal, nn, nn_bytes, stages, stream);
+  }
+};
+
+static_assert(MVD_PLANE_NO_STEP == MVD_ALIGN_NO_STEP, "the loop marks its last row with one flag for both fits");
+
+// THE loop of mvd_align_icp, mvd_plane_icp and mvd_mesh_icp (the header has the rule), with a fit and a search plugged in.  The entry has
+// run s.check() and the null checks of its own arrays; every check, there and here, comes before the first enqueue.  Row i of s.moved is
+// fitted to target[index[i]] (index == NULL: target[i]) and, by PlaneFit, the normal there.  flags: MVD_ALIGN_SCALE or 0.
+template <class Fit, class Search>
+static int al_icp(const char* fn, Search s, const float* source, int iters, int flags, float max_dist2, double* transform, double* history,
+                  void* scratch, size_t scratch_bytes, const float* target, const int* index, size_t nt, const float* normals) {
+  MVD_CHECK_ARG(s.method >= MVD_NN_AUTO && s.method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, s.method);
+  MVD_CHECK_ARG(s.grid >= 0 && s.grid <= 256, "%s: grid=%d outside [0, 256]", fn, s.grid);
+  MVD_CHECK_ARG(s.nscene >= 1 && s.nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, s.nscene);
+  MVD_CHECK_ARG(iters >= 0 && iters <= MVD_ALIGN_MAX_ITERS, "%s: iters=%d outside [0, %d]", fn, iters, MVD_ALIGN_MAX_ITERS);
+  MVD_CHECK_ARG((flags & ~MVD_ALIGN_SCALE) == 0, "%s: flags=%d (MVD_ALIGN_SCALE or 0)", fn, flags);
+  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
+  MVD_CHECK_ARG(transform && history && al_aligned(transform, 8) && al_aligned(history, 8), "%s: null or misaligned transform or history", fn);
+  const AlignPlan p = al_plan(s.nq, s.size(), s.nscene, s.method, s.grid, Fit::kSums, Search::kMesh);
+  if (!p.bytes) return s.too_large(fn), -1;
+  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
+                scratch_bytes, p.bytes);
+  const hipStream_t st = (hipStream_t)s.stream;
+  s.nn = p.nn_bytes ? (void*)((char*)scratch + p.off_nn) : nullptr, s.nn_bytes = p.nn_bytes;
+  const FitArgs a = al_args(p, scratch, s.moved, s.source_start, target, index, s.dist2, s.nq, nt, s.nscene, max_dist2, normals);
+  int rc = s(MVD_NN_BUILD);
+  if (rc == 0) al_launch_map(a, st);
+  const size_t row = (size_t)s.nscene * Fit::kHistory;
+  for (int k = 0; k <= iters && rc == 0; ++k) {      // row k: the pairs under the transform before step k; the last row has no step
+    al_launch_apply(source, s.source_start, s.nq, s.nscene, transform, s.moved, st);
+    rc = s(MVD_NN_QUERY);
+    if (rc != 0) break;      // (its argument checks are this function's own, so only a failed enqueue gets here: nothing is fitted to it)
+    // (the row before: PointFit carries its scale on, PlaneFit does not look)
+    al_launch_fit<Fit>(a, k < iters ? flags : (flags | MVD_ALIGN_NO_STEP), transform, history + (size_t)k * row,
+                       k ? history + (size_t)(k - 1) * row : nullptr, st);
+  }
+  if (rc != 0) {
+    char why[400];
+    snprintf(why, sizeof(why), "%s", mvd_last_error());
+    mvd_set_error("%s: %s", fn, why);
+    return rc;
+  }
+  MVD_CHECK_LAUNCH(fn);
+  return 0;
+}
+
 }  // namespace
 
 extern "C" size_t mvd_align_scratch(size_t nq, size_t nt, int nscene, int method, int grid) {
-  AlignPlan p;
-  return al_plan(nq, nt, nscene, method, grid, p) ? p.bytes : 0;
+  return al_plan(nq, nt, nscene, method, grid, kAlSums, false).bytes;
 }
 
 extern "C" int mvd_align_solve(const double* sums, int flags, double* step, double* scale) {
@@ -502,73 +629,23 @@ extern "C" int mvd_align_apply(const float* src, const int* src_start, size_t n,
 extern "C" int mvd_align_fit(const float* moved, const int* start, const float* target, const int* index, const float* dist2, size_t n,
                              size_t nt, int nscene, int flags, float max_dist2, double* transform, double* history_row, void* scratch,
                              size_t scratch_bytes, mvd_stream_t stream) {
-  const char* fn = "mvd_align_fit";
-  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
-  MVD_CHECK_ARG(n <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: n=%zu, nt=%zu beyond 2^31 - 1", fn, n, nt);
-  MVD_CHECK_ARG((flags & ~(MVD_ALIGN_SCALE | MVD_ALIGN_NO_STEP)) == 0, "%s: flags=%d (an OR of MVD_ALIGN_SCALE and MVD_ALIGN_NO_STEP)", fn, flags);
-  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
-  MVD_CHECK_ARG(start && transform && history_row && al_aligned(transform, 8) && al_aligned(history_row, 8),
-                "%s: null start, null or misaligned transform or history_row", fn);
-  MVD_CHECK_ARG(moved || n == 0, "%s: null moved with n=%zu", fn, n);
-  MVD_CHECK_ARG(target || nt == 0, "%s: null target with nt=%zu", fn, nt);
-  AlignPlan p;
-  al_plan(n, 0, nscene, MVD_NN_BRUTE, 0, p);
-  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
-                scratch_bytes, p.bytes);
-  const FitArgs a = al_args(p, scratch, moved, start, target, index, dist2, n, nt, nscene, max_dist2);
-  al_launch_map(a, (hipStream_t)stream);
-  al_launch_fit(a, flags, transform, history_row, nullptr, (hipStream_t)stream);
-  MVD_CHECK_LAUNCH(fn);
-  return 0;
+  return al_fit<PointFit>("mvd_align_fit", MVD_ALIGN_SCALE | MVD_ALIGN_NO_STEP, "an OR of MVD_ALIGN_SCALE and MVD_ALIGN_NO_STEP", moved, start, target,
+                          nullptr, index, dist2, n, nt, nscene, flags, max_dist2, transform, history_row, scratch, scratch_bytes, stream);
 }
 
 extern "C" int mvd_align_icp(const float* source, const int* source_start, const float* target, const int* target_start, size_t nq, size_t nt,
                              int nscene, int method, int grid, int iters, int flags, float max_dist2, double* transform, double* history,
                              float* moved, int* index, float* dist2, void* scratch, size_t scratch_bytes, mvd_stream_t stream) {
   const char* fn = "mvd_align_icp";
-  MVD_CHECK_ARG(method >= MVD_NN_AUTO && method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, method);
-  MVD_CHECK_ARG(grid >= 0 && grid <= 256, "%s: grid=%d outside [0, 256]", fn, grid);
-  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
-  MVD_CHECK_ARG(iters >= 0 && iters <= MVD_ALIGN_MAX_ITERS, "%s: iters=%d outside [0, %d]", fn, iters, MVD_ALIGN_MAX_ITERS);
-  MVD_CHECK_ARG(nq <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: nq=%zu, nt=%zu beyond 2^31 - 1", fn, nq, nt);
-  MVD_CHECK_ARG((flags & ~MVD_ALIGN_SCALE) == 0, "%s: flags=%d (MVD_ALIGN_SCALE or 0)", fn, flags);
-  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
-  MVD_CHECK_ARG(source_start && target_start, "%s: null source_start or target_start", fn);
-  MVD_CHECK_ARG(transform && history && al_aligned(transform, 8) && al_aligned(history, 8), "%s: null or misaligned transform or history", fn);
-  MVD_CHECK_ARG((source && moved && index && dist2) || nq == 0, "%s: null source, moved, index or dist2 with nq=%zu", fn, nq);
+  const PointSearch search{moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, stream};
+  if (search.check(fn, source) != 0) return -1;
   MVD_CHECK_ARG(target || nt == 0, "%s: null target with nt=%zu", fn, nt);
-  AlignPlan p;
-  MVD_CHECK_ARG(al_plan(nq, nt, nscene, method, grid, p), "%s: nscene * grid^3 cells beyond 2^31 - 1 (nscene=%d, grid=%d)", fn, nscene, grid);
-  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
-                scratch_bytes, p.bytes);
-  const hipStream_t st = (hipStream_t)stream;
-  void* nn = p.nn_bytes ? (void*)((char*)scratch + p.off_nn) : nullptr;
-  const FitArgs a = al_args(p, scratch, moved, source_start, target, index, dist2, nq, nt, nscene, max_dist2);
-  int rc = mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, p.nn_bytes,
-                                     MVD_NN_BUILD, stream);
-  if (rc == 0) al_launch_map(a, st);
-  const size_t row = (size_t)nscene * MVD_ALIGN_HISTORY;
-  for (int k = 0; k <= iters && rc == 0; ++k) {      // row k: the pairs under the transform before step k; the last row has no step
-    al_launch_apply(source, source_start, nq, nscene, transform, moved, st);
-    rc = mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, p.nn_bytes,
-                                   MVD_NN_QUERY, stream);
-    if (rc != 0) break;      // (its argument checks are this function's own, so only a failed enqueue gets here: nothing is fitted to it)
-    al_launch_fit(a, k < iters ? flags : (flags | MVD_ALIGN_NO_STEP), transform, history + (size_t)k * row, k ? history + (size_t)(k - 1) * row : nullptr, st);
-  }
-  if (rc != 0) {
-    char why[400];
-    snprintf(why, sizeof(why), "%s", mvd_last_error());
-    mvd_set_error("%s: %s", fn, why);
-    return rc;
-  }
-  MVD_CHECK_LAUNCH(fn);
-  return 0;
+  return al_icp<PointFit>(fn, search, source, iters, flags, max_dist2, transform, history, scratch, scratch_bytes, target, index, nt, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- point to plane: entries
 extern "C" size_t mvd_plane_scratch(size_t nq, size_t nt, int nscene, int method, int grid) {
-  AlignPlan p;
-  return al_plan(nq, nt, nscene, method, grid, p, kPlSums) ? p.bytes : 0;
+  return al_plan(nq, nt, nscene, method, grid, kPlSums, false).bytes;
 }
 
 extern "C" int mvd_plane_solve(const double* sums, double* step, int* rank) {
@@ -581,24 +658,8 @@ extern "C" int mvd_plane_solve(const double* sums, double* step, int* rank) {
 extern "C" int mvd_plane_fit(const float* moved, const int* start, const float* target, const float* normals, const int* index,
                              const float* dist2, size_t n, size_t nt, int nscene, int flags, float max_dist2, double* transform,
                              double* history_row, void* scratch, size_t scratch_bytes, mvd_stream_t stream) {
-  const char* fn = "mvd_plane_fit";
-  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
-  MVD_CHECK_ARG(n <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: n=%zu, nt=%zu beyond 2^31 - 1", fn, n, nt);
-  MVD_CHECK_ARG((flags & ~MVD_PLANE_NO_STEP) == 0, "%s: flags=%d (MVD_PLANE_NO_STEP or 0)", fn, flags);
-  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
-  MVD_CHECK_ARG(start && transform && history_row && al_aligned(transform, 8) && al_aligned(history_row, 8),
-                "%s: null start, null or misaligned transform or history_row", fn);
-  MVD_CHECK_ARG(moved || n == 0, "%s: null moved with n=%zu", fn, n);
-  MVD_CHECK_ARG((target && normals) || nt == 0, "%s: null target or normals with nt=%zu", fn, nt);
-  AlignPlan p;
-  al_plan(n, 0, nscene, MVD_NN_BRUTE, 0, p, kPlSums);
-  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
-                scratch_bytes, p.bytes);
-  const FitArgs a = al_args(p, scratch, moved, start, target, index, dist2, n, nt, nscene, max_dist2, normals);
-  al_launch_map(a, (hipStream_t)stream);
-  al_launch_fit<PlaneFit>(a, flags, transform, history_row, nullptr, (hipStream_t)stream);
-  MVD_CHECK_LAUNCH(fn);
-  return 0;
+  return al_fit<PlaneFit>("mvd_plane_fit", MVD_PLANE_NO_STEP, "MVD_PLANE_NO_STEP or 0", moved, start, target, normals, index, dist2, n, nt, nscene,
+                          flags, max_dist2, transform, history_row, scratch, scratch_bytes, stream);
 }
 
 extern "C" int mvd_plane_icp(const float* source, const int* source_start, const float* target, const int* target_start, const float* normals,
@@ -606,48 +667,15 @@ extern "C" int mvd_plane_icp(const float* source, const int* source_start, const
                              double* history, float* moved, int* index, float* dist2, void* scratch, size_t scratch_bytes,
                              mvd_stream_t stream) {
   const char* fn = "mvd_plane_icp";
-  MVD_CHECK_ARG(method >= MVD_NN_AUTO && method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, method);
-  MVD_CHECK_ARG(grid >= 0 && grid <= 256, "%s: grid=%d outside [0, 256]", fn, grid);
-  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
-  MVD_CHECK_ARG(iters >= 0 && iters <= MVD_ALIGN_MAX_ITERS, "%s: iters=%d outside [0, %d]", fn, iters, MVD_ALIGN_MAX_ITERS);
-  MVD_CHECK_ARG(nq <= 0x7fffffffull && nt <= 0x7fffffffull, "%s: nq=%zu, nt=%zu beyond 2^31 - 1", fn, nq, nt);
-  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
-  MVD_CHECK_ARG(source_start && target_start, "%s: null source_start or target_start", fn);
-  MVD_CHECK_ARG(transform && history && al_aligned(transform, 8) && al_aligned(history, 8), "%s: null or misaligned transform or history", fn);
-  MVD_CHECK_ARG((source && moved && index && dist2) || nq == 0, "%s: null source, moved, index or dist2 with nq=%zu", fn, nq);
+  const PointSearch search{moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, stream};
+  if (search.check(fn, source) != 0) return -1;
   MVD_CHECK_ARG((target && normals) || nt == 0, "%s: null target or normals with nt=%zu", fn, nt);
-  AlignPlan p;
-  MVD_CHECK_ARG(al_plan(nq, nt, nscene, method, grid, p, kPlSums), "%s: nscene * grid^3 cells beyond 2^31 - 1 (nscene=%d, grid=%d)", fn, nscene, grid);
-  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
-                scratch_bytes, p.bytes);
-  const hipStream_t st = (hipStream_t)stream;
-  void* nn = p.nn_bytes ? (void*)((char*)scratch + p.off_nn) : nullptr;
-  const FitArgs a = al_args(p, scratch, moved, source_start, target, index, dist2, nq, nt, nscene, max_dist2, normals);
-  int rc = mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, p.nn_bytes,
-                                     MVD_NN_BUILD, stream);
-  if (rc == 0) al_launch_map(a, st);
-  const size_t row = (size_t)nscene * MVD_PLANE_HISTORY;
-  for (int k = 0; k <= iters && rc == 0; ++k) {      // row k: the pairs under the transform before step k; the last row has no step
-    al_launch_apply(source, source_start, nq, nscene, transform, moved, st);
-    rc = mvd_nearest_points_stages(moved, source_start, target, target_start, nq, nt, nscene, method, grid, index, dist2, nn, p.nn_bytes,
-                                   MVD_NN_QUERY, stream);
-    if (rc != 0) break;
-    al_launch_fit<PlaneFit>(a, k < iters ? 0 : MVD_PLANE_NO_STEP, transform, history + (size_t)k * row, nullptr, st);
-  }
-  if (rc != 0) {
-    char why[400];
-    snprintf(why, sizeof(why), "%s", mvd_last_error());
-    mvd_set_error("%s: %s", fn, why);
-    return rc;
-  }
-  MVD_CHECK_LAUNCH(fn);
-  return 0;
+  return al_icp<PlaneFit>(fn, search, source, iters, 0, max_dist2, transform, history, scratch, scratch_bytes, target, index, nt, normals);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- mesh target: entries
 extern "C" size_t mvd_mesh_icp_scratch(size_t nq, size_t nf, int nscene, int method, int grid) {
-  AlignPlan p;
-  return al_plan(nq, nf, nscene, method, grid, p, kPlSums, true) ? p.bytes : 0;
+  return al_plan(nq, nf, nscene, method, grid, kPlSums, true).bytes;
 }
 
 extern "C" int mvd_mesh_icp(const float* source, const int* source_start, const float* vertices, const int* faces, const int* face_start,
@@ -655,46 +683,8 @@ extern "C" int mvd_mesh_icp(const float* source, const int* source_start, const 
                             double* history, float* moved, int* face, float* dist2, float* point, float* normal, void* scratch,
                             size_t scratch_bytes, mvd_stream_t stream) {
   const char* fn = "mvd_mesh_icp";
-  MVD_CHECK_ARG(method >= MVD_NN_AUTO && method <= MVD_NN_GRID, "%s: method=%d (MVD_NN_AUTO, _BRUTE or _GRID)", fn, method);
-  MVD_CHECK_ARG(grid >= 0 && grid <= 256, "%s: grid=%d outside [0, 256]", fn, grid);
-  MVD_CHECK_ARG(nscene >= 1 && nscene <= 65535, "%s: nscene=%d outside [1, 65535]", fn, nscene);
-  MVD_CHECK_ARG(iters >= 0 && iters <= MVD_ALIGN_MAX_ITERS, "%s: iters=%d outside [0, %d]", fn, iters, MVD_ALIGN_MAX_ITERS);
-  MVD_CHECK_ARG(nq <= 0x7fffffffull && nv <= 0x7fffffffull && nf <= 0x7fffffffull, "%s: nq=%zu, nv=%zu, nf=%zu beyond 2^31 - 1", fn, nq, nv, nf);
-  MVD_CHECK_ARG(max_dist2 >= 0.f, "%s: max_dist2=%g (>= 0, +inf for no gate)", fn, (double)max_dist2);
-  MVD_CHECK_ARG(source_start && face_start, "%s: null source_start or face_start", fn);
-  MVD_CHECK_ARG(transform && history && al_aligned(transform, 8) && al_aligned(history, 8), "%s: null or misaligned transform or history", fn);
-  MVD_CHECK_ARG((source && moved && face && dist2 && point && normal) || nq == 0, "%s: null source, moved, face, dist2, point or normal with nq=%zu",
-                fn, nq);
-  MVD_CHECK_ARG(faces || nf == 0, "%s: null faces with nf=%zu", fn, nf);
-  MVD_CHECK_ARG(vertices || nv == 0, "%s: null vertices with nv=%zu", fn, nv);
-  AlignPlan p;
-  MVD_CHECK_ARG(al_plan(nq, nf, nscene, method, grid, p, kPlSums, true),
-                "%s: nscene * grid^3 cells or nf * %d references beyond 2^31 - 1 (nscene=%d, grid=%d, nf=%zu)", fn,
-                MVD_MESH_SPAN * MVD_MESH_SPAN * MVD_MESH_SPAN, nscene, grid, nf);
-  MVD_CHECK_ARG(scratch && scratch_bytes >= p.bytes && al_aligned(scratch, 16), "%s: scratch of %zu bytes (needs %zu, 16-byte aligned)", fn,
-                scratch_bytes, p.bytes);
-  const hipStream_t st = (hipStream_t)stream;
-  void* nn = p.nn_bytes ? (void*)((char*)scratch + p.off_nn) : nullptr;
+  const MeshSearch search{moved, source_start, vertices, faces, face_start, nq, nv, nf, nscene, method, grid, face, dist2, point, normal, stream};
+  if (search.check(fn, source) != 0) return -1;
   // the pairs of the plane fit: row i of moved with row i of point and normal
-  const FitArgs a = al_args(p, scratch, moved, source_start, point, nullptr, dist2, nq, nq, nscene, max_dist2, normal);
-  // (the search checks its own arguments before it enqueues anything, so a refusal here has written nothing either)
-  int rc = mvd_nearest_on_mesh_stages(moved, source_start, vertices, faces, face_start, nq, nv, nf, nscene, method, grid, face, dist2, point,
-                                      nullptr, nullptr, normal, nn, p.nn_bytes, MVD_NN_BUILD, stream);
-  if (rc == 0) al_launch_map(a, st);
-  const size_t row = (size_t)nscene * MVD_PLANE_HISTORY;
-  for (int k = 0; k <= iters && rc == 0; ++k) {      // row k: the pairs under the transform before step k; the last row has no step
-    al_launch_apply(source, source_start, nq, nscene, transform, moved, st);
-    rc = mvd_nearest_on_mesh_stages(moved, source_start, vertices, faces, face_start, nq, nv, nf, nscene, method, grid, face, dist2, point,
-                                    nullptr, nullptr, normal, nn, p.nn_bytes, MVD_NN_QUERY, stream);
-    if (rc != 0) break;
-    al_launch_fit<PlaneFit>(a, k < iters ? 0 : MVD_PLANE_NO_STEP, transform, history + (size_t)k * row, nullptr, st);
-  }
-  if (rc != 0) {
-    char why[400];
-    snprintf(why, sizeof(why), "%s", mvd_last_error());
-    mvd_set_error("%s: %s", fn, why);
-    return rc;
-  }
-  MVD_CHECK_LAUNCH(fn);
-  return 0;
+  return al_icp<PlaneFit>(fn, search, source, iters, 0, max_dist2, transform, history, scratch, scratch_bytes, point, nullptr, nq, normal);
 }

@@ -76,6 +76,15 @@ def _ndc_lin(P, device):
     return torch.linspace(1.0 - 1.0 / P, -1.0 + 1.0 / P, P, dtype=torch.float32).to(device)
 
 
+def _scratch(nbytes, dev):
+    return torch.empty((int(nbytes) + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def _p(t):
+    """The pointer the library takes for ``t``: NULL for None and for an empty tensor."""
+    return hip.ptr(t) if t is not None and t.numel() else None
+
+
 def _run(lat, rgb, cams, N, V, S, up, depth_scale, depth_shift, lo, hi, tau, min_support, max_conflicts):
     """The two launches.  lat (N*V, 5, S, S), rgb (N*V, 3, P, P) or None, cams (N*V, CAM_RECORD), all fp32 on one GPU.  Returns
     (xyz, rgb or None, support, index) cut to the kept points -- one host read, of the count."""
@@ -422,9 +431,8 @@ def _march(tsdf, weight, color, cweight, N, G, center, half_extent, fill):
     vertices = torch.empty(nvert, 3, dtype=torch.float32, device=dev)
     faces = torch.empty(nface, 3, dtype=torch.int32, device=dev)
     colors = torch.empty(nvert, 3, dtype=torch.float32, device=dev) if color is not None else None
-    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
     hip.check(L.mvd_mesh_emit(hip.ptr(tsdf), hip.ptr(weight), hip.ptr(color), hip.ptr(cweight), N, G, *center, half_extent,
-                              (ctypes.c_float * 3)(*fill), p(vertices), p(colors), p(faces), nvert, nface, hip.ptr(scratch), nbytes,
+                              (ctypes.c_float * 3)(*fill), _p(vertices), _p(colors), _p(faces), nvert, nface, hip.ptr(scratch), nbytes,
                               hip.stream()))
     return vertices, colors, faces, starts[0].clone(), starts[1].clone()
 
@@ -512,8 +520,7 @@ def _raster(vertices, colors, faces, vertex_start, face_start, cams, N, M, P, cu
     bg = (ctypes.c_float * 3)(*background)
     if colors is not None and nvert == 0:
         colors = f32(1, 3)                   # (an empty mesh with colour: the library pairs a non-NULL colors with rgb; nothing reads it)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_render_mesh(p(vertices), hip.ptr(colors), p(faces), hip.ptr(vertex_start), hip.ptr(face_start),
+    hip.check(L.mvd_render_mesh(_p(vertices), hip.ptr(colors), _p(faces), hip.ptr(vertex_start), hip.ptr(face_start),
                                 hip.ptr(cams), nvert, nface, N, M, P, int(cull), float(znear), float(empty_depth), bg, hip.ptr(face),
                                 hip.ptr(depth), hip.ptr(bary), hip.ptr(normal), hip.ptr(rgb), hip.ptr(scratch), nbytes, hip.stream()))
     return rgb, depth, face, bary, normal
@@ -681,10 +688,9 @@ def _nearest(query, query_start, target, target_start, N, method, grid):
     index = torch.empty(nq, dtype=torch.int32, device=dev)
     dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
     nbytes = int(L.mvd_nearest_points_scratch(nt, N, method, grid))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_nearest_points(p(query), hip.ptr(query_start), p(target), hip.ptr(target_start), nq, nt, N, method, grid, p(index),
-                                   p(dist2), p(scratch), nbytes, hip.stream()))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_nearest_points(_p(query), hip.ptr(query_start), _p(target), hip.ptr(target_start), nq, nt, N, method, grid, _p(index),
+                                   _p(dist2), _p(scratch), nbytes, hip.stream()))
     return index, dist2
 
 
@@ -806,11 +812,10 @@ def _nearest_on_mesh(query, query_start, vertices, faces, face_start, N, method,
     f32 = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
     out = NearestOnMesh(face=i32(nq), dist2=f32(nq), point=f32(nq, 3), bary=f32(nq, 3), region=i32(nq), normal=f32(nq, 3))
     nbytes = int(L.mvd_nearest_on_mesh_scratch(nf, N, method, grid))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_nearest_on_mesh(p(query), hip.ptr(query_start), p(vertices), p(faces), hip.ptr(face_start), nq, nv, nf, N, method, grid,
-                                    p(out.face), p(out.dist2), p(out.point), p(out.bary), p(out.region), p(out.normal), p(scratch), nbytes,
-                                    hip.stream()))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_nearest_on_mesh(_p(query), hip.ptr(query_start), _p(vertices), _p(faces), hip.ptr(face_start), nq, nv, nf, N, method, grid,
+                                    _p(out.face), _p(out.dist2), _p(out.point), _p(out.bary), _p(out.region), _p(out.normal), _p(scratch),
+                                    nbytes, hip.stream()))
     return out
 
 
@@ -861,10 +866,9 @@ def _knn(query, query_start, target, target_start, N, k, method, grid):
     index = torch.empty(nq, k, dtype=torch.int32, device=dev)
     dist2 = torch.empty(nq, k, dtype=torch.float32, device=dev)
     nbytes = int(L.mvd_nearest_points_scratch(nt, N, method, grid))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_knn_points(p(query), hip.ptr(query_start), p(target), hip.ptr(target_start), nq, nt, N, k, method, grid, p(index),
-                               p(dist2), p(scratch), nbytes, hip.stream()))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_knn_points(_p(query), hip.ptr(query_start), _p(target), hip.ptr(target_start), nq, nt, N, k, method, grid, _p(index),
+                               _p(dist2), _p(scratch), nbytes, hip.stream()))
     return index, dist2
 
 
@@ -917,9 +921,8 @@ def _normals(target, index, points, toward):
         hip._req(points), hip._req(toward)
     normal = torch.empty(n, 3, dtype=torch.float32, device=target.device)
     variation = torch.empty(n, dtype=torch.float32, device=target.device)
-    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
-    hip.check(L.mvd_point_normals(p(target), int(target.shape[0]), p(index), n, k, p(points) if toward is not None else None, p(toward), p(normal),
-                                  p(variation), hip.stream()))
+    hip.check(L.mvd_point_normals(_p(target), int(target.shape[0]), _p(index), n, k, _p(points) if toward is not None else None, _p(toward),
+                                  _p(normal), _p(variation), hip.stream()))
     return normal, variation
 
 
@@ -1076,44 +1079,81 @@ def _align_apply(xyz, start, N, transform):
     n = int(xyz.shape[0])
     hip._req(xyz), hip._req(start, torch.int32), hip._req(transform, torch.float64)
     out = torch.empty_like(xyz)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_align_apply(p(xyz), hip.ptr(start), n, N, hip.ptr(transform), p(out), hip.stream()))
+    hip.check(L.mvd_align_apply(_p(xyz), hip.ptr(start), n, N, hip.ptr(transform), _p(out), hip.stream()))
     return out
 
 
-def _align_fit(moved, start, target, index, N, flags, max_d2, transform):
-    """The enqueues of mvd_align_fit on the given pairing (index (n,) int32 or None: row i with row i; d2 formed by the kernel).
-    transform (N, 12) float64 is composed in place unless flags has hip.ALIGN_NO_STEP.  Returns the history row (N, 3) float64."""
+def _ptrs(arrays):
+    """``_p`` of each of the fp32 / int32 tensors an entry takes side by side, checked as ``hip._req`` checks one."""
+    for t in arrays:
+        hip._req(t, torch.float32 if t.is_floating_point() else torch.int32)
+    return [_p(t) for t in arrays]
+
+
+def _fit(entry, scratch_entry, history_width, moved, start, target_args, index, N, flags, max_d2, transform):
+    """The enqueues of one fit entry of the library (mvd_align_fit, mvd_plane_fit) on the given pairing: index (n,) int32, or None for
+    row i with row i; d2 is formed by the kernel.  target_args: the target-side tensors in the entry's order -- (target,) or (target,
+    normals), (nt, 3) fp32.  transform (N, 12) float64 is composed in place unless flags has the entry's NO_STEP.  Returns the history
+    row (N, history_width) float64."""
     L = hip.lib()
-    dev, n, nt = moved.device, int(moved.shape[0]), int(target.shape[0])
-    hip._req(moved), hip._req(target), hip._req(start, torch.int32), hip._req(transform, torch.float64)
+    dev, n, nt = moved.device, int(moved.shape[0]), int(target_args[0].shape[0])
+    hip._req(moved), hip._req(start, torch.int32), hip._req(transform, torch.float64)
     if index is not None:
         hip._req(index, torch.int32)
-    row = torch.empty(N, hip.ALIGN_HISTORY, dtype=torch.float64, device=dev)
-    nbytes = int(L.mvd_align_scratch(n, 0, N, hip.NN_BRUTE, 0))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
-    hip.check(L.mvd_align_fit(p(moved), hip.ptr(start), p(target), p(index), None, n, nt, N, flags, max_d2, hip.ptr(transform), hip.ptr(row),
-                              hip.ptr(scratch), nbytes, hip.stream()))
+    row = torch.empty(N, history_width, dtype=torch.float64, device=dev)
+    nbytes = int(getattr(L, scratch_entry)(n, 0, N, hip.NN_BRUTE, 0))
+    scratch = _scratch(nbytes, dev)
+    hip.check(getattr(L, entry)(_p(moved), hip.ptr(start), *_ptrs(target_args), _p(index), None, n, nt, N, flags, max_d2, hip.ptr(transform),
+                                hip.ptr(row), hip.ptr(scratch), nbytes, hip.stream()))
     return row
 
 
-def _align_icp(source, source_start, target, target_start, N, method, grid, iters, flags, max_d2, transform):
-    """The enqueues of mvd_align_icp.  transform (N, 12) float64 holds the start and is overwritten with the result.  Returns
-    (history (iters + 1, N, 3) float64, moved (n, 3) fp32, index (n,) int32, dist2 (n,) fp32).  No host synchronisation."""
+def _icp(entry, scratch_entry, history_width, source, source_start, target_args, target_sizes, N, method, grid, iters, flags, max_d2, transform,
+         extra_outputs=()):
+    """The enqueues of one ICP entry of the library (mvd_align_icp, mvd_plane_icp, mvd_mesh_icp).  target_args: the target-side tensors
+    in the entry's order; target_sizes: their row counts as the entry takes them, the last being the one its scratch entry counts;
+    flags: None for an entry without them; extra_outputs: (n, 3) fp32 outputs behind dist2.  transform (N, 12) float64 holds the start
+    and is overwritten with the result.  Returns (history (iters + 1, N, history_width) float64, moved (n, 3) fp32, index (n,) int32,
+    dist2 (n,) fp32).  No host synchronisation."""
     L = hip.lib()
-    dev, nq, nt = source.device, int(source.shape[0]), int(target.shape[0])
-    hip._req(source), hip._req(target), hip._req(source_start, torch.int32), hip._req(target_start, torch.int32), hip._req(transform, torch.float64)
-    history = torch.empty(iters + 1, N, hip.ALIGN_HISTORY, dtype=torch.float64, device=dev)
+    dev, nq = source.device, int(source.shape[0])
+    hip._req(source), hip._req(source_start, torch.int32), hip._req(transform, torch.float64)
+    history = torch.empty(iters + 1, N, history_width, dtype=torch.float64, device=dev)
     moved = torch.empty_like(source)
     index = torch.empty(nq, dtype=torch.int32, device=dev)
     dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
-    nbytes = int(L.mvd_align_scratch(nq, nt, N, method, grid))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_align_icp(p(source), hip.ptr(source_start), p(target), hip.ptr(target_start), nq, nt, N, method, grid, iters, flags, max_d2,
-                              hip.ptr(transform), hip.ptr(history), p(moved), p(index), p(dist2), hip.ptr(scratch), nbytes, hip.stream()))
+    nbytes = int(getattr(L, scratch_entry)(nq, target_sizes[-1], N, method, grid))
+    scratch = _scratch(nbytes, dev)
+    hip.check(getattr(L, entry)(_p(source), hip.ptr(source_start), *_ptrs(target_args), nq, *target_sizes, N, method, grid, iters,
+                                *(() if flags is None else (flags,)), max_d2, hip.ptr(transform), hip.ptr(history), _p(moved), _p(index),
+                                _p(dist2), *_ptrs(extra_outputs), hip.ptr(scratch), nbytes, hip.stream()))
     return history, moved, index, dist2
+
+
+# The entries by name: what the aligners call (and what a test or a benchmark replaces or times on its own).
+def _align_fit(moved, start, target, index, N, flags, max_d2, transform):
+    return _fit("mvd_align_fit", "mvd_align_scratch", hip.ALIGN_HISTORY, moved, start, (target,), index, N, flags, max_d2, transform)
+
+
+def _plane_fit(moved, start, target, normals, index, N, flags, max_d2, transform):
+    return _fit("mvd_plane_fit", "mvd_plane_scratch", hip.PLANE_HISTORY, moved, start, (target, normals), index, N, flags, max_d2, transform)
+
+
+def _align_icp(source, source_start, target, target_start, N, method, grid, iters, flags, max_d2, transform):
+    return _icp("mvd_align_icp", "mvd_align_scratch", hip.ALIGN_HISTORY, source, source_start, (target, target_start), (int(target.shape[0]),), N,
+                method, grid, iters, flags, max_d2, transform)
+
+
+def _plane_icp(source, source_start, target, target_start, normals, N, method, grid, iters, max_d2, transform):
+    return _icp("mvd_plane_icp", "mvd_plane_scratch", hip.PLANE_HISTORY, source, source_start, (target, target_start, normals),
+                (int(target.shape[0]),), N, method, grid, iters, None, max_d2, transform)
+
+
+def _mesh_icp(source, source_start, vertices, faces, face_start, N, method, grid, iters, max_d2, transform):
+    """(history, moved, face, dist2): the loop's point and normal outputs are scratch to the caller."""
+    return _icp("mvd_mesh_icp", "mvd_mesh_icp_scratch", hip.PLANE_HISTORY, source, source_start, (vertices, faces, face_start),
+                (int(vertices.shape[0]), int(faces.shape[0])), N, method, grid, iters, None, max_d2, transform,
+                extra_outputs=(torch.empty_like(source), torch.empty_like(source)))
 
 
 @dataclass
@@ -1180,6 +1220,40 @@ def _fl32_square(v):
         return float("inf")
 
 
+def _check_icp(iters, max_distance, scale=False):
+    """(iters as an int, max_d2) of the arguments the ICP functions share, checked in the order iters, scale, max_distance."""
+    iters = _check_count(iters, "iters", 0, hip.ALIGN_MAX_ITERS)
+    if not isinstance(scale, bool):
+        raise ValueError(f"scale = {scale!r}: True or False")
+    return iters, _max_d2(max_distance)
+
+
+def _max_d2(max_distance):
+    """The gate as the kernel compares it: fl32(max_distance)^2, +inf for None."""
+    if max_distance is not None and not float(max_distance) >= 0:
+        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    return float("inf") if max_distance is None else _fl32_square(float(max_distance))
+
+
+def _check_pairs(pairs, n, nt):
+    if pairs is None:
+        if n != nt:
+            raise ValueError(f"target: {nt} points for {n} of source -- row i goes with row i; give pairs otherwise")
+    elif not torch.is_tensor(pairs) or tuple(pairs.shape) != (n,) or pairs.dtype != torch.int32:
+        raise ValueError(f"pairs: an ({n},) int32 tensor, one target row (or -1) per source row")
+
+
+def _given_pairs(moved, start, target, index, nt, N):
+    """(index, dist2) of a GIVEN pairing as a search would report it: -1 / +inf for a skipped row."""
+    rows = torch.arange(int(moved.shape[0]), dtype=torch.int32, device=moved.device)
+    j = rows if index is None else index
+    has = (j >= 0) & (j < nt) & (rows >= start[0]) & (rows < start[N])
+    d = moved - target[j.long().clamp(0, max(nt - 1, 0))] if nt else torch.full_like(moved, float("nan"))
+    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]          # (the search's order: every torch op rounds once)
+    has = has & (d2 < float("inf"))
+    return torch.where(has, j, torch.full_like(j, -1)), torch.where(has, d2, torch.full_like(d2, float("inf")))
+
+
 def fit_similarity(source, target, scenes=1, scale=True, pairs=None):
     """The similarity (rigid with ``scale=False``) that best takes ``source`` onto ``target`` in the least-squares sense, for KNOWN
     correspondences, in closed form (Horn's quaternion solve; include/mvd_hip.h: mvd_align_fit has the rule) -> Alignment.
@@ -1198,11 +1272,7 @@ def fit_similarity(source, target, scenes=1, scale=True, pairs=None):
     s, s_scene = _points_of(source, "source", N)
     t, t_scene = _points_of(target, "target", N)
     dev, n, nt = s.device, int(s.shape[0]), int(t.shape[0])
-    if pairs is None:
-        if n != nt:
-            raise ValueError(f"target: {nt} points for {n} of source -- row i goes with row i; give pairs otherwise")
-    elif not torch.is_tensor(pairs) or tuple(pairs.shape) != (n,) or pairs.dtype != torch.int32:
-        raise ValueError(f"pairs: an ({n},) int32 tensor, one target row (or -1) per source row")
+    _check_pairs(pairs, n, nt)
     s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
     start = _scene_start(s_scene, n, N, dev)
     index = None if pairs is None else pairs.to(dev).contiguous()
@@ -1211,14 +1281,7 @@ def fit_similarity(source, target, scenes=1, scale=True, pairs=None):
     first = _align_fit(s, start, t, index, N, flags, float("inf"), transform)
     moved = _align_apply(s, start, N, transform)
     last = _align_fit(moved, start, t, index, N, flags | hip.ALIGN_NO_STEP, float("inf"), transform)
-    rows = torch.arange(n, dtype=torch.int32, device=dev)
-    j = rows if index is None else index
-    has = (j >= 0) & (j < nt) & (rows >= start[0]) & (rows < start[N])
-    d = moved - t[j.long().clamp(0, max(nt - 1, 0))] if nt else torch.full_like(moved, float("nan"))
-    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]          # (the search's order: every torch op rounds once)
-    has = has & (d2 < float("inf"))
-    return _alignment(transform, first[:, 2].clone(), last[None], moved, torch.where(has, j, torch.full_like(j, -1)),
-                      torch.where(has, d2, torch.full_like(d2, float("inf"))))
+    return _alignment(transform, first[:, 2].clone(), last[None], moved, *_given_pairs(moved, start, t, index, nt, N))
 
 
 def _centroid_init(s, s_start, t, t_start, N, scale):
@@ -1266,6 +1329,21 @@ def _check_init(init, N, dev):
     return m[:, :3, :].reshape(N, 12).contiguous(), torch.linalg.det(m[:, :3, :3]).abs().pow(1.0 / 3.0)
 
 
+def _start_transform(init, N, dev, centroid):
+    """(transform (N, 12) float64 on dev, scale (N,) float64) of the ``init`` argument of the ICP functions.  centroid: a callable that
+    gives ``_centroid_init``'s pair; it is called for "centroid" only, the one form that may read the host.  The loop writes its result
+    into ``transform``, so it is ALWAYS a fresh tensor: ``_check_init``'s can be a view of the caller's matrix (one scene: the first three
+    rows of a (4, 4) float64 matrix are contiguous as they lie)."""
+    if init is None:
+        return _identity_transform(N, dev), torch.ones(N, dtype=torch.float64, device=dev)
+    if isinstance(init, str):
+        if init != "centroid":
+            raise ValueError(f"init = {init!r}: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
+        return centroid()
+    transform, scale0 = _check_init(init, N, dev)
+    return transform.clone(), scale0
+
+
 def align_geometry(source, target, scenes=1, iters=ALIGN_ITERS, scale=False, max_distance=None, init=None, method="auto", grid=None):
     """Point-to-point ICP: ``iters`` times, every source point under the current transform is matched with its exact nearest target
     point (``nearest_points``' bits) and the transform is re-fitted to the accepted pairs in closed form (include/mvd_hip.h:
@@ -1285,69 +1363,21 @@ def align_geometry(source, target, scenes=1, iters=ALIGN_ITERS, scale=False, max
               "centroid" -- the source's per-scene centroid mapped onto the target's and, with ``scale``, the RMS radii matched
               (float64 torch ops per scene slice; reads the scene offsets once).  ICP converges to the nearest local optimum: it needs
               a start in its basin -- ``register_geometry`` finds one from an arbitrary pose, and its result is a valid ``init``.
+              ``init`` is copied, never written into, here and in ``align_to_surface`` and ``align_to_mesh``.
     method, grid : those of ``nearest_points``.
     ``iters`` and ``max_distance`` are INTERFACE defaults: no trained checkpoint or scan was available when this was written, so
     nobody has tuned them on real data -- expect to.  A scene with fewer than 3 accepted pairs keeps its transform.  Apart from
     ``init="centroid"`` nothing synchronises with the host."""
     N, method, grid = _check_nn(scenes, method, grid)
-    if isinstance(iters, bool) or not isinstance(iters, (int, float)) or int(iters) != iters or not 0 <= iters <= hip.ALIGN_MAX_ITERS:
-        raise ValueError(f"iters = {iters}: an integer in [0, {hip.ALIGN_MAX_ITERS}]")
-    if not isinstance(scale, bool):
-        raise ValueError(f"scale = {scale!r}: True or False")
-    if max_distance is not None and not float(max_distance) >= 0:
-        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    iters, max_d2 = _check_icp(iters, max_distance, scale)
     s, s_scene = _points_of(source, "source", N)
     t, t_scene = _points_of(target, "target", N)
     dev = s.device
     s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
     s_start, t_start = _scene_start(s_scene, int(s.shape[0]), N, dev), _scene_start(t_scene, int(t.shape[0]), N, dev)
-    if init is None:
-        transform, scale0 = _identity_transform(N, dev), torch.ones(N, dtype=torch.float64, device=dev)
-    elif isinstance(init, str):
-        if init != "centroid":
-            raise ValueError(f"init = {init!r}: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
-        transform, scale0 = _centroid_init(s, s_start, t, t_start, N, scale)
-    else:
-        transform, scale0 = _check_init(init, N, dev)
-    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
-    history, moved, index, dist2 = _align_icp(s, s_start, t, t_start, N, method, grid, int(iters), hip.ALIGN_SCALE if scale else 0, max_d2, transform)
+    transform, scale0 = _start_transform(init, N, dev, lambda: _centroid_init(s, s_start, t, t_start, N, scale))
+    history, moved, index, dist2 = _align_icp(s, s_start, t, t_start, N, method, grid, iters, hip.ALIGN_SCALE if scale else 0, max_d2, transform)
     return _alignment(transform, scale0 * history[-1, :, 2], history, moved, index, dist2)
-
-
-def _plane_fit(moved, start, target, normals, index, N, flags, max_d2, transform):
-    """The enqueues of mvd_plane_fit: ``_align_fit`` with the target's normals (nt, 3) fp32.  transform (N, 12) float64 is composed in
-    place unless flags has hip.PLANE_NO_STEP.  Returns the history row (N, 4) float64."""
-    L = hip.lib()
-    dev, n, nt = moved.device, int(moved.shape[0]), int(target.shape[0])
-    hip._req(moved), hip._req(target), hip._req(normals), hip._req(start, torch.int32), hip._req(transform, torch.float64)
-    if index is not None:
-        hip._req(index, torch.int32)
-    row = torch.empty(N, hip.PLANE_HISTORY, dtype=torch.float64, device=dev)
-    nbytes = int(L.mvd_plane_scratch(n, 0, N, hip.NN_BRUTE, 0))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t is not None and t.numel() else None
-    hip.check(L.mvd_plane_fit(p(moved), hip.ptr(start), p(target), p(normals), p(index), None, n, nt, N, flags, max_d2, hip.ptr(transform),
-                              hip.ptr(row), hip.ptr(scratch), nbytes, hip.stream()))
-    return row
-
-
-def _plane_icp(source, source_start, target, target_start, normals, N, method, grid, iters, max_d2, transform):
-    """The enqueues of mvd_plane_icp.  transform (N, 12) float64 holds the start and is overwritten with the result.  Returns
-    (history (iters + 1, N, 4) float64, moved (n, 3) fp32, index (n,) int32, dist2 (n,) fp32).  No host synchronisation."""
-    L = hip.lib()
-    dev, nq, nt = source.device, int(source.shape[0]), int(target.shape[0])
-    hip._req(source), hip._req(target), hip._req(normals), hip._req(source_start, torch.int32), hip._req(target_start, torch.int32)
-    hip._req(transform, torch.float64)
-    history = torch.empty(iters + 1, N, hip.PLANE_HISTORY, dtype=torch.float64, device=dev)
-    moved = torch.empty_like(source)
-    index = torch.empty(nq, dtype=torch.int32, device=dev)
-    dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
-    nbytes = int(L.mvd_plane_scratch(nq, nt, N, method, grid))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_plane_icp(p(source), hip.ptr(source_start), p(target), hip.ptr(target_start), p(normals), nq, nt, N, method, grid, iters,
-                              max_d2, hip.ptr(transform), hip.ptr(history), p(moved), p(index), p(dist2), hip.ptr(scratch), nbytes, hip.stream()))
-    return history, moved, index, dist2
 
 
 @dataclass
@@ -1396,11 +1426,7 @@ def fit_plane_step(source, target, normals, scenes=1, pairs=None):
     dev, n, nt = s.device, int(s.shape[0]), int(t.shape[0])
     if normals is None:
         raise ValueError("normals: a PointNormals or an (nt, 3) tensor (estimate_normals(target) makes them)")
-    if pairs is None:
-        if n != nt:
-            raise ValueError(f"target: {nt} points for {n} of source -- row i goes with row i; give pairs otherwise")
-    elif not torch.is_tensor(pairs) or tuple(pairs.shape) != (n,) or pairs.dtype != torch.int32:
-        raise ValueError(f"pairs: an ({n},) int32 tensor, one target row (or -1) per source row")
+    _check_pairs(pairs, n, nt)
     s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
     nrm = _target_normals(normals, t, t_scene, N, NORMALS_K, hip.NN_AUTO, 0, nt)
     start = _scene_start(s_scene, n, N, dev)
@@ -1409,14 +1435,8 @@ def fit_plane_step(source, target, normals, scenes=1, pairs=None):
     _plane_fit(s, start, t, nrm, index, N, 0, float("inf"), transform)
     moved = _align_apply(s, start, N, transform)
     last = _plane_fit(moved, start, t, nrm, index, N, hip.PLANE_NO_STEP, float("inf"), transform)
-    rows = torch.arange(n, dtype=torch.int32, device=dev)
-    j = rows if index is None else index
-    has = (j >= 0) & (j < nt) & (rows >= start[0]) & (rows < start[N])
-    d = moved - t[j.long().clamp(0, max(nt - 1, 0))] if nt else torch.full_like(moved, float("nan"))
-    d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]          # (the search's order: every torch op rounds once)
-    has = has & (d2 < float("inf"))
     return _plane_alignment(transform, torch.ones(N, dtype=torch.float64, device=dev), last[None], moved,
-                            torch.where(has, j, torch.full_like(j, -1)), torch.where(has, d2, torch.full_like(d2, float("inf"))))
+                            *_given_pairs(moved, start, t, index, nt, N))
 
 
 def align_to_surface(source, target, normals=None, k=NORMALS_K, scenes=1, iters=ALIGN_ITERS, max_distance=None, init=None, method="auto",
@@ -1443,10 +1463,7 @@ def align_to_surface(source, target, normals=None, k=NORMALS_K, scenes=1, iters=
     the six that each row's pairs constrain; rows as in ``Alignment``.  Apart from ``init="centroid"`` nothing synchronises with the
     host."""
     N, method, grid = _check_nn(scenes, method, grid)
-    if isinstance(iters, bool) or not isinstance(iters, (int, float)) or int(iters) != iters or not 0 <= iters <= hip.ALIGN_MAX_ITERS:
-        raise ValueError(f"iters = {iters}: an integer in [0, {hip.ALIGN_MAX_ITERS}]")
-    if max_distance is not None and not float(max_distance) >= 0:
-        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    iters, max_d2 = _check_icp(iters, max_distance)
     if normals is None:
         k = _check_k(k, hip.KNN_MAX_K, "hip.KNN_MAX_K")
         if k < 3:
@@ -1455,40 +1472,11 @@ def align_to_surface(source, target, normals=None, k=NORMALS_K, scenes=1, iters=
     t, t_scene = _points_of(target, "target", N)
     dev = s.device
     s, t = s.float().contiguous(), t.to(dev, torch.float32).contiguous()
-    if isinstance(init, str) and init != "centroid":
-        raise ValueError(f"init = {init!r}: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
     s_start, t_start = _scene_start(s_scene, int(s.shape[0]), N, dev), _scene_start(t_scene, int(t.shape[0]), N, dev)
-    if init is None:
-        transform, scale0 = _identity_transform(N, dev), torch.ones(N, dtype=torch.float64, device=dev)
-    elif isinstance(init, str):
-        transform, scale0 = _centroid_init(s, s_start, t, t_start, N, False)
-    else:
-        transform, scale0 = _check_init(init, N, dev)
-        transform = transform.clone()          # (the loop writes its result there: never into the caller's init, which a view can alias)
+    transform, scale0 = _start_transform(init, N, dev, lambda: _centroid_init(s, s_start, t, t_start, N, False))
     nrm = _target_normals(normals, t, t_scene, N, k, method, grid, int(t.shape[0]))
-    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
-    history, moved, index, dist2 = _plane_icp(s, s_start, t, t_start, nrm, N, method, grid, int(iters), max_d2, transform)
+    history, moved, index, dist2 = _plane_icp(s, s_start, t, t_start, nrm, N, method, grid, iters, max_d2, transform)
     return _plane_alignment(transform, scale0, history, moved, index, dist2)
-
-
-def _mesh_icp(source, source_start, vertices, faces, face_start, N, method, grid, iters, max_d2, transform):
-    """The enqueues of mvd_mesh_icp.  transform (N, 12) float64 holds the start and is overwritten with the result.  Returns
-    (history (iters + 1, N, 4) float64, moved (n, 3) fp32, face (n,) int32, dist2 (n,) fp32).  No host synchronisation."""
-    L = hip.lib()
-    dev, nq, nv, nf = source.device, int(source.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
-    hip._req(source), hip._req(vertices), hip._req(faces, torch.int32), hip._req(source_start, torch.int32), hip._req(face_start, torch.int32)
-    hip._req(transform, torch.float64)
-    history = torch.empty(iters + 1, N, hip.PLANE_HISTORY, dtype=torch.float64, device=dev)
-    moved, point, normal = torch.empty_like(source), torch.empty_like(source), torch.empty_like(source)
-    face = torch.empty(nq, dtype=torch.int32, device=dev)
-    dist2 = torch.empty(nq, dtype=torch.float32, device=dev)
-    nbytes = int(L.mvd_mesh_icp_scratch(nq, nf, N, method, grid))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_mesh_icp(p(source), hip.ptr(source_start), p(vertices), p(faces), hip.ptr(face_start), nq, nv, nf, N, method, grid, iters,
-                             max_d2, hip.ptr(transform), hip.ptr(history), p(moved), p(face), p(dist2), p(point), p(normal), hip.ptr(scratch),
-                             nbytes, hip.stream()))
-    return history, moved, face, dist2
 
 
 def align_to_mesh(source, mesh, scenes=1, iters=ALIGN_ITERS, max_distance=None, init=None, method="auto", grid=None):
@@ -1497,36 +1485,26 @@ def align_to_mesh(source, mesh, scenes=1, iters=ALIGN_ITERS, max_distance=None, 
     residual falls with the sampling density; here the pair is the exact closest point of the triangles with that face's normal, so
     nothing depends on a sampling of the target.  The loop, the fit, the gate and the rank rule are ``align_to_surface``'s.
 
-    source, scenes, iters, max_distance, init, method, grid : as for ``align_to_surface`` (``init`` is copied, never written into; the
-              fit is rigid and carries a scale in ``init`` through untouched); ``iters`` and ``max_distance`` are the same untuned
-              interface defaults.
+    source, scenes, iters, max_distance, init, method, grid : as for ``align_to_surface`` (the fit is rigid and carries a scale in
+              ``init`` through untouched); ``iters`` and ``max_distance`` are the same untuned interface defaults.
     mesh    : a TriangleMesh of at most ``scenes`` scenes; a degenerate face pairs with nothing (its normal is zero).
     ``nearest`` is the NearestOnMesh of the moved source against the mesh (the final correspondences).  Apart from
     ``init="centroid"`` -- which centres on the mesh's VERTICES -- nothing synchronises with the host."""
     import dataclasses
     N, method, grid = _check_nn(scenes, method, grid)
-    if isinstance(iters, bool) or not isinstance(iters, (int, float)) or int(iters) != iters or not 0 <= iters <= hip.ALIGN_MAX_ITERS:
-        raise ValueError(f"iters = {iters}: an integer in [0, {hip.ALIGN_MAX_ITERS}]")
-    if max_distance is not None and not float(max_distance) >= 0:
-        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    iters, max_d2 = _check_icp(iters, max_distance)
     s, s_scene = _points_of(source, "source", N)
     dev = s.device
     s = s.float().contiguous()
     vertices, faces, face_start = _mesh_arrays(mesh, N, dev)
-    if isinstance(init, str) and init != "centroid":
-        raise ValueError(f"init = {init!r}: None, 'centroid', an Alignment, or a (4, 4) or ({N}, 4, 4) matrix")
     s_start = _scene_start(s_scene, int(s.shape[0]), N, dev)
-    if init is None:
-        transform, scale0 = _identity_transform(N, dev), torch.ones(N, dtype=torch.float64, device=dev)
-    elif isinstance(init, str):
+
+    def centroid():
         v_start = [int(v) for v in mesh.vertex_start.tolist()]
         v_start = torch.tensor(v_start + [v_start[-1]] * (N + 1 - len(v_start)), dtype=torch.int32).to(dev)
-        transform, scale0 = _centroid_init(s, s_start, vertices, v_start, N, False)
-    else:
-        transform, scale0 = _check_init(init, N, dev)
-        transform = transform.clone()          # (the loop writes its result there: never into the caller's init, which a view can alias)
-    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
-    history, moved, face, dist2 = _mesh_icp(s, s_start, vertices, faces, face_start, N, method, grid, int(iters), max_d2, transform)
+        return _centroid_init(s, s_start, vertices, v_start, N, False)
+    transform, scale0 = _start_transform(init, N, dev, centroid)
+    history, moved, face, dist2 = _mesh_icp(s, s_start, vertices, faces, face_start, N, method, grid, iters, max_d2, transform)
     out = _plane_alignment(transform, scale0, history, moved, face, dist2)
     # every field of the final correspondences (the loop keeps face, dist2, point and normal only): the same search once more
     return dataclasses.replace(out, nearest=_nearest_on_mesh(moved, s_start, vertices, faces, face_start, N, method, grid))
@@ -1605,9 +1583,8 @@ def _register_build(target, target_start, N, method, grid, scratch, nbytes):
     """MVD_NN_BUILD of mvd_nearest_points_stages into the head of ``scratch``: the grid every following score walks."""
     L = hip.lib()
     nt = int(target.shape[0])
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_nearest_points_stages(None, hip.ptr(target_start), p(target), hip.ptr(target_start), 0, nt, N, method, grid, None, None,
-                                          p(scratch), nbytes, hip.NN_BUILD, hip.stream()))
+    hip.check(L.mvd_nearest_points_stages(None, hip.ptr(target_start), _p(target), hip.ptr(target_start), 0, nt, N, method, grid, None, None,
+                                          _p(scratch), nbytes, hip.NN_BUILD, hip.stream()))
 
 
 def _register_score(points, start, target, target_start, N, hyp, trunc2, method, grid, scratch, nbytes):
@@ -1618,8 +1595,7 @@ def _register_score(points, start, target, target_start, N, hyp, trunc2, method,
     hip._req(points), hip._req(target), hip._req(start, torch.int32), hip._req(target_start, torch.int32), hip._req(hyp, torch.float64)
     score = torch.empty(N, H, dtype=torch.float64, device=dev)
     inliers = torch.empty(N, H, dtype=torch.int32, device=dev)
-    p = lambda t: hip.ptr(t) if t.numel() else None
-    hip.check(L.mvd_register_score(p(points), hip.ptr(start), p(target), hip.ptr(target_start), n, nt, N, H, hip.ptr(hyp), trunc2, method, grid,
+    hip.check(L.mvd_register_score(_p(points), hip.ptr(start), _p(target), hip.ptr(target_start), n, nt, N, H, hip.ptr(hyp), trunc2, method, grid,
                                    hip.ptr(score), hip.ptr(inliers), hip.ptr(scratch), nbytes, hip.stream()))
     return score, inliers
 
@@ -1742,8 +1718,7 @@ def register_geometry(source, target, scenes=1, rotations=REGISTER_ROTATIONS, sa
         raise ValueError(f"separation = {separation}: degrees in [0, 180]")
     if trunc is not None and not 0 < float(trunc) < float("inf"):
         raise ValueError(f"trunc = {trunc}: None or a finite distance > 0")
-    if max_distance is not None and not float(max_distance) >= 0:
-        raise ValueError(f"max_distance = {max_distance}: None or a distance >= 0")
+    max_d2 = _max_d2(max_distance)
     if not torch.is_tensor(rotations):
         _check_count(rotations, "rotations", 1, hip.REGISTER_MAX_H)
     s, s_scene = _points_of(source, "source", N)
@@ -1756,13 +1731,12 @@ def register_geometry(source, target, scenes=1, rotations=REGISTER_ROTATIONS, sa
     s_start, t_start = _scene_start(s_scene, n, N, dev), _scene_start(t_scene, nt, N, dev)
     hyp, k_, sample, sample_start, trunc2 = _register_inputs(s, s_start, t, t_start, N, R, scale, samples, trunc)
     nbytes = max(_register_scratch(int(sample.shape[0]), nt, N, H, method, grid), _register_scratch(n, nt, N, K, method, grid))
-    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+    scratch = _scratch(nbytes, dev)
     _register_build(t, t_start, N, method, grid, scratch, nbytes)
     grid_score, _ = _register_score(sample, sample_start, t, t_start, N, hyp, trunc2, method, grid, scratch, nbytes)
     cos_half = math.cos(math.radians(float(separation)) / 2.0) if float(separation) > 0 else 2.0
     top, _ = _register_select(grid_score, quat.to(dev).contiguous(), K, cos_half)
     flags = hip.ALIGN_SCALE if scale else 0
-    max_d2 = float("inf") if max_distance is None else _fl32_square(float(max_distance))
     scene_ids = torch.arange(N, device=dev)
     refined, refined_scale = [], []
     for k in range(K):
@@ -1880,14 +1854,6 @@ def _topo_arrays(mesh):
     to_dev = lambda s: torch.tensor(s, dtype=torch.int32).to(dev)
     return (vertices.to(dev, torch.float32).contiguous(), faces.to(dev, torch.int32).contiguous(),
             None if rgb is None else rgb.to(dev, torch.float32).contiguous(), to_dev(starts[0]), to_dev(starts[1]), len(starts[0]) - 1)
-
-
-def _scratch(nbytes, dev):
-    return torch.empty((int(nbytes) + 7) // 8, dtype=torch.int64, device=dev)
-
-
-def _p(t):
-    return hip.ptr(t) if t is not None and t.numel() else None
 
 
 def _incidence(faces, vertex_start, face_start, nv, N):

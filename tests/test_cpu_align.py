@@ -302,6 +302,56 @@ def test_align_geometry_validates_and_enqueues(stub):
         fusion.align_geometry(a.xyz, b.xyz, init=al)          # three scenes into one
 
 
+def test_the_start_transform_shares_no_storage_with_init():
+    """The loop writes its result into the start transform.  With one scene the first three rows of a float64 (4, 4) matrix are
+    contiguous as they lie, so a reshape of them is a view of the caller's tensor: the start must be a copy, for every form of init."""
+    T = torch.from_numpy(A.similarity(1.25, 30.0, (1, 2, 3), (0.1, 0.2, 0.3)))
+    assert T[None][:, :3, :].reshape(1, 12).contiguous().data_ptr() == T.data_ptr()          # (the view this guards against)
+    m34 = T[:3].reshape(1, 3, 4)
+    by_hand = fusion.Alignment(matrix=T[None].clone(), rotation=m34[:, :, :3] / 1.25, translation=m34[:, :, 3].clone(), scale=torch.tensor([1.25]).double(),
+                               rms=torch.zeros(1, 1).double(), pairs=torch.zeros(1, 1, dtype=torch.int64), xyz=torch.zeros(0, 3), nearest=None)
+    never = lambda: pytest.fail("the centroid start was asked for")
+    for init in (T.clone(), T[None].clone(), by_hand):
+        held = init.matrix if isinstance(init, fusion.Alignment) else init
+        before = held.clone()
+        transform, scale0 = fusion._start_transform(init, 1, "cpu", never)
+        assert transform.shape == (1, 12) and transform.dtype == torch.float64 and torch.equal(transform, T[:3].reshape(1, 12))
+        assert abs(float(scale0[0]) - 1.25) <= 1e-14
+        assert transform.untyped_storage().data_ptr() != held.untyped_storage().data_ptr()
+        transform.fill_(-7.25)
+        scale0.fill_(-7.25)
+        assert torch.equal(held, before) and (not isinstance(init, fusion.Alignment) or float(init.scale[0]) == 1.25)
+    transform, scale0 = fusion._start_transform(None, 3, "cpu", never)
+    assert torch.equal(transform, IDENTITY12.repeat(3, 1)) and torch.equal(scale0, torch.ones(3, dtype=torch.float64))
+    assert transform.untyped_storage().data_ptr() != fusion._start_transform(None, 3, "cpu", never)[0].untyped_storage().data_ptr()
+    given = (torch.full((2, 12), 0.5, dtype=torch.float64), torch.full((2,), 2.0, dtype=torch.float64))
+    got = fusion._start_transform("centroid", 2, "cpu", lambda: given)
+    assert got[0] is given[0] and got[1] is given[1]
+    for init, text in (("pca", r"init = 'pca': None, 'centroid', an Alignment, or a \(4, 4\) or \(1, 4, 4\) matrix"),
+                       (torch.eye(3), r"init: None, 'centroid', an Alignment, or a \(4, 4\) or \(1, 4, 4\) matrix"),
+                       (torch.eye(4).expand(2, 4, 4), r"init: None, 'centroid', an Alignment, or a \(4, 4\) or \(1, 4, 4\) matrix"),
+                       (torch.diag(torch.tensor([-1.0, 1, 1, 1])), r"init: the 3 x 3 block must have a positive determinant \(a similarity, not a reflection\)"),
+                       (torch.zeros(4, 4), r"init: a finite matrix whose last row is \(0, 0, 0, 1\)")):
+        with pytest.raises(ValueError, match=text):
+            fusion._start_transform(init, 1, "cpu", never)
+
+
+def test_the_shared_icp_checks():
+    for iters in (-1, 1025, 1.5, True):
+        with pytest.raises(ValueError, match=r"iters = .*: an integer in \[0, 1024\]"):
+            fusion._check_icp(iters, None)
+    for max_distance in (-1, float("nan")):
+        with pytest.raises(ValueError, match="max_distance = .*: None or a distance >= 0"):
+            fusion._check_icp(3, max_distance)
+    with pytest.raises(ValueError, match="scale = 1: True or False"):
+        fusion._check_icp(3, None, 1)
+    assert fusion._check_icp(0, None) == (0, float("inf")) and fusion._check_icp(1024.0, None, True) == (1024, float("inf"))
+    iters, max_d2 = fusion._check_icp(7, 0.1875)
+    assert type(iters) is int and iters == 7 and max_d2 == 0.1875 ** 2 == float(np.float32(0.1875) * np.float32(0.1875))
+    f32 = np.float32(0.1)
+    assert fusion._check_icp(7, 0.1)[1] == float(np.float32(f32 * f32)) and fusion._check_icp(7, 1e30)[1] == float("inf")
+
+
 def test_the_centroid_start_is_the_float64_map(stub):
     case = A.make_case("pairs_4099")
     for scale in (False, True):

@@ -232,5 +232,6 @@ def test_align_to_mesh_validates_before_it_reaches_the_library(monkeypatch):
         with pytest.raises(ValueError):
             fusion.align_to_mesh(**args)
     assert not reached
-    for text in ("mvd_mesh_icp", "copied", "rigid", "interface defaults"):
+    for text in ("mvd_mesh_icp", "rigid", "interface defaults"):
         assert text in fusion.align_to_mesh.__doc__, text
+    assert "copied, never written into" in fusion.align_geometry.__doc__ and "align_to_mesh" in fusion.align_geometry.__doc__

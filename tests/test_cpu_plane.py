@@ -161,7 +161,8 @@ def test_the_header_and_the_binding_agree():
     src = open(os.path.join(ROOT, "mvdfusion_amd", "csrc", "align.hip")).read()
     # one copy of the reduction: both fits go through the same two kernels and the same chunk map
     assert src.count("void accumulate_kernel(") == 1 and src.count("void solve_kernel(") == 1 and src.count("void chunk_count_kernel(") == 1
-    assert "al_launch_fit<PlaneFit>" in src and "atomicAdd" not in src
+    assert "al_fit<PlaneFit>(" in src and "al_icp<PlaneFit>(" in src and src.count("al_launch_fit<Fit>(") == 2 and "atomicAdd" not in src
+    assert src.count("k <= iters") == 1          # one host loop for the three ICP entries
     L = hip.lib()
     assert int(L.mvd_plane_scratch(5000, 0, 3, hip.NN_BRUTE, 0)) >= (5 + 3) * 30 * 8 + 4 * 4
     assert int(L.mvd_plane_scratch(5000, 5000, 1, hip.NN_GRID, 7)) >= int(L.mvd_plane_scratch(5000, 0, 1, hip.NN_BRUTE, 0)) + \

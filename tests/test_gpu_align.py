@@ -271,6 +271,108 @@ def test_icp_recovers_every_correspondence_and_the_transform(hip, icp_runs, name
     assert bool(al.nearest.hit.all()) and float(al.nearest.dist2.max()) <= (2.0 ** -22) ** 2 * case.n
 
 
+def _by_hand(hip, dev, case, iters, method, grid):
+    """The sequence mvd_align_icp stands for, issued by the caller: mvd_nearest_points_stages(BUILD) once, then per row mvd_align_apply,
+    mvd_nearest_points_stages(QUERY) and mvd_align_fit (with MVD_ALIGN_SCALE) on the pairs and distances the search left."""
+    L, p = hip.lib(), hip.ptr
+    out = _icp_buffers(hip, case, iters, method, grid)
+    transform = _identity(case.nscene)
+    nn_bytes = int(L.mvd_nearest_points_scratch(case.nt, case.nscene, method, grid))
+    nn = _scratch(nn_bytes)
+    search = lambda stages: hip.check(L.mvd_nearest_points_stages(p(out["moved"]), p(dev["start"]), p(dev["target"]), p(dev["tstart"]), case.n, case.nt,
+                                                                  case.nscene, method, grid, p(out["index"]), p(out["dist2"]),
+                                                                  p(nn) if nn_bytes else None, nn_bytes, stages, hip.stream()))
+    search(hip.NN_BUILD)
+    for k in range(iters + 1):
+        hip.check(_apply(hip, dev["source"], dev["start"], case.n, case.nscene, transform, out["moved"]))
+        search(hip.NN_QUERY)
+        hip.check(_fit(hip, out["moved"], dev["start"], dev["target"], out["index"], out["dist2"], case.n, case.nt, case.nscene,
+                       hip.ALIGN_SCALE | (0 if k < iters else hip.ALIGN_NO_STEP), INF, transform, out["history"][k]))
+    torch.cuda.synchronize()
+    return dict(out, transform=transform)
+
+
+def _loop_is_the_sequence(hip, case, iters, method, grid):
+    dev = _device(case)
+    out, transform = _icp_buffers(hip, case, iters, method, grid), _identity(case.nscene)
+    hip.check(_icp(hip, dev, case, out, transform, iters, hip.ALIGN_SCALE, INF, method, grid))
+    torch.cuda.synchronize()
+    hand = _by_hand(hip, dev, case, iters, method, grid)
+    assert not bool((out["history"] == SENTINEL).any())
+    assert _same(hand["transform"], transform)
+    for k in ("moved", "index", "dist2"):
+        assert _same(hand[k], out[k]), k
+    assert _same(hand["history"][:, :, :2], out["history"][:, :, :2])
+    # column 2, the scale so far: a fit called by hand starts every row from 1, the loop carries the row before on -- one IEEE multiply
+    # per row, as al_finish forms it; the last row takes no step
+    r = hand["history"][:, :, 2].cpu().numpy()
+    carried = np.empty_like(r)
+    carried[0] = r[0]
+    for k in range(1, iters):
+        carried[k] = carried[k - 1] * r[k]
+    carried[iters] = carried[iters - 1]
+    assert np.array_equal(carried.view(np.int64), out["history"][:, :, 2].cpu().numpy().view(np.int64))
+    return out, transform
+
+
+@pytest.mark.parametrize("method, grid", [("NN_AUTO", 0), ("NN_BRUTE", 0), ("NN_GRID", 9)])
+def test_the_loop_is_the_sequence_it_stands_for(hip, method, grid):
+    """mvd_align_icp against the caller-issued sequence, bit for bit, on icp_sim5 with a scale fitted: the carried scale is the one thing
+    the point loop has that the plane loops have not."""
+    case = A.make_case("icp_sim5")
+    assert case.n == 1537 and case.scale
+    out, transform = _loop_is_the_sequence(hip, case, 4, getattr(hip, method), grid)
+    assert not torch.equal(transform, _identity(1)) and float(out["history"][-1, 0, 2]) != 1.0          # (a scale was fitted and carried)
+
+
+def test_the_loop_is_the_sequence_with_empty_and_tiny_scenes(hip):
+    """icp_sim5 in one batch with the scenes of 0, 1, 2 and 3 points of small_scenes: an empty scene and scenes with fewer than 3 pairs go
+    through the same loop and keep the identity; three pairs are fitted."""
+    a, b = A.make_case("icp_sim5"), A.make_case("small_scenes")
+    assert b.start[:5] == [0, 0, 1, 3, 6]
+    start = [0] + [a.n + v for v in b.start[:5]]
+    case = A.Case(source=torch.cat([a.source, b.source[:6]]), start=start, target=torch.cat([a.target, b.target[:6]]), tstart=start)
+    out, transform = _loop_is_the_sequence(hip, case, 2, hip.NN_AUTO, 0)
+    hist = out["history"].cpu()
+    assert torch.equal(transform[1:4].cpu(), _identity(3).cpu()) and not torch.equal(transform[0].cpu(), _identity(1)[0].cpu())
+    assert not torch.equal(transform[4].cpu(), _identity(1)[0].cpu())
+    assert hist[:, :, 1].tolist() == [[a.n, 0, 1, 2, 3]] * 3 and bool(torch.isnan(hist[:, 1, 0]).all()) and bool((hist[:, 1:4, 2] == 1.0).all())
+
+
+def test_no_aligner_writes_into_its_init(hip):
+    """``init`` is copied: a float64 (4, 4) matrix on the GPU, of which one scene's first three rows are contiguous as they lie, and the
+    matrix of a previous result keep their bits through every aligner, whose result is another transform."""
+    from mvdfusion_amd import fusion
+    import meshdist_f64 as M
+    n = 200
+    src = A.bulged_ellipsoid(n, 8190)
+    tgt = A.apply(A.similarity(1.0, 4.0, (1, -2, 0.5), (0.02, -0.01, 0.015))[:3][None], src, [0, n])
+    src, tgt = src.cuda(), tgt.cuda()
+    cube = M.make_case("cube")
+    mesh = fusion.TriangleMesh(vertices=torch.from_numpy(cube.vertices).cuda(), faces=torch.from_numpy(cube.faces).cuda(), rgb=None,
+                               vertex_start=torch.tensor([0, len(cube.vertices)], dtype=torch.int32),
+                               face_start=torch.tensor([0, len(cube.faces)], dtype=torch.int32))
+    aligners = dict(align_geometry=lambda init: fusion.align_geometry(src, tgt, iters=2, init=init),
+                    align_to_surface=lambda init: fusion.align_to_surface(src, tgt, iters=2, init=init),
+                    align_to_mesh=lambda init: fusion.align_to_mesh(src, mesh, iters=2, init=init))
+    inits = dict(matrix=lambda: torch.from_numpy(A.similarity(1.0, 1.0, (0, 0, 1), (0.01, 0.0, -0.01))).cuda(),
+                 alignment=lambda: fusion.align_geometry(src, tgt, iters=1),
+                 registration=lambda: fusion.register_geometry(src, tgt, rotations=16, samples=64, candidates=2, refine_iters=2, iters=2))
+    written = []
+    for form, make in inits.items():
+        for name, run in aligners.items():
+            init = make()
+            held = init if torch.is_tensor(init) else init.matrix
+            assert held.dtype == torch.float64 and held.is_cuda
+            before = held.clone()
+            result = run(init)
+            torch.cuda.synchronize()
+            assert not torch.equal(result.matrix.reshape(4, 4), before.reshape(4, 4)), (form, name)          # (so the check below is not vacuous)
+            if not _same(held, before):
+                written.append((form, name))
+    assert not written, written
+
+
 # ------------------------------------------------------------------------------------------------ 4. determinism and batching
 def test_runs_repeat_and_a_batch_equals_its_scenes(hip):
     from mvdfusion_amd import fusion

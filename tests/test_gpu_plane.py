@@ -211,6 +211,43 @@ def test_exact_partners_converge_to_the_permutation(hip):
         assert torch.equal(out["transform"], other["transform"]) and torch.equal(out["history"], other["history"])
 
 
+def _by_hand(hip, case, iters, method, grid):
+    """The sequence mvd_plane_icp stands for, issued by the caller: mvd_nearest_points_stages(BUILD) once, then per row mvd_align_apply,
+    mvd_nearest_points_stages(QUERY) and mvd_plane_fit on the pairs and distances the search left."""
+    L, p, base = hip.lib(), hip.ptr, case.base
+    source, target, normals = base.source.cuda(), base.target.cuda(), case.normals.contiguous().cuda()
+    sstart, tstart, nq, nt = _i32(base.start), _i32(base.tstart), base.n, base.nt
+    transform = _identity(1)
+    history = torch.full((iters + 1, 1, 4), SENTINEL, dtype=torch.float64, device="cuda")
+    moved, index, dist2 = torch.empty_like(source), torch.empty(nq, dtype=torch.int32, device="cuda"), torch.empty(nq, device="cuda")
+    nn_bytes = int(L.mvd_nearest_points_scratch(nt, 1, method, grid))
+    nn = torch.empty((nn_bytes + 7) // 8 + 2, dtype=torch.int64, device="cuda")
+    search = lambda stages: hip.check(L.mvd_nearest_points_stages(p(moved), p(sstart), p(target), p(tstart), nq, nt, 1, method, grid, p(index), p(dist2),
+                                                                  p(nn) if nn_bytes else None, nn_bytes, stages, hip.stream()))
+    search(hip.NN_BUILD)
+    for k in range(iters + 1):
+        hip.check(L.mvd_align_apply(p(source), p(sstart), nq, 1, p(transform), p(moved), hip.stream()))
+        search(hip.NN_QUERY)
+        hip.check(_fit(hip, moved, sstart, target, normals, index, dist2, nq, nt, 1, 0 if k < iters else hip.PLANE_NO_STEP, base.max_d2, transform,
+                       history[k]))
+    torch.cuda.synchronize()
+    return dict(transform=transform, history=history, moved=moved, index=index, dist2=dist2)
+
+
+@pytest.mark.parametrize("method, grid", [("NN_AUTO", 0), ("NN_BRUTE", 0), ("NN_GRID", 9)])
+def test_the_loop_is_the_sequence_it_stands_for(hip, method, grid):
+    """mvd_plane_icp against the caller-issued sequence: every output and every history column, bit for bit (no column is carried from
+    row to row)."""
+    case, iters, method = P.make_case("icp_exact"), 4, getattr(hip, method)
+    rc, out, _ = _icp(hip, case, iters, method=method, grid=grid)
+    assert rc == 0, hip.lib().mvd_last_error()
+    hand = _by_hand(hip, case, iters, method, grid)
+    bits = lambda t: t.view(torch.int64 if t.dtype == torch.float64 else torch.int32)
+    assert not bool((out["history"] == SENTINEL).any()) and not torch.equal(out["transform"], _identity(1))
+    for k in ("transform", "history", "moved", "index", "dist2"):
+        assert torch.equal(bits(hand[k]), bits(out[k])), k
+
+
 def test_sliding_follows_the_oracle_to_a_sixteenth_of_its_own_error(hip):
     ref = P.icp_refs("icp_sliding")
     case = ref.case
