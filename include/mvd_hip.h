@@ -139,7 +139,8 @@ typedef struct mvd_gemm_desc {
   int ldr;
   /* MVD_EPI_QKV */
   void *q_hi, *q_lo, *k_hi, *k_lo, *vt_hi, *vt_lo;
-  int heads, dhead, L, Lpad; /* rows m = b*L + token */
+  int heads, dhead, L, Lpad; /* rows m = b*L + token.  heads*dhead % 32 == 0 (the epilogue routes 32-column blocks, each inside one of
+                                q / k / v), dhead % 4 == 0, L % 4 == 0: anything else is refused */
   float qscale;              /* dhead^-0.5 * log2(e), applied to q in fp32 before the split: mvd_attention computes its
                                 softmax with exp2 on the raw q.k products */
   /* split-K: 1 = none; >1 = that many K slices; 0 = choose automatically (fills the 256 CUs when the tile grid
@@ -324,7 +325,10 @@ size_t mvd_attn_qk_plane_elems(int B, int heads, int L, int dhead);
 size_t mvd_attn_vt_plane_elems(int B, int heads, int L, int dhead);
 int mvd_attn_lpad(int L);
 /* L = tokens (rows) per batch item; Lkeys (0 = L) = the leading tokens that take part as KEYS: a sequence padded to a multiple
- * of 4 rows (CLIP: 257 -> 260) keeps its padding rows out of every softmax. */
+ * of 4 rows (CLIP: 257 -> 260) keeps its padding rows out of every softmax.
+ * Head widths served: dhead % 4 == 0 with roundup(dhead, 16) in {16, 32, 48, 64, 80, 160}, i.e. 4..80 and 148..160; any other
+ * width (84..144, above 160) is refused.  Key rows / V^T columns [Lkeys, Lpad) and query rows [L, Lpad) may hold any finite
+ * values (they are masked or never stored); channels [dhead, roundup(dhead, 16)) of q and k must be zero. */
 int mvd_attention(const void* q_hi, const void* q_lo, const void* k_hi, const void* k_lo, const void* vt_hi,
                   const void* vt_lo, void* out_sp, int ldo, int B, int heads, int L, int Lkeys, int dhead, int prec,
                   mvd_stream_t stream);

@@ -518,7 +518,7 @@ extern "C" int mvd_attention(const void* q_hi, const void* q_lo, const void* k_h
     rc = launch_attn<3>(q_hi, q_lo, k_hi, k_lo, vt_hi, vt_lo, out_sp, ldo, B, heads, L, Lk, Lpad, dhead, (hipStream_t)stream);
   else
     rc = launch_attn<1>(q_hi, q_lo, k_hi, k_lo, vt_hi, vt_lo, out_sp, ldo, B, heads, L, Lk, Lpad, dhead, (hipStream_t)stream);
-  MVD_CHECK_ARG(rc == 0, "mvd_attention: unsupported head dim %d (supported: <=32, 33..64, 65..96 with dv 80, 160)", dhead);
+  MVD_CHECK_ARG(rc == 0, "mvd_attention: unsupported head dim %d (supported: 4..80 and 148..160, i.e. roundup(dhead, 16) in {16, 32, 48, 64, 80, 160})", dhead);
   MVD_CHECK_LAUNCH("mvd_attention");
   return 0;
 }

@@ -510,7 +510,11 @@ extern "C" int mvd_gemm(const mvd_gemm_desc* dp, mvd_stream_t stream) {
     d.bias_b = nullptr;
   } else if (d.epi == MVD_EPI_QKV) {
     MVD_CHECK_ARG(d.q_hi && d.q_lo && d.k_hi && d.k_lo && d.vt_hi && d.vt_lo, "mvd_gemm: QKV planes missing");
-    MVD_CHECK_ARG(d.heads > 0 && d.dhead > 0 && d.N == 3 * d.heads * d.dhead, "mvd_gemm: QKV needs N == 3*heads*dhead");
+    // (the tile epilogue routes whole 32-column blocks: gemm_device.hpp `which = wn0 / C` -- a block that straddles the q | k or k | v boundary
+    //  would be stored with a head index past the last head, outside the plane)
+    MVD_CHECK_ARG(d.heads > 0 && d.dhead > 0 && (d.heads * d.dhead) % 32 == 0,
+                  "mvd_gemm: QKV needs heads*dhead %% 32 == 0 (heads=%d dhead=%d)", d.heads, d.dhead);
+    MVD_CHECK_ARG(d.N == 3 * d.heads * d.dhead, "mvd_gemm: QKV needs N == 3*heads*dhead");
     MVD_CHECK_ARG(d.L > 0 && d.M % d.L == 0 && d.Lpad >= d.L, "mvd_gemm: QKV needs M %% L == 0");
     MVD_CHECK_ARG(d.dhead % 4 == 0 && d.L % 4 == 0, "mvd_gemm: QKV needs dhead %% 4 == 0 and L %% 4 == 0");
   } else {
