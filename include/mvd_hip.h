@@ -1294,6 +1294,81 @@ int mvd_mesh_cluster_dedupe(const int* mapped_faces, const uint8_t* keep, const 
                             uint8_t* keep_out, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Inside or outside a mesh: the generalized winding number (Jacobson, Kavan, Sorkine-Hornung 2013) of a triangle mesh at every query
+ * point (csrc/winding.hip; host: mvdfusion_amd/fusion.py winding_number, signed_distance, voxelize_mesh, volume_iou).  Not in the
+ * reference either.  It is the sum over the faces of the signed solid angle seen from the query, divided by 4 pi: an integer for a
+ * closed oriented mesh (1 inside a mesh whose normals point out, as mvd_mesh_emit winds them) and a smooth function otherwise, so it
+ * degrades gracefully on the open and non-manifold meshes the mesh filter and the simplification can leave, where ray parity does not.
+ *
+ * mvd_winding_number:
+ *   Inputs, scenes, clamping of the two start tables, pointer alignment and size limits are those of mvd_nearest_on_mesh: query (nq, 3)
+ *   fp32; vertices (nv, 3) fp32; faces (nf, 3) int32 GLOBAL rows; query_start, face_start nscene + 1 int32 DEVICE values each, clamped to
+ *   [0, nq] or [0, nf]; query i of scene s sees the faces f with face_start[s] <= f < face_start[s + 1].
+ *   Candidates: a face whose three ids lie in [0, nv), whose nine coordinates are finite and whose fp64 normal n = (B - A) x (C - A) has
+ *               three components that are not all exactly 0; the components are formed as mvd_nearest_on_mesh forms them, one
+ *               subtraction of two products each (n_x = ab_y ac_z - ab_z ac_y, ...).  A face that is no candidate contributes nothing
+ *               under either method.
+ *   Per pair  : fp64 on the exact conversions of the fp32 inputs, every operation rounded once (compiled without contraction).
+ *               dot(u, v) = (u_x v_x + u_y v_y) + u_z v_z.  With q the query: a = A - q, b = B - q, c = C - q; la = sqrt(dot(a, a)),
+ *               lb, lc likewise; x = b x c (components as above); num = dot(a, x);
+ *               den = (((la lb) lc + dot(a, b) lc) + dot(b, c) la) + dot(c, a) lb.
+ *               Omega = 0 when num == 0 (a query in the face's plane: no sign of zero to argue about), else Omega = 2 atan2(num, den)
+ *               (Van Oosterom and Strackee 1983).
+ *   MVD_WIND_EXACT: S = the sum of Omega over the scene's faces in ascending face row, started from 0.  The value does not depend on
+ *               the launch geometry.
+ *   MVD_WIND_CELLS(cells, beta): one level of cells with a dipole far field (Barill et al. 2018, first order).
+ *     Grid    : per scene the box of the vertices of its candidate faces (integer atomicMin on the order-preserving keys of
+ *               mvd_nearest_points), then fp64 by the expressions of the mesh simplification: h = longest extent / cells;
+ *               n_k = clamp(floor(extent_k / h) + 1, 1, cells) (1 when h == 0); a face belongs to the cell of its centroid
+ *               g = ((A + B) + C) / 3 per axis, cell index clamp(floor((g_k - lo_k) / h), 0, n_k - 1) (0 when h == 0), linear id
+ *               (iz n_y + iy) n_x + ix.  1 <= cells <= MVD_WIND_MAX_CELLS and nscene * cells^3 <= 2^28.
+ *     Members : the list of a cell ascends by face row (count, scan, fill through an atomic cursor, rank: the pattern of the mesh
+ *               simplification).
+ *     Moments : per occupied cell over its members ascending, with the weight m_f = sqrt(dot(n_f, n_f)): M = sum m_f;
+ *               p = (sum m_f g_f) / M per axis (each term one product); N = 0.5 * sum n_f per axis; rho2 = the maximum over the
+ *               members' three vertices X of dot(X - p, X - p).  Every sum starts from 0.
+ *     Query   : over the scene's occupied cells in ascending cell id, with d = p - q and r2 = dot(d, d): the cell is FAR iff
+ *               r2 > (beta * beta) * rho2 -- strictly, so r2 == 0 is never far; beta * beta is formed once on the host.  A far cell
+ *               contributes dot(N, d) / (r2 * sqrt(r2)); a near cell the sum of Omega over its members ascending, started from 0.
+ *               S = the sum of the cells' contributions in that order, started from 0.
+ *               beta = +inf makes every cell near, beta = 0 every cell with r2 > 0 far.  cells = 1 with beta = +inf gives the bits of
+ *               MVD_WIND_EXACT.  The far field's error is a property of this rule, not of the arithmetic: DESIGN.md has it measured.
+ *   MVD_WIND_AUTO : chosen from nf / nscene on the host; cells = 0 asks for the library's choice, a host function of nf / nscene
+ *               (csrc/winding.hip: kWCellsMinFaces, kWCellsFactor).  Both are INTERFACE defaults from a cost model, not from a sweep.
+ *   Outputs   : each optional -- a NULL is not written.  winding (nq,) fp64 (8-byte aligned): w = S / (4.0 * 3.141592653589793);
+ *               inside (nq,) uint8: w >= 0.5.  A query with a non-finite coordinate, or of no scene, gets w = NaN, inside = 0; a query
+ *               whose scene has no candidate face gets w = 0, inside = 0.
+ *   beta >= 0 or +inf; a NaN is refused (MVD_WIND_EXACT checks it too).  nq = 0 and nf = 0 are valid calls.
+ *   scratch   : mvd_winding_scratch(nf, nscene, method, cells) bytes, 16-byte aligned -- a function of these four alone; 0 bytes (NULL
+ *               allowed) for MVD_WIND_EXACT and wherever MVD_WIND_AUTO resolves to it; the function returns 0 for an argument out of
+ *               range.
+ *   Enqueued on the caller's stream with no host synchronisation and no allocation; every argument is checked before anything is
+ *   enqueued; a refused call writes nothing and names the entry in mvd_last_error(); every scratch word that is read is written
+ *   earlier in the same call; everything read back from the scratch is clamped.  Integer atomics only and every fp64 sum in list
+ *   order: the same bits run to run, and for a scene alone or inside a batch.
+ *   Kernels   : MVD_WIND_EXACT stages resolved face records through LDS in tiles of MVD_WIND_FACE_TILE, one thread per query;
+ *               MVD_WIND_CELLS stages the 64-byte occupied-cell records in tiles of MVD_WIND_CELL_TILE and walks a near cell's
+ *               resolved 36-byte member records from global memory.
+ * mvd_winding_number_stages: the same call restricted to `stages` (MVD_NN_BUILD -- nothing for MVD_WIND_EXACT --, MVD_NN_QUERY), for
+ *   timing the two or for several query sets against one built grid (same vertices, faces, face_start, nf, nscene, method, cells).
+ *
+ * Out of scope: a tree or several levels of cells and higher-order expansions; winding numbers of point clouds; ray casting; mesh
+ * volume and area; repairing orientation; hole filling; gradients. */
+#define MVD_WIND_AUTO 0
+#define MVD_WIND_EXACT 1
+#define MVD_WIND_CELLS 2
+#define MVD_WIND_MAX_CELLS 64
+#define MVD_WIND_FACE_TILE 512
+#define MVD_WIND_CELL_TILE 128
+size_t mvd_winding_scratch(size_t nf, int nscene, int method, int cells);
+int mvd_winding_number(const float* query, const int* query_start, const float* vertices, const int* faces, const int* face_start, size_t nq,
+                       size_t nv, size_t nf, int nscene, int method, int cells, double beta, double* winding, unsigned char* inside,
+                       void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+int mvd_winding_number_stages(const float* query, const int* query_start, const float* vertices, const int* faces, const int* face_start,
+                              size_t nq, size_t nv, size_t nf, int nscene, int method, int cells, double beta, double* winding,
+                              unsigned char* inside, void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

@@ -43,6 +43,11 @@ non-manifold and misoriented edges with the Euler characteristic, a face filter 
 area-weighted vertex normals for ``write_ply``, and Taubin smoothing.  All of them rest on one deterministic vertex -> face incidence
 table built on the device; each reads back at most one small table of counts.  ``ViewFusion.mesh`` forwards ``largest``, ``min_faces``
 and ``smooth``.
+
+``winding_number`` says whether a point lies inside a mesh (include/mvd_hip.h: mvd_winding_number): the generalized winding number, which
+stays meaningful on the open and non-manifold meshes the steps above can leave.  ``signed_distance`` signs ``nearest_on_mesh`` with it,
+``voxelize_mesh`` turns a mesh back into an occupancy volume over ``integrate_tsdf``'s box, and ``volume_iou`` is the volumetric
+intersection over union beside Chamfer and F-score.  None of them synchronises; nothing of the model is bound, so no ``ViewFusion`` method.
 """
 import math
 from dataclasses import dataclass
@@ -836,6 +841,174 @@ def nearest_on_mesh(query, mesh, scenes=1, method="auto", grid=None):
     vertices, faces, face_start = _mesh_arrays(mesh, N, dev)
     q = q.float().contiguous()
     return _nearest_on_mesh(q, _scene_start(q_scene, int(q.shape[0]), N, dev), vertices, faces, face_start, N, method, grid)
+
+
+WINDING_BETA = 2.0                           # Barill et al.'s accuracy parameter of the far field: an INTERFACE default, not swept here
+WINDING_METHODS = {"auto": hip.WIND_AUTO, "exact": hip.WIND_EXACT, "cells": hip.WIND_CELLS}
+
+
+@dataclass
+class WindingNumber:
+    """What ``winding_number`` returns, per query point."""
+    value: torch.Tensor                      # (nq,) fp64: the generalized winding number; NaN for a non-finite query or one of no scene
+    inside: torch.Tensor                     # (nq,) bool: value >= 0.5
+    scene: torch.Tensor                      # (nq,) int64: the scene each query was tested against
+
+
+@dataclass
+class SignedDistance:
+    """What ``signed_distance`` returns, per query point."""
+    nearest: NearestOnMesh                   # ``nearest_on_mesh`` of the same query
+    inside: torch.Tensor                     # (nq,) bool: ``winding_number`` of the same query
+    distance: torch.Tensor                   # (nq,) fp32: sqrt(nearest.dist2), negated where inside
+
+
+@dataclass
+class OccupancyVolume:
+    """What ``voxelize_mesh`` returns: ``occupied`` is (N, G, G, G) bool in z, y, x order over the box center +- half_extent; voxel
+    (k, j, i) has its centre where ``TSDFVolume`` puts it, center - half_extent + (index + 0.5) * 2 * half_extent / G per axis."""
+    occupied: torch.Tensor
+    center: tuple
+    half_extent: float
+
+
+@dataclass
+class VolumeIoU:
+    """What ``volume_iou`` returns, per scene."""
+    intersection: torch.Tensor               # (N,) int64: voxels both sides occupy
+    union: torch.Tensor                      # (N,) int64: voxels either side occupies
+    iou: torch.Tensor                        # (N,) fp64: intersection / union, NaN where union == 0
+
+
+def _check_winding(scenes, method, cells, beta):
+    if isinstance(scenes, bool) or int(scenes) != scenes or not 1 <= scenes <= 65535:
+        raise ValueError(f"scenes = {scenes}: an integer in [1, 65535]")
+    if method not in WINDING_METHODS:
+        raise ValueError(f"method = {method!r}: one of {sorted(WINDING_METHODS)}")
+    if cells is not None and (isinstance(cells, bool) or int(cells) != cells or not 1 <= cells <= hip.WIND_MAX_CELLS):
+        raise ValueError(f"cells = {cells}: None or an integer in [1, {hip.WIND_MAX_CELLS}]")
+    if cells is not None and int(scenes) * int(cells) ** 3 > hip.WIND_MAX_TABLE:
+        raise ValueError(f"cells = {cells} for {scenes} scene(s): scenes * cells^3 <= 2^28")
+    if isinstance(beta, bool) or not float(beta) >= 0.0:
+        raise ValueError(f"beta = {beta}: >= 0 or inf")
+    return int(scenes), WINDING_METHODS[method], 0 if cells is None else int(cells), float(beta)
+
+
+def _winding(query, query_start, vertices, faces, face_start, N, method, cells, beta):
+    """The enqueues of mvd_winding_number, both outputs -> (value (nq,) fp64, inside (nq,) uint8).  No host synchronisation."""
+    L = hip.lib()
+    dev, nq, nv, nf = query.device, int(query.shape[0]), int(vertices.shape[0]), int(faces.shape[0])
+    hip._req(query), hip._req(vertices), hip._req(faces, torch.int32), hip._req(query_start, torch.int32), hip._req(face_start, torch.int32)
+    value = torch.empty(nq, dtype=torch.float64, device=dev)
+    inside = torch.empty(nq, dtype=torch.uint8, device=dev)
+    nbytes = int(L.mvd_winding_scratch(nf, N, method, cells))
+    scratch = _scratch(nbytes, dev)
+    hip.check(L.mvd_winding_number(_p(query), hip.ptr(query_start), _p(vertices), _p(faces), hip.ptr(face_start), nq, nv, nf, N, method, cells,
+                                   beta, _p(value), _p(inside), _p(scratch), nbytes, hip.stream()))
+    return value, inside
+
+
+def winding_number(query, mesh, scenes=1, method="auto", cells=None, beta=WINDING_BETA):
+    """The generalized winding number of ``mesh`` at every point of ``query`` (include/mvd_hip.h: mvd_winding_number has the rule)
+    -> WindingNumber.  1 inside a closed mesh whose normals point out (``extract_mesh`` winds them so), 0 outside, and a smooth value in
+    between near the holes of an open or non-manifold mesh -- where a ray-parity test has no answer; ``inside`` is ``value >= 0.5``.
+
+    query   : what ``nearest_points`` takes: an (n, 3) tensor (scene 0) or anything with ``.xyz`` and a sorted ``.scene``.
+    mesh    : a TriangleMesh; a point sees the faces of its own scene only.  A mesh of more scenes than ``scenes`` is refused.
+    method  : "exact" (every face, the sum in face order), "cells" (one level of cells with a dipole far field; near cells are summed
+              exactly) or "auto" (the library chooses from the faces per scene).
+    cells   : cells per axis for "cells", 1 .. hip.WIND_MAX_CELLS; None leaves it to the library.
+    beta    : a cell is far when the query is further from its centre than beta times its radius; inf makes "cells" exact.  The
+              default 2 is Barill et al.'s and, like the automatic method and cells, an INTERFACE default (DESIGN.md has the far field's
+              error measured: about 2e-2 at beta = 2, 6e-3 at beta = 3, in the winding number).
+    A face with an id outside the vertices, a non-finite coordinate or a zero normal contributes nothing.  Nothing is read back."""
+    N, method, cells, beta = _check_winding(scenes, method, cells, beta)
+    q, q_scene = _points_of(query, "query", N)
+    dev = q.device
+    vertices, faces, face_start = _mesh_arrays(mesh, N, dev)
+    q = q.float().contiguous()
+    value, inside = _winding(q, _scene_start(q_scene, int(q.shape[0]), N, dev), vertices, faces, face_start, N, method, cells, beta)
+    scene = torch.zeros(int(q.shape[0]), dtype=torch.int64, device=dev) if q_scene is None else q_scene.to(dev, torch.int64)
+    return WindingNumber(value=value, inside=inside.bool(), scene=scene)
+
+
+def signed_distance(query, mesh, scenes=1, method="auto", grid=None, winding="auto", cells=None, beta=WINDING_BETA):
+    """The signed distance of every point of ``query`` to ``mesh`` -> SignedDistance: ``nearest_on_mesh`` for the magnitude and
+    ``winding_number`` for the sign (negative inside), combined in torch ops.  method, grid go to the search; winding, cells, beta to
+    the inside test (its ``method``).  The magnitude is exact; the sign is that of the winding number, whatever holes the mesh has."""
+    _check_winding(scenes, winding, cells, beta)
+    near = nearest_on_mesh(query, mesh, scenes=scenes, method=method, grid=grid)
+    inside = winding_number(query, mesh, scenes=scenes, method=winding, cells=cells, beta=beta).inside
+    dist = near.dist
+    return SignedDistance(nearest=near, inside=inside, distance=torch.where(inside, -dist, dist))
+
+
+def _check_voxels(grid, center, half_extent, N):
+    if isinstance(grid, bool) or int(grid) != grid or not 1 <= grid <= 1024 or N * int(grid) ** 3 > 2 ** 31 - 1:
+        raise ValueError(f"grid = {grid} for {N} scene(s): an integer in [1, 1024] with scenes * grid^3 <= 2^31 - 1")
+    center = tuple(float(v) for v in center)
+    if len(center) != 3:
+        raise ValueError(f"center = {center}: three floats")
+    half_extent = float(half_extent)
+    if not 0 < half_extent < float("inf"):
+        raise ValueError(f"half_extent = {half_extent}: > 0")
+    return int(grid), center, half_extent
+
+
+def voxel_centres(grid, center=(0, 0, 0), half_extent=0.75):
+    """(G^3, 3) fp32 on the host: the voxel centres of ``TSDFVolume``'s box in z, y, x order (x fastest), each coordinate formed in fp64
+    as center - half_extent + (index + 0.5) * 2 * half_extent / G and rounded once."""
+    G, center, half_extent = _check_voxels(grid, center, half_extent, 1)
+    idx = torch.arange(G, dtype=torch.float64)
+    axis = [c - half_extent + (idx + 0.5) * 2 * half_extent / G for c in center]
+    zz, yy, xx = torch.meshgrid(axis[2], axis[1], axis[0], indexing="ij")
+    return torch.stack([xx, yy, zz], dim=-1).reshape(-1, 3).float()
+
+
+def voxelize_mesh(mesh, grid=128, center=(0, 0, 0), half_extent=0.75, method="auto", cells=None, beta=WINDING_BETA):
+    """A TriangleMesh -> OccupancyVolume: ``winding_number(...).inside`` at every voxel centre of the box ``integrate_tsdf`` uses, every
+    scene of the mesh against the same box.  grid: G voxels per side; method, cells, beta: those of ``winding_number``.  Nothing is
+    read back from the device."""
+    if not isinstance(mesh, TriangleMesh):
+        raise ValueError("mesh must be a TriangleMesh")
+    N = int(mesh.face_start.numel()) - 1
+    if N < 1:
+        raise ValueError("mesh: no scene")
+    G, center, half_extent = _check_voxels(grid, center, half_extent, N)
+    N, method, cells, beta = _check_winding(N, method, cells, beta)
+    dev = mesh.vertices.device
+    vertices, faces, face_start = _mesh_arrays(mesh, N, dev)
+    q = voxel_centres(G, center, half_extent).to(dev).repeat(N, 1).contiguous()
+    q_start = (torch.arange(N + 1, dtype=torch.int64) * G ** 3).to(torch.int32).to(dev)
+    _, inside = _winding(q, q_start, vertices, faces, face_start, N, method, cells, beta)
+    return OccupancyVolume(occupied=inside.bool().reshape(N, G, G, G), center=center, half_extent=half_extent)
+
+
+def volume_iou(a, b, grid=128, center=(0, 0, 0), half_extent=0.75, method="auto", cells=None, beta=WINDING_BETA):
+    """Volumetric intersection over union of two geometries per scene -> VolumeIoU.  Each side is a TriangleMesh, voxelised by
+    ``voxelize_mesh``, or an OccupancyVolume.  A volume fixes the box: a mesh beside it is voxelised into the volume's grid, center and
+    half_extent, two volumes must agree on them, and the arguments given here count only between two meshes.  The counts are integer
+    sums, so the result is the same bits run to run.  Nothing is read back from the device."""
+    sides = (a, b)
+    if not all(isinstance(s, (TriangleMesh, OccupancyVolume)) for s in sides):
+        raise ValueError("volume_iou: each side is a TriangleMesh or an OccupancyVolume")
+    G, center, half_extent = _check_voxels(grid, center, half_extent, 1)
+    boxes = [(int(s.occupied.shape[-1]), tuple(float(v) for v in s.center), float(s.half_extent)) for s in sides if isinstance(s, OccupancyVolume)]
+    for s in sides:
+        if isinstance(s, OccupancyVolume) and (s.occupied.dim() != 4 or len(set(s.occupied.shape[1:])) != 1 or s.occupied.dtype != torch.bool):
+            raise ValueError(f"volume_iou: occupied of shape {tuple(s.occupied.shape)} and dtype {s.occupied.dtype}, need (N, G, G, G) bool")
+    if boxes:
+        if any(box != boxes[0] for box in boxes):
+            raise ValueError(f"volume_iou: two volumes of different boxes, {boxes[0]} and {boxes[1]}")
+        G, center, half_extent = boxes[0]
+    vols = [s if isinstance(s, OccupancyVolume) else voxelize_mesh(s, G, center, half_extent, method, cells, beta) for s in sides]
+    x, y = vols[0].occupied, vols[1].occupied.to(vols[0].occupied.device)
+    if x.shape != y.shape:
+        raise ValueError(f"volume_iou: {x.shape[0]} and {y.shape[0]} scene(s)")
+    inter = (x & y).flatten(1).sum(1, dtype=torch.int64)
+    union = (x | y).flatten(1).sum(1, dtype=torch.int64)
+    iou = torch.where(union > 0, inter.double() / union.clamp(min=1).double(), torch.full_like(inter, float("nan"), dtype=torch.float64))
+    return VolumeIoU(intersection=inter, union=union, iou=iou)
 
 
 @dataclass

@@ -76,6 +76,10 @@ SIMPLIFY_PLACED_MEAN, SIMPLIFY_PLACED_QUADRIC, SIMPLIFY_PLACED_FALLBACK = 0, 1, 
 SIMPLIFY_RANK_RATIO = 1e-3                                 # MVD_SIMPLIFY_RANK_RATIO: an eigenvalue is kept above this share of the largest
 SIMPLIFY_BOX_SLACK_DIV = 1024                              # MVD_SIMPLIFY_BOX_SLACK_DIV: a cell's box is grown by h / this on each side
 SIMPLIFY_MAX_TABLE = 2 ** 28                               # the most words nscene * cells^3 of the dense cell table
+WIND_AUTO, WIND_EXACT, WIND_CELLS = 0, 1, 2                # method of mvd_winding_number
+WIND_MAX_CELLS = 64                                        # MVD_WIND_MAX_CELLS: the most cells per axis of MVD_WIND_CELLS
+WIND_FACE_TILE, WIND_CELL_TILE = 512, 128                  # MVD_WIND_FACE_TILE, MVD_WIND_CELL_TILE: records per LDS tile of the two query kernels
+WIND_MAX_TABLE = 2 ** 28                                   # the most words nscene * cells^3 of its dense cell table
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -235,6 +239,9 @@ SIGNATURES = {
     "mvd_mesh_cluster_count": (_i, [_vp] * 3 + [_sz, _sz, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mvd_mesh_cluster_emit": (_i, [_vp] * 8 + [_sz, _sz, _i, _i, _i, _sz] + [_vp] * 8 + [_sz, _vp]),
     "mvd_mesh_cluster_dedupe": (_i, [_vp] * 4 + [_sz, _sz, _vp, _vp]),
+    "mvd_winding_scratch": (_sz, [_sz, _i, _i, _i]),
+    "mvd_winding_number": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "mvd_winding_number_stages": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _i, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),
