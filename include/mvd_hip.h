@@ -1369,6 +1369,94 @@ int mvd_winding_number_stages(const float* query, const int* query_start, const 
                               unsigned char* inside, void* scratch, size_t scratch_bytes, int stages, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Texturing a mesh from views: a per-face atlas, the bake of the views into it and the lookup that brings it back into images
+ * (csrc/texture.hip; host: mvdfusion_amd/fusion.py bake_texture, sample_texture, render_mesh(texture=...), write_obj).  Not in the
+ * reference either.  A vertex colour of mvd_mesh_emit is about one colour sample per voxel and the simplification averages it again; the
+ * decoded views hold several times that detail.  The mesh arrays, scenes and clamping of the start tables are those of mvd_render_mesh.
+ *
+ * The atlas (closed form: no search, no texel-to-face table, no dilation pass):
+ *   T = texels in [1, MVD_TEX_MAX_TEXELS] texel intervals along a chart's legs; a cell is K = T + 3 texels square and holds two faces;
+ *   C >= 1 cells per row; the texture is A = C * K texels square, the same A for every scene of a call.  Texel (x, y) has its centre
+ *   at the integers (x, y), as a pixel of mvd_render_mesh has.
+ *   Cells   : local face l = f - face_start[s] of scene s is half h = l & 1 of cell c = l >> 1, which sits at column c % C, row c / C:
+ *             origin (ox, oy) = ((c % C) * K, (c / C) * K).  A face with l >= 2 * C * C has no chart: it is not baked and is looked up
+ *             as background.
+ *   Corners : of (a, b, c) -- lower half (h = 0): (ox, oy), (ox + T, oy), (ox, oy + T); upper half: the point reflection through the
+ *             cell, (ox + K - 1, oy + K - 1), (ox + K - 1 - T, oy + K - 1), (ox + K - 1, oy + K - 1 - T).
+ *   Owned   : cell-local (i, j) belongs to the lower face when i <= T, j <= T and i + j <= T + 1; to the upper face when the same test
+ *             holds for (i', j') = (K - 1 - i, K - 1 - j); to no face otherwise (the tests exclude each other: i + j <= T + 1 against
+ *             i + j >= T + 3), and to no face when its half has l >= the scene's face count.  A face owns (T + 1)(T + 2) / 2 + T
+ *             texels: the closed texel triangle and the T texels of the next diagonal, which are exactly the taps of non-zero weight
+ *             of a bilinear lookup anywhere in the closed triangle.
+ *   Barycentrics of an owned texel, with (i, j) the chart's own indices (mirrored for the upper half): b_b = i / T, b_c = j / T,
+ *             b_a = (1 - b_b) - b_c.  On the extra diagonal b_a = -1 / T: the texel extrapolates across the hypotenuse -- the gutter.
+ *   mvd_texture_atlas_side(nface_max, texels, nscene) = the smallest such A for scenes of at most nface_max faces:
+ *             C = max(1, ceil(sqrt(ceil(nface_max / 2)))) in integers.  0 for what the calls refuse: texels outside its range,
+ *             A > MVD_TEX_MAX_SIDE, nscene outside [1, 65535] or nscene * A * A >= 2^31.  The calls take any multiple A of K inside those limits.
+ *
+ * mvd_texture_bake: one thread per texel of (nscene, A, A).
+ *   vertices, colors (or NULL), faces, vertex_start, face_start, nvert, nface, nscene: as mvd_render_mesh takes them.
+ *   cams (nscene*V, MVD_CAM_RECORD): camera c = s*V + v is view v of scene s, 1 <= V <= MVD_TEX_MAX_VIEWS; rgb (nscene*V, 3, H, H) fp32
+ *   planar: the views; depth (nscene*V, Pd, Pd) fp32: the depth each view sees of the surface -- mvd_render_mesh's `depth` of this mesh
+ *   in these cameras, or any other depth map of them (then a consistency gate) --, an empty pixel not finite; Pd need not equal H;
+ *   1 <= H, Pd <= 32768.  tol finite >= 0; min_cos in [0, 1); power in [0, 8]; cull 0 or 1; blend MVD_TEX_MEAN / MVD_TEX_BEST;
+ *   znear >= 0; fill: 3 floats on the HOST, read at the call.
+ *   No face   : a texel that no face owns gets fill, views = 0, best = 255.
+ *   No view   : a face with an id outside its scene's vertex range reads no vertex: its texels get fill, views = 0, best = 255.
+ *               Otherwise the texel starts from fallback = (b_a c_a + b_b c_b) + b_c c_c per channel from the vertex colours, or fill
+ *               with colors NULL.  With n = (B - A) x (C - A) from the world positions (components as mvd_render_mesh forms them) and
+ *               nn = (n_0^2 + n_1^2) + n_2^2: a face whose nn is not finite or not > 0 has no contributing view.
+ *   Point     : X = (b_a * A + b_b * B) + b_c * C per axis.
+ *   Per view v = 0 .. V - 1 ascending, with (u, w) and the camera-space point xc of X exactly as mvd_render_mesh projects a vertex (one
+ *               function in the source), zc = xc_2.  View v CONTRIBUTES when all of, in this order:
+ *                 - zc > znear; u and w are finite;
+ *                 - cx = (1 - u) * (Pd / 2) - 0.5 and cy alike from w lie in [-0.5, Pd - 0.5];
+ *                 - d = depth[c, min(floor(cy + 0.5), Pd - 1), min(floor(cx + 0.5), Pd - 1)] is finite and zc <= d + tol.  An empty
+ *                   depth pixel is NOT visible: that keeps the background colour off the rim of the object;
+ *                 - cosv > min_cos, where n_cam_j = n_0 R[0][j] + n_1 R[1][j] + n_2 R[2][j], dot = (n_cam_0 xc_0 + n_cam_1 xc_1) +
+ *                   n_cam_2 xc_2, len = sqrt((xc_0^2 + xc_1^2) + xc_2^2), cosv = -dot / (sqrt(nn) * len), and with cull = 0
+ *                   cosv = |cosv|.
+ *               Weight: wt = 1, multiplied by cosv `power` times.  Colour: col_k = bilinear_mix(pixel_taps(u, w, H)) of channel k of
+ *               view v -- the lookup of mvd_fuse_points, one copy in the source.
+ *   Blend     : MVD_TEX_MEAN: sw += wt, sc_k += wt * col_k from 0 in view order; the texel is sc_k / sw.  MVD_TEX_BEST: col of the
+ *               largest wt, the lowest view between equal weights.  No contributing view: fallback.
+ *   Outputs   : texture (nscene, 3, A, A) fp32 planar; views (nscene, A, A) uint8 = the number of contributing views, or NULL;
+ *               best (nscene, A, A) uint8 = the view of the largest wt (under either blend), 255 without one, or NULL.
+ *   All fp32, compiled without contraction; no atomics, no scratch, one enqueue on the caller's stream, no host synchronisation.  A
+ *   texel is a pure function of its face, its chart indices and its scene's views, and A is common to the scenes of a call: the same
+ *   bits run to run, for a scene alone or inside a batch baked at the same A, and with either optional output NULL.  Every argument is
+ *   checked before anything is enqueued; a refused call writes nothing and names the entry in mvd_last_error().  nface = 0 is a valid
+ *   call.  Workgroups take whole cells and stage the resolved records of their faces in LDS.
+ *
+ * mvd_texture_sample: one thread per pixel of a mvd_render_mesh result.
+ *   face_out (nscene*M, P, P) int32 and bary (nscene*M, 3, P, P) fp32 as mvd_render_mesh wrote them; face_start, nface, nscene, M, P
+ *   with its limits; texture (nscene, 3, A, A); texels, A as above; filter; background: 3 floats on the HOST.
+ *   A pixel whose f = face_out lies in its scene's face range with l < 2 * C * C gets, with (t_a, t_b, t_c) the corners above,
+ *   t = (b_a t_a + b_b t_b) + b_c t_c per axis, clamped to [0, A - 1] (the clamp never moves a point of the chart);
+ *   MVD_TEX_NEAREST : the texel (floor(tx + 0.5), floor(ty + 0.5));
+ *   MVD_TEX_BILINEAR: x0 = floor(tx), x1 = min(x0 + 1, A - 1), wx = tx - x0, likewise in y; the four taps (y0, x0), (y0, x1), (y1, x0),
+ *                     (y1, x1) mixed as (z0 (1 - wx) + z1 wx) (1 - wy) + (z2 (1 - wx) + z3 wx) wy.  A tap whose weight is exactly 0
+ *                     (wx == 0 or wy == 0) is not read and enters as 0.
+ *   Any other pixel gets background.  rgb (nscene*M, 3, P, P) fp32.  One enqueue; checked as above.
+ *
+ * Out of scope: unwrapping into charts and seam minimisation (one chart per face is the whole atlas: simplify first); mip-maps and
+ * anisotropic filtering; inpainting unseen texels; exposure matching between views; gradients. */
+#define MVD_TEX_MEAN 0
+#define MVD_TEX_BEST 1
+#define MVD_TEX_NEAREST 0
+#define MVD_TEX_BILINEAR 1
+#define MVD_TEX_MAX_TEXELS 64
+#define MVD_TEX_MAX_SIDE 16384
+#define MVD_TEX_MAX_VIEWS 254
+int mvd_texture_atlas_side(size_t nface_max, int texels, int nscene);
+int mvd_texture_bake(const float* vertices, const float* colors, const int* faces, const int* vertex_start, const int* face_start,
+                     const float* cams, const float* rgb, const float* depth, size_t nvert, size_t nface, int nscene, int V, int H, int Pd,
+                     int texels, int A, float tol, float min_cos, int power, int cull, int blend, float znear, const float* fill,
+                     float* texture, unsigned char* views, unsigned char* best, mvd_stream_t stream);
+int mvd_texture_sample(const int* face_out, const float* bary, const int* face_start, const float* texture, size_t nface, int nscene, int M,
+                       int P, int texels, int A, int filter, const float* background, float* rgb, mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

@@ -12,13 +12,17 @@ constexpr int kCompactThreads = 256;                  // 4 wavefronts: a block c
 __device__ __forceinline__ float depth01(float lat) { return fminf(fmaxf((lat + 1.0f) / 2.0f, 0.f), 1.f); }
 
 // project() of gridattn_common.hpp that also returns camera-space z (the depth the other view's map is compared with)
-__device__ __forceinline__ void project_z(const Cam& c, const float* X, float& u, float& w, float& zc) {
-  float xc[3];
+// ... and the whole camera-space point xc (texture.hip: the viewing direction of a texel); project_z is this with zc = xc[2]
+__device__ __forceinline__ void project_xc(const Cam& c, const float* X, float& u, float& w, float* xc) {
 #pragma unroll
   for (int j = 0; j < 3; ++j) xc[j] = X[0] * c.R[0 * 3 + j] + X[1] * c.R[1 * 3 + j] + X[2] * c.R[2 * 3 + j] + c.T[j];
-  zc = xc[2];
   u = c.f[0] * xc[0] / xc[2] + c.p[0];
   w = c.f[1] * xc[1] / xc[2] + c.p[1];
+}
+__device__ __forceinline__ void project_z(const Cam& c, const float* X, float& u, float& w, float& zc) {
+  float xc[3];
+  project_xc(c, X, u, w, xc);
+  zc = xc[2];
 }
 
 // The pixel-centre lookup of NDC (u, w) in an S x S map: geometric pixel centres with a border clamp (NDC +1 is the left / top edge of

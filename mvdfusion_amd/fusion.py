@@ -48,6 +48,11 @@ and ``smooth``.
 stays meaningful on the open and non-manifold meshes the steps above can leave.  ``signed_distance`` signs ``nearest_on_mesh`` with it,
 ``voxelize_mesh`` turns a mesh back into an occupancy volume over ``integrate_tsdf``'s box, and ``volume_iou`` is the volumetric
 intersection over union beside Chamfer and F-score.  None of them synchronises; nothing of the model is bound, so no ``ViewFusion`` method.
+
+``bake_texture`` gives a mesh the colour detail of the views (include/mvd_hip.h: mvd_texture_bake): a closed-form atlas with one chart
+per face, every texel coloured from the views that see it.  ``render_mesh(texture=...)`` and ``sample_texture`` bring it back into
+images (mvd_texture_sample), ``write_obj`` saves mesh and texture as OBJ + MTL + PNG, and ``ViewFusion.texture`` binds the decoder.
+None of them synchronises beyond the mesh's own host tables.
 """
 import math
 from dataclasses import dataclass
@@ -531,18 +536,8 @@ def _raster(vertices, colors, faces, vertex_start, face_start, cams, N, M, P, cu
     return rgb, depth, face, bary, normal
 
 
-def render_mesh(mesh, cameras, size=256, cull=True, background=(1.0, 1.0, 1.0), znear=1e-3, empty_depth=float("inf")):
-    """Render a TriangleMesh into cameras by z-buffered rasterisation (include/mvd_hip.h: mvd_render_mesh has the rule) -> RenderedMesh.
-
-    mesh    : a TriangleMesh of one or several scenes (what ``extract_mesh`` returns).
-    cameras : M cameras (anything with .R .T .focal_length .principal_point): the mesh must be one scene's.  Or a list of N sets of M
-              cameras each, N the mesh's scene count: scene s goes into set s, and the outputs get a leading dimension N.
-    size    : P, the output side in pixels.  Per pixel centre the nearest face covering it with camera z > znear wins (ties: the lowest
-              face id); depth, colour and barycentrics are interpolated perspective-correctly.
-    cull    : drop back faces -- ``extract_mesh`` winds every triangle with its normal out of the surface.  A face with a vertex at or
-              behind znear is dropped whole (no near-plane clipping).
-    background, empty_depth : what a pixel no face covers holds in rgb / depth.
-    Nothing is read back from the device; the mesh's two offset tables are copied to it."""
+def _check_mesh(mesh):
+    """The mesh checks of ``render_mesh`` -> (vertices, faces, rgb or None, scene count)."""
     if not isinstance(mesh, TriangleMesh):
         raise ValueError("mesh must be a TriangleMesh")
     vertices, faces, colors = mesh.vertices, mesh.faces, mesh.rgb
@@ -559,6 +554,29 @@ def render_mesh(mesh, cameras, size=256, cull=True, background=(1.0, 1.0, 1.0), 
     if scenes < 1 or mesh.vertex_start.dim() != 1 or tuple(mesh.face_start.shape) != (scenes + 1,):
         raise ValueError(f"mesh: vertex_start of shape {tuple(mesh.vertex_start.shape)}, face_start of shape {tuple(mesh.face_start.shape)}: "
                          "need (N + 1,) each, N >= 1")
+    return vertices, faces, colors, scenes
+
+
+def render_mesh(mesh, cameras, size=256, cull=True, background=(1.0, 1.0, 1.0), znear=1e-3, empty_depth=float("inf"), texture=None,
+                filter="bilinear"):
+    """Render a TriangleMesh into cameras by z-buffered rasterisation (include/mvd_hip.h: mvd_render_mesh has the rule) -> RenderedMesh.
+
+    mesh    : a TriangleMesh of one or several scenes (what ``extract_mesh`` returns).
+    cameras : M cameras (anything with .R .T .focal_length .principal_point): the mesh must be one scene's.  Or a list of N sets of M
+              cameras each, N the mesh's scene count: scene s goes into set s, and the outputs get a leading dimension N.
+    size    : P, the output side in pixels.  Per pixel centre the nearest face covering it with camera z > znear wins (ties: the lowest
+              face id); depth, colour and barycentrics are interpolated perspective-correctly.
+    cull    : drop back faces -- ``extract_mesh`` winds every triangle with its normal out of the surface.  A face with a vertex at or
+              behind znear is dropped whole (no near-plane clipping).
+    background, empty_depth : what a pixel no face covers holds in rgb / depth.
+    texture : a MeshTexture of this mesh (``bake_texture``): rgb is then looked up in it through the face and the barycentrics of every
+              pixel (mvd_texture_sample) with ``filter`` "bilinear" or "nearest", and the mesh need not carry colour.  With the default
+              None the call is what it always was.
+    Nothing is read back from the device; the mesh's two offset tables are copied to it."""
+    vertices, faces, colors, scenes = _check_mesh(mesh)
+    if texture is not None:
+        _check_texture(texture, scenes, filter)
+        colors = None
     if int(size) != size or size < 1:
         raise ValueError(f"size = {size}: an integer >= 1")
     P, znear = int(size), float(znear)
@@ -591,6 +609,8 @@ def render_mesh(mesh, cameras, size=256, cull=True, background=(1.0, 1.0, 1.0), 
     cams = Cameras(*(torch.cat([getattr(c, k) for c in sets]) for k in ("R", "T", "focal_length", "principal_point")))
     rgb, depth, face, bary, normal = _raster(vertices, colors, faces, vertex_start, face_start, pack_cameras(cams).to(dev).contiguous(), N, M,
                                              P, bool(cull), znear, empty_depth, background)
+    if texture is not None:
+        rgb = _sample(face, bary, face_start, texture, int(faces.shape[0]), N, M, P, TEX_FILTERS[filter], background)
     lead = (M,) if single else (N, M)
     face = face.reshape(*lead, P, P)
     return RenderedMesh(rgb=None if rgb is None else rgb.reshape(*lead, 3, P, P), depth=depth.reshape(*lead, P, P), face=face,
@@ -2327,3 +2347,290 @@ def write_ply(path, cloud, normals=None):
     with open(path, "wb") as fh:
         fh.write((header + "end_header\n").encode("ascii"))
         fh.write(body)
+
+
+# ------------------------------------------------------------------------------------------------ texture
+TEX_BLENDS = {"mean": hip.TEX_MEAN, "best": hip.TEX_BEST}
+TEX_FILTERS = {"nearest": hip.TEX_NEAREST, "bilinear": hip.TEX_BILINEAR}
+
+
+def atlas_layout(nface_max, texels, scenes=1):
+    """(cells per row C, side A) of the atlas for scenes of at most ``nface_max`` faces -- mvd_texture_atlas_side's rule on the host:
+    cells of K = texels + 3 texels hold two faces each, C = max(1, ceil(sqrt(ceil(nface_max / 2)))), A = C * K."""
+    if int(texels) != texels or not 1 <= texels <= hip.TEX_MAX_TEXELS:
+        raise ValueError(f"texels = {texels}: an integer in [1, {hip.TEX_MAX_TEXELS}]")
+    cells = (int(nface_max) + 1) // 2
+    C = max(1, math.isqrt(cells - 1) + 1 if cells > 0 else 1)
+    A = C * (int(texels) + 3)
+    if A > hip.TEX_MAX_SIDE or scenes * A * A >= 2 ** 31:
+        raise ValueError(f"texels = {texels}: an atlas of {scenes} x {A} x {A} texels for {nface_max} faces per scene; the side is at most "
+                         f"{hip.TEX_MAX_SIDE} and the texel index 31 bits -- simplify the mesh or lower texels")
+    return C, A
+
+
+def _chart_of_texel(T, C, dev):
+    """Per texel of the (A, A) atlas: (local face l, chart indices i, j, owned) by the header's closed form, with torch ops."""
+    K = T + 3
+    A = C * K
+    y, x = torch.meshgrid(torch.arange(A, device=dev), torch.arange(A, device=dev), indexing="ij")
+    i, j, cell = x % K, y % K, (y // K) * C + x // K
+    lower = (i <= T) & (j <= T) & (i + j <= T + 1)
+    mi, mj = K - 1 - i, K - 1 - j
+    upper = (mi <= T) & (mj <= T) & (mi + mj <= T + 1)
+    return 2 * cell + upper.long(), torch.where(lower, i, mi), torch.where(lower, j, mj), lower | upper
+
+
+@dataclass
+class MeshTexture:
+    """What ``bake_texture`` returns; the leading scene dimension is present only for a list of camera sets.  Texel (x, y) has its centre
+    at the integers; local face l of a scene is half l & 1 of cell l >> 1, cell c at column c % cells_per_row, row c // cells_per_row
+    of cells ``texels + 3`` texels square (include/mvd_hip.h: the texture section has the layout in full)."""
+    image: torch.Tensor                      # (.., 3, A, A) fp32
+    views: torch.Tensor                      # (.., A, A) uint8: the views that contributed to the texel
+    best: torch.Tensor                       # (.., A, A) uint8: the contributing view of the largest weight, or 255
+    texels: int                              # T: texel intervals along a chart's legs
+    cells_per_row: int                       # C
+    side: int                                # A = C * (T + 3)
+    faces: tuple = ()                        # the face count of every scene the texture was baked for
+
+    def _local(self, mesh):
+        fs = mesh.face_start.long()
+        scene = torch.searchsorted(fs[1:].contiguous(), torch.arange(len(mesh)), right=True).clamp(max=fs.numel() - 2)
+        return torch.arange(len(mesh)) - fs[scene]
+
+    def corners(self, mesh):
+        """(m, 3, 2) int64: the texel (x, y) of the corners a, b, c of every face of ``mesh``."""
+        T, K, C = self.texels, self.texels + 3, self.cells_per_row
+        l = self._local(mesh)
+        cell, up = l // 2, (l % 2).bool()
+        o = torch.stack([(cell % C) * K, (cell // C) * K], dim=1)[:, None]                                   # (m, 1, 2)
+        low = torch.tensor([[0, 0], [T, 0], [0, T]])[None]
+        return torch.where(up[:, None, None], o + (K - 1) - low, o + low)
+
+    def uv(self, mesh):
+        """(m, 3, 2) fp32 in [0, 1]: the OBJ texture coordinates (u right, v UP) of the corners a, b, c of every face."""
+        c = self.corners(mesh).float()
+        return torch.stack([(c[..., 0] + 0.5) / self.side, 1.0 - (c[..., 1] + 0.5) / self.side], dim=-1)
+
+    def texel_face(self, mesh):
+        """(.., A, A) int64: the row in mesh.faces of the face that owns each texel, -1 for none -- the ownership map, built with torch
+        ops for inspection and tests (the kernels never need it)."""
+        l, _, _, owned = _chart_of_texel(self.texels, self.cells_per_row, "cpu")
+        fs = mesh.face_start.long()
+        out = [torch.where(owned & (l < fs[s + 1] - fs[s]), l + fs[s], torch.full_like(l, -1)) for s in range(fs.numel() - 1)]
+        return out[0] if self.image.dim() == 3 else torch.stack(out)
+
+    def coverage(self):
+        """The share of owned texels that at least one view contributed to: a 0-d tensor, or (N,) per scene."""
+        T = self.texels
+        per_face = (T + 1) * (T + 2) // 2 + T
+        owned = torch.tensor([min(n, 2 * self.cells_per_row ** 2) * per_face for n in self.faces], dtype=torch.float32)
+        seen = (self.views > 0).flatten(-2).sum(-1).float()
+        owned = owned.to(seen.device).reshape(seen.shape)
+        return seen / owned.clamp(min=1.0)
+
+
+def _check_texture(texture, scenes, filter):
+    if not isinstance(texture, MeshTexture):
+        raise ValueError("texture must be a MeshTexture")
+    if filter not in TEX_FILTERS:
+        raise ValueError(f"filter = {filter!r}: one of {sorted(TEX_FILTERS)}")
+    n = 1 if texture.image.dim() == 3 else int(texture.image.shape[0])
+    if texture.image.dim() not in (3, 4) or tuple(texture.image.shape[-3:]) != (3, texture.side, texture.side) or \
+            texture.side != texture.cells_per_row * (texture.texels + 3):
+        raise ValueError(f"texture: image of shape {tuple(texture.image.shape)} for side {texture.side}, texels {texture.texels}")
+    if n != scenes:
+        raise ValueError(f"texture: baked for {n} scene(s), the mesh has {scenes}")
+
+
+def _bake(vertices, colors, faces, vertex_start, face_start, cams, rgb, depth, N, V, texels, A, tol, min_cos, power, cull, blend, znear, fill):
+    """The one enqueue of mvd_texture_bake.  Mesh arrays as ``_raster`` takes them, cams (N*V, CAM_RECORD), rgb (N*V, 3, H, H), depth
+    (N*V, Pd, Pd), all contiguous on one GPU -> (texture (N, 3, A, A), views (N, A, A), best (N, A, A)).  No host synchronisation."""
+    import ctypes
+    L = hip.lib()
+    dev = vertices.device
+    hip._req(vertices), hip._req(cams), hip._req(rgb), hip._req(depth)
+    hip._req(faces, torch.int32), hip._req(vertex_start, torch.int32), hip._req(face_start, torch.int32)
+    if colors is not None:
+        hip._req(colors)
+    texture = torch.empty(N, 3, A, A, dtype=torch.float32, device=dev)
+    views, best = (torch.empty(N, A, A, dtype=torch.uint8, device=dev) for _ in range(2))
+    hip.check(L.mvd_texture_bake(_p(vertices), _p(colors), _p(faces), hip.ptr(vertex_start), hip.ptr(face_start), hip.ptr(cams), hip.ptr(rgb),
+                                 hip.ptr(depth), int(vertices.shape[0]), int(faces.shape[0]), N, V, int(rgb.shape[-1]), int(depth.shape[-1]),
+                                 texels, A, float(tol), float(min_cos), int(power), int(cull), blend, float(znear),
+                                 (ctypes.c_float * 3)(*fill), hip.ptr(texture), hip.ptr(views), hip.ptr(best), hip.stream()))
+    return texture, views, best
+
+
+def _sample(face, bary, face_start, texture, nface, N, M, P, filter, background):
+    """The one enqueue of mvd_texture_sample on ``_raster``'s face and bary -> rgb (N*M, 3, P, P)."""
+    import ctypes
+    L = hip.lib()
+    image = texture.image.reshape(N, 3, texture.side, texture.side).to(face.device, torch.float32).contiguous()
+    rgb = torch.empty(N * M, 3, P, P, dtype=torch.float32, device=face.device)
+    hip._req(bary), hip._req(face, torch.int32), hip._req(face_start, torch.int32)
+    hip.check(L.mvd_texture_sample(hip.ptr(face), hip.ptr(bary), hip.ptr(face_start), hip.ptr(image), int(nface), N, M, P, texture.texels,
+                                   texture.side, filter, (ctypes.c_float * 3)(*background), hip.ptr(rgb), hip.stream()))
+    return rgb
+
+
+def bake_texture(mesh, rgb, cameras, texels=8, depth=None, size=None, tolerance=None, min_cos=0.1, power=2, blend="mean", cull=True,
+                 fill=(0.5, 0.5, 0.5), znear=1e-3):
+    """Texture a TriangleMesh from views of it (include/mvd_hip.h: mvd_texture_bake has the rule in full) -> MeshTexture.
+
+    Every face gets a chart of its own in a closed-form atlas -- a right triangle with legs of ``texels`` texel intervals, two to a
+    cell -- so simplify first (``simplify_mesh``): the atlas has about (texels + 3)^2 / 2 texels per face.  Every texel takes the world
+    point its barycentrics name, projects it into every view and blends the colours of the views that see it.
+    rgb, cameras : as ``fuse_views`` takes them -- (V, 3, H, H) in [0, 1] with the V cameras for a one-scene mesh, or (N, V, 3, H, H)
+              with a list of N camera sets for an N-scene mesh.  V <= 254.
+    depth   : what each view sees of the surface, (.., V, Pd, Pd), empty pixels not finite.  None renders the mesh into the same cameras
+              at ``size`` (default H) pixels.  A given depth is taken as it is -- the model's own depth maps, say, which then act as a
+              consistency gate.  A view sees a texel when the texel's camera z is at most the depth of the pixel it falls into plus
+              ``tolerance`` (default TAU_FRACTION * DEPTH_SCALE, in world units); a texel over an empty depth pixel is not seen.
+    min_cos, power, cull : a view contributes where the cosine between the face normal and the direction to the camera exceeds min_cos
+              (cull=False: its absolute value), with the weight cosine^power (an integer in [0, 8]; 0 weighs the views equally).
+    blend   : "mean" the weighted mean of the contributing views, "best" the colour of the view of the largest weight.
+    fill    : what a texel of no face holds; a texel of a face no view contributes to holds the interpolated vertex colours when the
+              mesh has colour, else fill.  MeshTexture.views says which.
+
+    tolerance, min_cos and power are INTERFACE defaults: no trained checkpoint was available when this was written, so nobody has tuned
+    them on real samples -- expect to.  No seam handling beyond the gutter texel of every chart, no mip-maps, no inpainting of unseen
+    texels, no exposure matching.  The same bits run to run, and for a scene alone or in a batch baked at the same side.  No host
+    synchronisation: the atlas side comes from the mesh's own host tables."""
+    vertices, faces, colors, scenes = _check_mesh(mesh)
+    if not torch.is_tensor(rgb) or rgb.dim() not in (4, 5):
+        raise ValueError("rgb must be a (V, 3, H, H) or (N, V, 3, H, H) tensor")
+    single = rgb.dim() == 4
+    if single:
+        if isinstance(cameras, (list, tuple)):
+            raise ValueError("(V, 3, H, H) images take one camera set, not a list")
+        rgb, cameras = rgb[None], [cameras]
+        if torch.is_tensor(depth) and depth.dim() == 3:
+            depth = depth[None]
+    elif not isinstance(cameras, (list, tuple)) or len(cameras) != rgb.shape[0]:
+        raise ValueError(f"(N, V, 3, H, H) images take a list of N = {rgb.shape[0]} camera sets")
+    N, V, Cn, H, H2 = rgb.shape
+    if Cn != 3 or H != H2 or H < 1:
+        raise ValueError(f"rgb of shape {tuple(rgb.shape)}: need 3 channels and a square image")
+    if not 1 <= V <= hip.TEX_MAX_VIEWS:
+        raise ValueError(f"V = {V} views outside [1, {hip.TEX_MAX_VIEWS}]")
+    if N != scenes:
+        raise ValueError(f"cameras: {N} camera set(s) for a mesh of {scenes} scene(s)" + (" (pass a list of sets)" if single else ""))
+    sets = [_as_cameras(c) for c in cameras]
+    if any(len(c) != V for c in sets):
+        raise ValueError(f"cameras: {[len(c) for c in sets]} cameras for {N} x {V} views")
+    if blend not in TEX_BLENDS:
+        raise ValueError(f"blend = {blend!r}: one of {sorted(TEX_BLENDS)}")
+    if int(power) != power or not 0 <= power <= 8:
+        raise ValueError(f"power = {power}: an integer in [0, 8]")
+    min_cos, znear = float(min_cos), float(znear)
+    if not 0 <= min_cos < 1:
+        raise ValueError(f"min_cos = {min_cos} outside [0, 1)")
+    if not znear >= 0:
+        raise ValueError(f"znear = {znear}: >= 0")
+    if cull not in (True, False, 0, 1):
+        raise ValueError(f"cull = {cull}: True or False")
+    tol = TAU_FRACTION * DEPTH_SCALE if tolerance is None else float(tolerance)
+    if not 0 <= tol < math.inf:
+        raise ValueError(f"tolerance = {tol}: finite, >= 0")
+    fill = tuple(float(v) for v in fill)
+    if len(fill) != 3:
+        raise ValueError(f"fill = {fill}: three floats")
+    counts = tuple(int(n) for n in (mesh.face_start[1:] - mesh.face_start[:-1]))
+    C, A = atlas_layout(max(counts), texels, N)
+    T = int(texels)
+    if depth is not None:
+        if not torch.is_tensor(depth) or depth.dim() != 4 or tuple(depth.shape[:2]) != (N, V) or depth.shape[2] != depth.shape[3]:
+            raise ValueError(f"depth of shape {tuple(depth.shape) if torch.is_tensor(depth) else depth}: need (.., V, Pd, Pd) with the images' "
+                             "leading dimensions")
+    Pd = H if size is None else size
+    if depth is None and (int(Pd) != Pd or Pd < 1 or N * V * Pd * Pd >= 2 ** 31 or N * V > 65535):
+        raise ValueError(f"size = {Pd}: an integer >= 1 with N * V * size^2 < 2^31 and N * V <= 65535")
+    dev = vertices.device
+    vertices = vertices.float().contiguous()
+    faces = faces.to(dev).contiguous()
+    colors = None if colors is None else colors.to(dev, torch.float32).contiguous()
+    vertex_start, face_start = (t.to(torch.int32).to(dev).contiguous() for t in (mesh.vertex_start, mesh.face_start))
+    cams = pack_cameras(_cat_cameras(sets)).to(dev).contiguous()
+    if depth is None:
+        depth = _raster(vertices, None, faces, vertex_start, face_start, cams, N, V, int(Pd), bool(cull), znear, float("inf"), fill)[1]
+    else:
+        depth = depth.reshape(N * V, depth.shape[-1], depth.shape[-1]).to(dev, torch.float32).contiguous()
+    image = rgb.reshape(N * V, 3, H, H).to(dev, torch.float32).contiguous()
+    texture, views, best = _bake(vertices, colors, faces, vertex_start, face_start, cams, image, depth, N, V, T, A, tol, min_cos, int(power),
+                                 bool(cull), TEX_BLENDS[blend], znear, fill)
+    if single:
+        texture, views, best = texture[0], views[0], best[0]
+    return MeshTexture(image=texture, views=views, best=best, texels=T, cells_per_row=C, side=A, faces=counts)
+
+
+def sample_texture(rendered, mesh, texture, filter="bilinear", background=(1.0, 1.0, 1.0)):
+    """The RenderedMesh ``rendered`` of ``mesh`` with its rgb looked up in ``texture`` (mvd_texture_sample): what
+    ``render_mesh(mesh, cameras, texture=texture)`` returns, for a render that already exists.  No host synchronisation."""
+    import dataclasses
+    _, faces, _, scenes = _check_mesh(mesh)
+    _check_texture(texture, scenes, filter)
+    if not isinstance(rendered, RenderedMesh):
+        raise ValueError("rendered must be a RenderedMesh")
+    background = tuple(float(v) for v in background)
+    if len(background) != 3:
+        raise ValueError(f"background = {background}: three floats")
+    single = rendered.face.dim() == 3
+    N = 1 if single else int(rendered.face.shape[0])
+    if N != scenes:
+        raise ValueError(f"rendered: {N} scene(s), the mesh has {scenes}")
+    M, P = int(rendered.face.shape[-3]), int(rendered.face.shape[-1])
+    dev = rendered.face.device
+    face = rendered.face.reshape(N * M, P, P).contiguous()
+    bary = rendered.bary.reshape(N * M, 3, P, P).contiguous()
+    rgb = _sample(face, bary, mesh.face_start.to(torch.int32).to(dev).contiguous(), texture, int(faces.shape[0]), N, M, P, TEX_FILTERS[filter],
+                  background)
+    out = dataclasses.replace(rendered, rgb=rgb.reshape(*rendered.bary.shape))
+    if "_depth_map" in vars(rendered):
+        out._depth_map = rendered._depth_map
+    return out
+
+
+def _png(image):
+    """An (h, w, 3) uint8 array as the bytes of an 8-bit RGB PNG (zlib + struct: no imaging library)."""
+    import struct
+    import zlib
+    h, w = int(image.shape[0]), int(image.shape[1])
+    chunk = lambda tag, data: struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xffffffff)
+    rows = b"".join(b"\x00" + image[y].tobytes() for y in range(h))
+    return b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(rows, 6)) + \
+        chunk(b"IEND", b"")
+
+
+def write_obj(path, mesh, texture, scene=None):
+    """A textured mesh as Wavefront OBJ: ``path`` (v, three vt per face, f a/ta b/tb c/tc, 1-based), ``path + ".mtl"`` (map_Kd) and the
+    texture as an 8-bit RGB PNG next to it (round(255 clip(image)), row 0 on top).  One scene per file: a mesh of several takes
+    ``scene=``."""
+    import os
+    import numpy as np
+    _, _, _, scenes = _check_mesh(mesh)
+    _check_texture(texture, scenes, "bilinear")
+    if scenes > 1 and scene is None:
+        raise ValueError(f"write_obj: a mesh of {scenes} scenes takes scene=")
+    s = 0 if scene is None else int(scene)
+    if not 0 <= s < scenes:
+        raise ValueError(f"scene {scene} of a mesh of {scenes} scene(s)")
+    f0 = int(mesh.face_start[s])
+    sub = mesh.scene(s)
+    uv = texture.uv(mesh)[f0:f0 + len(sub)].reshape(-1, 2).numpy()
+    image = texture.image if texture.image.dim() == 3 else texture.image[s]
+    pixels = np.rint(np.clip(image.detach().cpu().numpy(), 0.0, 1.0) * 255.0).astype("u1").transpose(1, 2, 0)
+    stem = os.path.splitext(os.path.basename(path))[0]
+    png, mtl = os.path.splitext(path)[0] + ".png", path + ".mtl"
+    with open(png, "wb") as fh:
+        fh.write(_png(np.ascontiguousarray(pixels)))
+    with open(mtl, "w") as fh:
+        fh.write(f"newmtl {stem}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {os.path.basename(png)}\n")
+    v = sub.vertices.detach().cpu().numpy()
+    f = sub.faces.detach().cpu().numpy().astype("i8") + 1
+    lines = [f"mtllib {os.path.basename(mtl)}", f"usemtl {stem}"]
+    lines += [f"v {x:.9g} {y:.9g} {z:.9g}" for x, y, z in v]
+    lines += [f"vt {a:.9g} {b:.9g}" for a, b in uv]
+    lines += [f"f {a}/{3 * k + 1} {b}/{3 * k + 2} {c}/{3 * k + 3}" for k, (a, b, c) in enumerate(f)]
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")

@@ -80,6 +80,9 @@ WIND_AUTO, WIND_EXACT, WIND_CELLS = 0, 1, 2                # method of mvd_windi
 WIND_MAX_CELLS = 64                                        # MVD_WIND_MAX_CELLS: the most cells per axis of MVD_WIND_CELLS
 WIND_FACE_TILE, WIND_CELL_TILE = 512, 128                  # MVD_WIND_FACE_TILE, MVD_WIND_CELL_TILE: records per LDS tile of the two query kernels
 WIND_MAX_TABLE = 2 ** 28                                   # the most words nscene * cells^3 of its dense cell table
+TEX_MEAN, TEX_BEST = 0, 1                                  # blend of mvd_texture_bake
+TEX_NEAREST, TEX_BILINEAR = 0, 1                           # filter of mvd_texture_sample
+TEX_MAX_TEXELS, TEX_MAX_SIDE, TEX_MAX_VIEWS = 64, 16384, 254      # MVD_TEX_MAX_TEXELS, MVD_TEX_MAX_SIDE, MVD_TEX_MAX_VIEWS
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -242,6 +245,9 @@ SIGNATURES = {
     "mvd_winding_scratch": (_sz, [_sz, _i, _i, _i]),
     "mvd_winding_number": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _vp]),
     "mvd_winding_number_stages": (_i, [_vp] * 5 + [_sz, _sz, _sz, _i, _i, _i, C.c_double, _vp, _vp, _vp, _sz, _i, _vp]),
+    "mvd_texture_atlas_side": (_i, [_sz, _i, _i]),
+    "mvd_texture_bake": (_i, [_vp] * 8 + [_sz, _sz] + [_i] * 6 + [_f, _f, _i, _i, _i, _f, C.POINTER(_f)] + [_vp] * 4),
+    "mvd_texture_sample": (_i, [_vp] * 4 + [_sz] + [_i] * 6 + [C.POINTER(_f), _vp, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),

@@ -674,17 +674,22 @@ class ViewFusion(nn.Module):
         return img.reshape(*latents.shape[:-3], 3, img.shape[-2], img.shape[-1])
 
     @torch.no_grad()
-    def mesh(self, latents, batch_cameras, grid=128, up=8, decode=True, largest=None, min_faces=None, smooth=0, simplify=None, **kw):
+    def mesh(self, latents, batch_cameras, grid=128, up=8, decode=True, largest=None, min_faces=None, smooth=0, simplify=None, texture=None,
+             **kw):
         """The sampled views as a closed triangle mesh with vertex colours: fusion.integrate_tsdf with this model's depth_scale /
         depth_shift, then fusion.extract_mesh.  latents and cameras as ``fuse`` takes them; decode: colour from ``self.decode``
         (8 S pixels per side, so up <= 8), otherwise pass ``rgb=`` or get an uncoloured mesh.  Other keywords: center, half_extent, trunc,
         carve, foreground (integrate_tsdf) and fill (extract_mesh).
         largest, min_faces: when either is given, fusion.keep_components drops the floaters of the extracted mesh; smooth: when > 0,
         fusion.smooth_mesh(iters=smooth) follows; simplify: when given, fusion.simplify_mesh(cells=simplify) comes last, after floater
-        removal and smoothing.  With the defaults none is called and the mesh is extract_mesh's own."""
-        from .fusion import extract_mesh, integrate_tsdf, keep_components, simplify_mesh, smooth_mesh
+        removal and smoothing.  With the defaults none is called and the mesh is extract_mesh's own.
+        texture: when given, the finished mesh is textured from the same images with ``texels=texture`` (fusion.bake_texture's other
+        defaults) and the return value is (mesh, MeshTexture); it needs colour (decode or ``rgb=``)."""
+        from .fusion import bake_texture, extract_mesh, integrate_tsdf, keep_components, simplify_mesh, smooth_mesh
         if decode:
             kw["rgb"] = self._decoded(latents)
+        if texture is not None and kw.get("rgb") is None:
+            raise ValueError("texture: needs images -- decode=True or rgb=")
         fill = {"fill": kw.pop("fill")} if "fill" in kw else {}
         vol = integrate_tsdf(latents, batch_cameras, grid=grid, up=up, depth_scale=self.view_attn.depth_scale,
                              depth_shift=self.view_attn.depth_shift, **kw)
@@ -695,7 +700,27 @@ class ViewFusion(nn.Module):
             mesh = smooth_mesh(mesh, iters=smooth)
         if simplify is not None:
             mesh = simplify_mesh(mesh, cells=simplify)
+        if texture is not None:
+            return mesh, bake_texture(mesh, kw["rgb"], batch_cameras, texels=texture)
         return mesh
+
+    @torch.no_grad()
+    def texture(self, mesh, latents, batch_cameras, texels=8, decode=True, **kw):
+        """A texture for a mesh of ``self.mesh`` from the sampled views (fusion.bake_texture): every texel of a per-face atlas takes
+        its colour from the decoded views that see it.  latents and cameras as ``fuse`` takes them; decode: the images are
+        ``self.decode(latents[:, :4])``, otherwise pass ``rgb=``.  Other keywords: depth, size, tolerance, min_cos, power, blend, cull,
+        fill, znear.
+
+            mesh = model.mesh(latents, batch_cameras, simplify=64)
+            tex = model.texture(mesh, latents, batch_cameras)           # tex.image (3, A, A), tex.views, tex.coverage()
+            views = model.render_mesh(mesh, batch_cameras, texture=tex)
+            fusion.write_obj("object.obj", mesh, tex)
+        """
+        from .fusion import bake_texture
+        rgb = self._decoded(latents) if decode else kw.pop("rgb", None)
+        if rgb is None:
+            raise ValueError("texture: needs images -- decode=True or rgb=")
+        return bake_texture(mesh, rgb, batch_cameras, texels=texels, **kw)
 
     @torch.no_grad()
     def render(self, cloud, cameras, size=256, radius=1, **kw):
