@@ -181,9 +181,10 @@ typedef struct mvd_gemm_desc {
    * that ran, or a 256-column span of the split-K reduce); the number of slots written per row goes to rs_count[0] (device int).
    * rs_ld >= N / 32 (the narrowest wave tile).  No atomics: the consumer adds the slots in order.  NULL = off.
    * Precision: a slot is a plain fp32 {sum x, sum x^2} over <= 256 columns and the consumer forms var = E[x^2] - mean^2 in double, so the
-   * relative error of the variance is ~1e-7 mean^2 / var: validated for rows with |mean| / std <= 3 (tests/test_gpu_ops.py::
-   * test_gemm_layernorm_fold, 2e-6); residual streams with outlier channels (|mean| / std in the hundreds) should use mvd_layernorm
-   * (two-pass) -- the host mirror's switch is Ctx.ln_fold. */
+   * relative error of the variance is ~1e-7 mean^2 / var -- the kappa term of the conditioning contract at mvd_groupnorm_nhwc below:
+   * validated for rows with |mean| / std <= 3 (tests/test_gpu_ops.py::test_gemm_layernorm_fold, 2e-6) and at 8 std against float64
+   * (tests/test_gpu_norm_f64.py::test_layernorm_folded_into_the_gemm); residual streams with outlier channels (|mean| / std in the
+   * hundreds) should use mvd_layernorm (two-pass) -- the host mirror's switch is Ctx.ln_fold. */
   float* rs_out;
   int* rs_count;
   int rs_ld;
@@ -287,7 +288,30 @@ int mvd_gemv(const float* W, const float* bias, const float* x, float* y, int M,
  * GroupNorm(32 groups) on channels-last data; `silu` bit 0 = fused SiLU, bit 1 = round the normalised value to fp16 first
  * (the VAE decoder tail, diffusionmodules/model.py:564-570) (openaimodel.py:201-203,225-227 eps 1e-5;
  * attention.py:76,243,274 and mvdfusion/attention.py:92,132 eps 1e-6; unet.py:496-498).
- * ws: B * chunks * groups * 2 doubles with chunks = mvd_groupnorm_chunks(HW); ws_elems = its capacity in doubles (checked). */
+ * ws: B * chunks * groups * 2 doubles with chunks = mvd_groupnorm_chunks(HW); ws_elems = its capacity in doubles (checked).
+ *
+ * Conditioning contract (the counterpart of the operand range contract above; bars and measurements: tests/norm_f64.py,
+ * tests/test_gpu_norm_f64.py).  Every FORWARD GroupNorm path -- mvd_groupnorm_nhwc, mvd_groupnorm_from_stats behind
+ * mvd_gemm_desc.gn_stats / mvd_concat_channels, mvd_gemm_desc.gna_out_sp, mvd_concat_groupnorm -- and the LayerNorm folded into a
+ * GEMM (mvd_gemm_desc.ln_stats) form  var = E[x^2] - mean^2  from fp32 partial sums in one pass.  With
+ *     kappa = (mean^2 + var) / (var + eps)      per (image, group) or row
+ * each x^2 carries a rounding of 2^-24, so E[x^2] is off by up to 2^-24 (mean^2 + var), var + eps by 2^-24 kappa relative and rstd
+ * by half of that; the fp32 mean in the folded shift beta - mean * rstd * gamma adds 2^-24 sqrt(kappa).  Per (image, group):
+ *     |y - GroupNorm(x)| <= (3e-6 + 2^-24 * c * kappa) * max|y|       (+ the split-plane representation of y)
+ * with c = 1 while no thread adds more than 16 terms in fp32 (the 8-rows-per-workgroup geometry of mvd_groupnorm_chunks; a float32
+ * emulation of the kernel's summation order stays below half of this: tests/test_cpu_norm_f64.py).  Longer fp32 chains pay for their
+ * length R with c = (R + 1) / 2: a prime HW leaves ONE chunk (R = HW / TY with the TY = 1 ... 4 row slices of gn_stats_kernel), the
+ * 16-row slab producers add the group's C / groups columns in order (R = C / groups + 6), the GEMM tile epilogue its wave tile's
+ * rows first (R <= 64 + C / groups).
+ * kappa is ~1 for activations with |mean| <= sigma, 65 at |mean| = 8 sigma (c = 1: 4e-6) and 4097 at 64 sigma (2.4e-4): a tensor
+ * whose groups sit many sigma off zero loses that much, silently.
+ * Statistics slot (gn_stats): {sum, sum of squares} * 2^24 in 64-bit integers.  Capacity 2^63 / 2^24 = 5.5e11 for either total, i.e.
+ * HW * (C / groups) * mean(x^2) < 5.5e11 (a 1024 x 40 group: rms |x| < 3.6e3; the `big` fixture of tests/norm_f64.py sits at a fifth
+ * of it: tests/test_cpu_norm_f64.py::test_fixture_conditions).  Resolution 2^-25 of the sum, 2^-25 / n of the mean: y moves by
+ * 2^-25 / n * rstd * gamma, which only shows for a group of a handful of elements without variance.
+ * NOT subject to kappa: mvd_groupnorm_backward takes its moments in fp64 per element (gn_moments_kernel) and mvd_layernorm /
+ * mvd_layernorm_backward take the variance in a second pass over (x - mean); only the mean rounded to fp32 enters:
+ *     error <= (project bar + 2^-23 sqrt(kappa)) * max|result| of the group / row. */
 int mvd_groupnorm_chunks(int HW);
 /* y_sp: the normalised activations in split-planes format (B*HW, C), C % 32 == 0 -- GroupNorm only feeds GEMMs / convs. */
 int mvd_groupnorm_nhwc(const float* x, void* y_sp, const float* gamma, const float* beta, int B, int HW, int C,

@@ -453,7 +453,7 @@ extern "C" int mvd_softmax_rows(const float* x, void* y_sp, int rows, int cols, 
 extern "C" int mvd_layernorm_groups(const float* x, void* y_sp, float* y_f32, const float* w, const float* b, int ldw, int rows,
                                     int rows_per_group, int C, float eps, int w_plus_one, mvd_stream_t stream) {
   MVD_CHECK_ARG(x && (y_sp || y_f32) && rows > 0, "mvd_layernorm: bad arguments");
-  MVD_CHECK_ARG(C % 32 == 0, "mvd_layernorm: split-planes output needs C %% 32 == 0 (C=%d)", C);
+  MVD_CHECK_ARG(!y_sp || C % 32 == 0, "mvd_layernorm: split-planes output needs C %% 32 == 0 (C=%d)", C);
   u16* yh = (u16*)y_sp;
   MVD_CHECK_ARG(C % 4 == 0 && C >= 4 && C <= 1280, "mvd_layernorm: C=%d must be a multiple of 4 and <= 1280", C);
   MVD_CHECK_ARG(rows_per_group > 0 && rows % rows_per_group == 0 && ldw >= 0 && ldw % 4 == 0,

@@ -675,6 +675,18 @@ def test_attention_phased_equals_single_tile(hip, prec, B, H, L, Lk, d):
     assert rel_err(planes_to_float(outs[0]), ref) < 2 * TOL[prec] + PL
 
 
+def layernorm_fold_producer(hip, x, Win, bin_, res, ws, cfg=None, splitk=1):
+    """The producer GEMM of a folded LayerNorm: t = x Win^T + bin + res as fp32 (M, C), its split planes and the per-row
+    {sum, sum of squares} slots (mvd_gemm_desc.rs_out) -> (t, planes, RowStats), all on the device."""
+    M, C = x.shape[0], Win.shape[0]
+    tp = hip.planes_like(M, C, "cuda")
+    tt = torch.empty(M, C, device="cuda")
+    rs = hip.RowStats(M, C, "cuda")
+    hip.gemm(hip.split_planes(x.cuda()), hip.pack_linear(Win.cuda(), bin_.cuda()), tt, res=res.cuda(), out_planes=tp, row_stats=rs,
+             workspace=ws, cfg=cfg, splitk=splitk)
+    return tt, tp, rs
+
+
 @pytest.mark.parametrize("pcfg,psplit", [(0, 1), (_hip.make_cfg(2, 1), 1), (_hip.make_cfg(1, 0), 1), (_hip.make_cfg(3, 4), 1), (0, 3)])
 @pytest.mark.parametrize("B,L,H,d,offs", [(2, 256, 8, 40, 0.0), (1, 64, 8, 160, 3.0), (3, 32, 4, 24, -1.5)])
 def test_gemm_layernorm_fold(hip, pcfg, psplit, B, L, H, d, offs):
@@ -697,11 +709,7 @@ def test_gemm_layernorm_fold(hip, pcfg, psplit, B, L, H, d, offs):
     ws = torch.empty(16 * 1024 * 1024, device="cuda")
     normc = norm.cuda()
     # producer: t (fp32), its planes and the row statistics
-    tp = hip.planes_like(M, C, "cuda")
-    tt = torch.empty(M, C, device="cuda")
-    rs = hip.RowStats(M, C, "cuda")
-    hip.gemm(hip.split_planes(x.cuda()), hip.pack_linear(Win.cuda(), bin_.cuda()), tt, res=res.cuda(), out_planes=tp, row_stats=rs,
-             workspace=ws, cfg=pcfg or None, splitk=psplit)
+    tt, tp, rs = layernorm_fold_producer(hip, x, Win, bin_, res, ws, pcfg or None, psplit)
     assert rel_err(tt, t) < TOL[4]
     cnt = int(rs.count.item())
     got = rs.slots[:, :cnt].sum(1).cpu().double()
