@@ -1481,6 +1481,82 @@ int mvd_texture_sample(const int* face_out, const float* bary, const int* face_s
                        int P, int texels, int A, int filter, const float* background, float* rgb, mvd_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scoring views against ground truth: squared error / PSNR, SSIM and the depth-error family (csrc/view_metrics.hip; host:
+ * mvdfusion_amd/view_metrics.py compare_images, compare_depth, compare_views, ViewFusion.compare).  Not in the reference, which scores
+ * its views with library calls.  Everything is accumulated in fp64, compiled without contraction.
+ *
+ * mvd_image_metrics: a, b (B, C, H, W) fp32 contiguous; mask (B, H, W) uint8 or NULL, non-zero = the pixel counts (NULL: every pixel).
+ *   Squared error, per image: count = the number of counted pixels; sq_sum = the sum over counted pixels and all channels of d * d with
+ *             d = double(a) - double(b) (exact: only the square rounds).
+ *   SSIM      : with weights = `window` doubles on the HOST (read at the call, passed by value into the launch; no transcendental runs
+ *             on the device), per (image, channel) plane over the "valid" region of Ho x Wo = (H - window + 1) x (W - window + 1)
+ *             window positions, position (r, c) covering pixels (r .. r + window - 1, c .. c + window - 1):
+ *               1. the five maps x = double(a), y = double(b), x * x, x * y, y * y (products of two fp32 values: exact);
+ *               2. each filtered horizontally: h(r, c) = the sum over k = 0 .. window - 1 ASCENDING of weights[k] * map(r, c + k), from 0.0;
+ *               3. each filtered vertically: E(r, c) = the sum over k ascending of weights[k] * h(r + k, c), from 0.0;
+ *               4. sxx = E[xx] - mx * mx, sxy = E[xy] - mx * my, syy = E[yy] - my * my with mx = E[x], my = E[y];
+ *               5. ssim = ((2 * mx * my + c1) * (2 * sxy + c2)) / ((mx * mx + my * my + c1) * (sxx + syy + c2)), products left to right.
+ *             ssim_map (B, C, Ho, Wo) fp64 or NULL.  Position (r, c) COUNTS when mask[b, r + window / 2, c + window / 2] is non-zero (the
+ *             mask cropped by window / 2 on each side); ssim_count = the number of counting positions of the image (not times C),
+ *             ssim_sum = the sum of ssim over the channels and the counting positions, so the mean SSIM is ssim_sum / (C * ssim_count).
+ *             Only + - * / : the map is the same bits wherever these operations round correctly.
+ *             weights NULL: no SSIM; window, c1, c2 are not looked at and ssim_sum, ssim_count, ssim_map are not written.
+ *   A pixel that is not finite enters the sums it belongs to like any other: under the mask it makes sq_sum, and ssim_sum through every
+ *   counting position whose window holds it, not finite; it is not left out.
+ *   Limits    : window odd in [3, MVD_SSIM_MAX_WINDOW]; H, W >= window with weights; 1 <= H, W <= 32768; C >= 1; B >= 0 with
+ *             B * C <= 65535 (offsets are 64-bit: no limit on B * C * H * W below those); weights, c1, c2 finite.  B = 0 succeeds and
+ *             enqueues nothing.
+ *   scratch   : mvd_image_metrics_scratch(B, C, H, W, window) bytes (window = 0 without weights), 8-byte aligned; 0 for arguments outside
+ *             the limits.  It holds one partial per (image, chunk of MVD_METRIC_CHUNK pixels) and per (plane, tile).
+ *   Kernels   : squared error: a workgroup per chunk; SSIM: a workgroup per tile of MVD_SSIM_TILE_W x MVD_SSIM_TILE_H window positions of
+ *             a plane, the fp32 tile plus halo of both images staged in LDS, the five moments taken one after the other through ONE
+ *             row-filtered fp64 plane in LDS -- 36.3 KiB per workgroup whatever the window, four workgroups per CU; then one workgroup
+ *             per image sums the partials.  Three enqueues (two without weights).
+ *
+ * mvd_depth_metrics: pred, target (B, H, W) fp32; valid (B, H, W) uint8 or NULL.  A pixel COUNTS when valid is non-zero (or NULL) and
+ *   both values are finite and > 0 (the renderers' empty depth, +inf, drops out by itself).
+ *   Pass 1    : per image n, Sp, St, Spp, Spt over the counting pixels with p = double(pred), t = double(target) (the products exact),
+ *             and the fit (s, b):  MVD_DEPTH_ALIGN_NONE: (1, 0);  _SCALE: (Spt / Spp, 0) (0 / 0 = NaN without a pixel);
+ *             _SCALE_SHIFT: det = n * Spp - Sp * Sp; s = (n * Spt - Sp * St) / det, b = (Spp * St - Sp * Spt) / det, and s = b = NaN
+ *             unless det > 0 (one pixel: det is exactly 0);  _GIVEN: pass 1 does not run, (s, b) = fit_in[image] (B, 2) fp64 on the
+ *             device -- required with _GIVEN, refused otherwise.
+ *   Pass 2    : q = s * p + b (the product, then the sum).  A counting pixel whose q is not > 0 (a NaN fit: all of them) is DROPPED and
+ *             counted as such.  Over the others, with d = q - t:
+ *               sums   (B, 4) fp64 : |d| / t;  (d * d) / t;  d * d;  l * l with l = log(q) - log(t)
+ *               counts (B, 5) int64: r < 1.25;  r < 1.5625;  r < 1.953125 with r = max(q / t, t / q) (strict: p = 4, t = 5 is not
+ *                                    below 1.25);  the pixels summed;  the pixels dropped
+ *             fit (B, 2) fp64: the (s, b) used.  Every output may be NULL.  log is the device library's fp64 logarithm, the one
+ *             operation here that is not correctly rounded (DESIGN.md has its error measured).
+ *   Limits    : 0 <= B <= 65535 (B = 0 succeeds and enqueues nothing), 1 <= H, W <= 32768.
+ *   scratch   : mvd_depth_metrics_scratch(B, H, W) bytes, 8-byte aligned; 0 outside the limits.
+ *   Kernels   : a workgroup per chunk of MVD_METRIC_CHUNK pixels and one per image for the second stage, in both passes: four
+ *             enqueues, two with _GIVEN.
+ *
+ * Both: every sum is fp64 with a fixed order -- in a thread ascending, in a workgroup a fixed tree, over the partials in the scratch
+ * thread t takes partials t, t + 256, ... and the tree again -- a function of (C, H, W, window) alone: the same bits run to run, for
+ * an image alone or at any place in a batch, and with any subset of the outputs NULL.  No floating-point atomics; the counts are
+ * integers.  Every argument is checked before anything is enqueued; a refused call returns non-zero, writes nothing and names the entry
+ * in mvd_last_error().  Work goes to the caller's stream with no host synchronisation.
+ *
+ * Out of scope: LPIPS and any other learned metric; multi-scale SSIM; "same"-padded SSIM; gradients. */
+#define MVD_SSIM_MAX_WINDOW 33
+#define MVD_SSIM_TILE_W 32
+#define MVD_SSIM_TILE_H 16
+#define MVD_METRIC_CHUNK 2048
+#define MVD_DEPTH_ALIGN_NONE 0
+#define MVD_DEPTH_ALIGN_SCALE 1
+#define MVD_DEPTH_ALIGN_SCALE_SHIFT 2
+#define MVD_DEPTH_ALIGN_GIVEN 3
+size_t mvd_image_metrics_scratch(int B, int C, int H, int W, int window);
+int mvd_image_metrics(const float* a, const float* b, const unsigned char* mask, int B, int C, int H, int W, const double* weights,
+                      int window, double c1, double c2, double* sq_sum, long long* count, double* ssim_sum, long long* ssim_count,
+                      double* ssim_map, void* scratch, size_t scratch_bytes, mvd_stream_t stream);
+size_t mvd_depth_metrics_scratch(int B, int H, int W);
+int mvd_depth_metrics(const float* pred, const float* target, const unsigned char* valid, int B, int H, int W, int align,
+                      const double* fit_in, double* fit, double* sums, long long* counts, void* scratch, size_t scratch_bytes,
+                      mvd_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * hipGraph capture of a whole denoising step and HIP-event timing on the caller's stream. */
 int mvd_graph_begin(mvd_stream_t stream);
 int mvd_graph_end(mvd_stream_t stream, void** graph_exec);

@@ -53,6 +53,10 @@ intersection over union beside Chamfer and F-score.  None of them synchronises; 
 per face, every texel coloured from the views that see it.  ``render_mesh(texture=...)`` and ``sample_texture`` bring it back into
 images (mvd_texture_sample), ``write_obj`` saves mesh and texture as OBJ + MTL + PNG, and ``ViewFusion.texture`` binds the decoder.
 None of them synchronises beyond the mesh's own host tables.
+
+How good a rendered or sampled image or depth map is -- PSNR, SSIM, abs-rel, the delta accuracies -- is measured in
+``mvdfusion_amd/view_metrics.py`` (include/mvd_hip.h: mvd_image_metrics, mvd_depth_metrics): ``compare_images``, ``compare_depth``,
+``compare_views`` on the ``RenderedViews`` / ``RenderedMesh`` records of this module, and ``ViewFusion.compare``.
 """
 import math
 from dataclasses import dataclass

@@ -83,6 +83,9 @@ WIND_MAX_TABLE = 2 ** 28                                   # the most words nsce
 TEX_MEAN, TEX_BEST = 0, 1                                  # blend of mvd_texture_bake
 TEX_NEAREST, TEX_BILINEAR = 0, 1                           # filter of mvd_texture_sample
 TEX_MAX_TEXELS, TEX_MAX_SIDE, TEX_MAX_VIEWS = 64, 16384, 254      # MVD_TEX_MAX_TEXELS, MVD_TEX_MAX_SIDE, MVD_TEX_MAX_VIEWS
+SSIM_MAX_WINDOW, SSIM_TILE_W, SSIM_TILE_H = 33, 32, 16     # MVD_SSIM_MAX_WINDOW; MVD_SSIM_TILE_W, _TILE_H: window positions per workgroup of mvd_image_metrics
+METRIC_CHUNK = 2048                                        # MVD_METRIC_CHUNK: pixels per workgroup of the pixel-wise sums of both metric entries
+DEPTH_ALIGN_NONE, DEPTH_ALIGN_SCALE, DEPTH_ALIGN_SCALE_SHIFT, DEPTH_ALIGN_GIVEN = 0, 1, 2, 3      # align of mvd_depth_metrics
 
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 c_void_p = C.c_void_p
@@ -248,6 +251,10 @@ SIGNATURES = {
     "mvd_texture_atlas_side": (_i, [_sz, _i, _i]),
     "mvd_texture_bake": (_i, [_vp] * 8 + [_sz, _sz] + [_i] * 6 + [_f, _f, _i, _i, _i, _f, C.POINTER(_f)] + [_vp] * 4),
     "mvd_texture_sample": (_i, [_vp] * 4 + [_sz] + [_i] * 6 + [C.POINTER(_f), _vp, _vp]),
+    "mvd_image_metrics_scratch": (_sz, [_i] * 5),
+    "mvd_image_metrics": (_i, [_vp] * 3 + [_i] * 4 + [C.POINTER(C.c_double), _i, C.c_double, C.c_double] + [_vp] * 6 + [_sz, _vp]),
+    "mvd_depth_metrics_scratch": (_sz, [_i] * 3),
+    "mvd_depth_metrics": (_i, [_vp] * 3 + [_i] * 4 + [_vp] * 5 + [_sz, _vp]),
     "mvd_graph_begin": (_i, [_vp]),
     "mvd_graph_end": (_i, [_vp, C.POINTER(_vp)]),
     "mvd_graph_launch": (_i, [_vp, _vp]),

@@ -753,6 +753,31 @@ class ViewFusion(nn.Module):
         return out
 
     @torch.no_grad()
+    def compare(self, latents, target_latents, decode=True, rgb=None, target_rgb=None, foreground=(0.02, 0.98), align="none", **kw):
+        """Score sampled views against ground-truth views (view_metrics.compare_images, compare_depth) -> (ImageMetrics or None,
+        DepthMetrics), each with the latents' leading dimensions.  latents, target_latents: (.., 5, S, S) of one shape.
+        decode: the images are ``self.decode`` of both stacks' four image channels (8 S pixels per side); otherwise pass ``rgb=`` and
+        ``target_rgb=`` (.., 3, H, W), or neither to score the depth alone.  The depth maps are the depth channels as ``fuse`` reads
+        them -- clamp((lat4 + 1) / 2, 0, 1) * depth_scale + depth_shift with this model's values -- scored where the TARGET's depth channel
+        is foreground (``fuse_views``' rule).  Depth at S and images at their own size: nothing is resampled, and the images are
+        scored unmasked.  align: as ``compare_depth`` takes it.  Other keywords go to ``compare_images``.
+
+            images, depth = model.compare(latents, batch_latents)      # images.psnr (V,), images.ssim, depth.abs_rel, depth.delta1
+        """
+        from .view_metrics import compare_depth, compare_images, latent_depth
+        if not torch.is_tensor(latents) or not torch.is_tensor(target_latents) or latents.shape != target_latents.shape:
+            raise ValueError("compare: latents and target_latents must be tensors of one shape (.., 5, S, S)")
+        scale, shift = float(self.view_attn.depth_scale), float(self.view_attn.depth_shift)
+        depth, _ = latent_depth(latents, scale, shift, foreground)
+        target_depth, valid = latent_depth(target_latents, scale, shift, foreground)
+        if decode:
+            rgb, target_rgb = self._decoded(latents), self._decoded(target_latents)
+        if (rgb is None) != (target_rgb is None):
+            raise ValueError("compare: rgb= and target_rgb= go together")
+        images = compare_images(rgb, target_rgb, **kw) if rgb is not None else None
+        return images, compare_depth(depth, target_depth, valid=valid, align=align)
+
+    @torch.no_grad()
     def p_losses(self, batch, trainer_config, noise_source=None, _aux=None):
         """viewfusion_zero_depth_rgb.py:362-392 -- the training objective's FORWARD pass on the HIP path: prepare_batch, shared
         random timestep, q_sample, apply_model (cfg 1, condition dropout when self.training), MSE against the noise.
