@@ -25,6 +25,8 @@
  *     (mvd_pack_*, undone exactly through acc_scale) so they always sit in the normal range.  The host mirrors check the
  *     final latents / images once per sample (mvdfusion_amd/hip.py: check_finite) and raise FloatingPointError; the bf16
  *     flavour (libmvd_hip_bf16.so, precision "bf16x3") has fp32's exponent range at ~2^-16 relative operand error.
+ *     The per-element bars that follow from this contract (operand error, fp32 roundings of the k loop, the absolute floor), their
+ *     derivation and the measurements against float64: tests/gemm_f64.py, tests/test_gpu_gemm_f64.py (CPU proof: tests/test_cpu_gemm_f64.py).
  *   - one host thread per process / GPU (matches the reference's mp.spawn model, demo.py:208).
  */
 #ifndef MVD_HIP_H
@@ -53,6 +55,7 @@ int mvd_operand_format(void);
  * image (1 KiB) is the 16x16x32 MFMA B fragment as a wave holds it: lane l = (n & 15) + 16 * ((k & 31) >> 3) owns the 8 elements
  * k & 7 = 0..7 at byte 16 l -- a granule of the LDS-DMA is one contiguous KiB and the fragment read from LDS is lane-contiguous.
  * K padded to 32, N padded to 16 with zeros.  Bytes = mvd_packed_weight_bytes(N, K).
+ * (tests/gemm_f64.py: packed_index / decode_packed decode an image from this text alone; tests/test_gpu_gemm_f64.py holds the packers to it.)
  * Replaces nothing in the reference (its weights stay fp32 nn.Parameters); the Python mirrors keep the
  * fp32 parameters under the reference's state_dict keys and pack on first use. */
 size_t mvd_packed_weight_bytes(int N, int K);
@@ -78,6 +81,9 @@ int mvd_pack_conv3x3_weight(const float* w, int Cout, int Cin, int cin_pad, floa
  *   nn.Conv2d 3x3 (s1, s2, after nearest-2x upsample)   openaimodel.py:107,116,151,204,229-231; unet.py:323,499 */
 #define MVD_A_DENSE 0   /* A: (M, K) row-major planes, leading dim lda (elements) */
 #define MVD_A_CONV3X3 1 /* A: NHWC (B, Hin, Win, Cin) planes, pad 1; M = B*Hout*Wout, K = 9*Cin */
+/* Conv geometry (Hin / Win / Hout / Wout, stride, upsample, no_pad_tl, the centre-tap tail and the four-tap form below): stated as an explicit
+ * gather over (b, oy, ox, ky, kx) in tests/gemm_f64.py (conv_taps, up4_taps) and pinned bit for bit, at non-square and odd sizes, by the
+ * `geometry` fixture of tests/test_gpu_gemm_f64.py. */
 
 #define MVD_EPI_STORE 0 /* out[m,n] = res[m,n] + colscale[n] * act(acc + bias[n] + bias_b[m / rows_per_batch, n]) */
 #define MVD_EPI_GEGLU 1 /* out[m,j] = (acc_v + bias[j]) * gelu(acc_g + bias[N/2 + j]);  out has N/2 columns */

@@ -681,7 +681,7 @@ def split_planes(x, out=None, ldp=None, scale=None):
 def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_NONE, res=None, colscale=None,
          bias_b=None, rows_per_batch=0, epi=EPI_STORE, conv=None, qkv=None, workspace=None, splitk=0, ldo=None,
          out_planes=None, out_planes_col=0, cfg=None, gn_stats=None, gn_hw=0, gn_groups=32, row_stats=None, ln=None, gn_apply=None, cat=None,
-         acc_scale_dev=None, a2=None):
+         acc_scale_dev=None, a2=None, ldr=None):
     """out = epilogue(A @ W^T).  A: split planes (M, 2*K) int16 (dense) or the NHWC image rows (B*H*W, 2*C) with
     conv=dict(B, Hin, Win, Cin, Hout, Wout, stride, upsample).  qkv = dict(planes=(qh,ql,kh,kl,vh,vl), heads, dhead, L).
     out: fp32 tensor or None; out_planes: split-planes tensor or None (feeds the next GEMM); out_planes_col: first column
@@ -697,6 +697,7 @@ def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_N
     acc_scale_dev: device scalar multiplied into the accumulator scale (mvd_gemm_desc.acc_scale_dev: the backward's 1 / gradient scale).
     a2: split planes (M, 2 * lda2) of a second input that a weight of pack_conv3x3_tail reads at the centre tap behind the convolution's
     own k-tiles: out = epilogue(conv3x3(A) + a2 @ Wt^T) (mvd_gemm_desc.tap_mode = MVD_TAPS_CENTRE_TAIL).
+    ldr: row pitch of `res` in floats (default: its last dimension), as ldo is that of `out`.
     """
     assert A.dtype == torch.int16, "A must be in split-planes format (see hip.split_planes)"
     d = GemmDesc()
@@ -750,7 +751,7 @@ def gemm(A, W, out=None, *, prec=PREC_X4, M=None, lda=None, bias=True, act=ACT_N
         d.colscale = colscale.data_ptr()
     if res is not None:
         d.res = res.data_ptr()
-        d.ldr = int(res.shape[-1])
+        d.ldr = int(ldr if ldr is not None else res.shape[-1])
     if qkv is not None:
         qh, ql, kh, kl, vh, vl = qkv["planes"]
         d.q_hi, d.q_lo, d.k_hi, d.k_lo, d.vt_hi, d.vt_lo = (t.data_ptr() for t in (qh, ql, kh, kl, vh, vl))

@@ -31,6 +31,13 @@ def test_bf16_flavour_op_tests():
     assert " passed" in out and "failed" not in out, out[-800:]
 
 
+def test_bf16_flavour_gemm_f64():
+    """The GEMM family against float64 per element (tests/test_gpu_gemm_f64.py) with bf16 operands: the bars take the flavour's operand
+    contract (tests/gemm_f64.py: e_op), the exact fixtures stay exact."""
+    out = _run([os.path.join("tests", "test_gpu_gemm_f64.py")])
+    assert " passed" in out and "failed" not in out and "skipped" not in out, out[-800:]
+
+
 def test_bf16_flavour_denoise_step_and_gridattn_goldens():
     """One full-width and one reduced-width denoising step, the fused GridAttn at V = 4 and V = 15 and the graph replay, against the
     reference's goldens in the bf16 flavour (MVD_TEST_FULL=1: every step / GridAttn golden, 95 s)."""
