@@ -418,6 +418,27 @@ int mvd_timestep_embedding_scenes(const float* steps, const int* iter, const flo
                                   int steps_scene_stride, mvd_stream_t stream);
 int mvd_advance_iter(int* iter, mvd_stream_t stream);
 
+/* Vectors of a step that depend on the conditioning or on the schedule only: computed once per sample by the step's own launches
+ * (mvd_gemv per <= 16 rows, mvd_timestep_embedding_scenes), so every row is bit-identical to what the step would compute in place.
+ *
+ * mvd_cond_vectors: cc_projection (viewfusion_zero_depth_rgb.py:96-104,322) and the length-1 cross-attention vectors of all layers:
+ *   h1 = SiLU(w0 clip + b0), h2 = SiLU(w2 h1 + b2), context[:rows] = w4 h2 + b4      (rows x width each; clip rows x k_in, ld_clip)
+ *   xvec = wx context + bx over ALL ctx_rows rows of context (rows of the null branch beyond `rows` are read as they are), (ctx_rows, nx).
+ * mvd_step_table: for every row r of `steps` (n_rows x MVD_STEP_STRIDE; row0 points at a device int holding 0):
+ *   tsin[r] = sinusoid(dim) of t_r, h[r] = SiLU(w0 tsin[r] + b0), emb[r] = w2 h[r] + b2 (hidden), and with w3: out3[r] = w3 SiLU(emb[r]) + b3
+ *   (n3) -- ViewFusion.time_embed (w3 NULL) and the UNet's time_embed + row-concatenated emb_layers (unet.py:537-538).
+ * mvd_select_step_rows: d_i[0 .. w_i) = t_i[*iter][0 .. w_i) for up to three tables of n_rows rows (w_i floats, multiples of 4, 16-byte
+ *   aligned; w1 / w2 = 0 skip a table): the one launch of a captured step that picks the row of the device iteration counter.  A counter
+ *   outside [0, n_rows) copies nothing. */
+int mvd_cond_vectors(const float* clip, int ld_clip, int rows, int k_in, int width, const float* w0, const float* b0, const float* w2,
+                     const float* b2, const float* w4, const float* b4, float* h1, float* h2, float* context, const float* wx,
+                     const float* bx, int nx, int ctx_rows, float* xvec, mvd_stream_t stream);
+int mvd_step_table(const float* steps, const int* row0, int n_rows, const float* freqs, int dim, int hidden, const float* w0,
+                   const float* b0, const float* w2, const float* b2, const float* w3, const float* b3, int n3, float* tsin, float* h,
+                   float* emb, float* out3, mvd_stream_t stream);
+int mvd_select_step_rows(const int* iter, int n_rows, const float* t0, float* d0, int w0, const float* t1, float* d1, int w1,
+                         const float* t2, float* d2, int w2, mvd_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * GridAttn: depth-conditioned cross-view aggregation (mvdfusion/view_attn_efficient2.py).
  * Camera record (20 floats): R row-major (9), T (3), focal (2), principal point (2), centre C = -T R^T (3), pad. */

@@ -325,6 +325,27 @@ __global__ void timestep_embedding_kernel(const float* __restrict__ steps, const
   }
 }
 
+// row iter[0] of up to three per-step tables (widths in float4) into the fixed buffers the step's consumers read; one float4 per thread
+__global__ __launch_bounds__(256) void select_step_rows_kernel(const int* __restrict__ iter, int n_rows, const float4* __restrict__ t0,
+                                                               float4* __restrict__ d0, int w0, const float4* __restrict__ t1,
+                                                               float4* __restrict__ d1, int w1, const float4* __restrict__ t2,
+                                                               float4* __restrict__ d2, int w2) {
+  const int r = iter[0];
+  if (r < 0 || r >= n_rows) return;          // (the host keeps iter inside the table: never read past it)
+  int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < w0) {
+    d0[e] = t0[(size_t)r * w0 + e];
+    return;
+  }
+  e -= w0;
+  if (e < w1) {
+    d1[e] = t1[(size_t)r * w1 + e];
+    return;
+  }
+  e -= w1;
+  if (e < w2) d2[e] = t2[(size_t)r * w2 + e];
+}
+
 __global__ void advance_iter_kernel(int* iter) {
   if (threadIdx.x == 0) iter[0] += 1;
 }
@@ -425,6 +446,31 @@ extern "C" int mvd_gemv(const float* W, const float* bias, const float* x, float
     hipLaunchKernelGGL(gemv_kernel<16>, grid, block, 0, s, W, bias, x, y, M, N, K, ldx, ldy, act_in, act_out);
   MVD_CHECK_LAUNCH("mvd_gemv");
   return 0;
+}
+
+// mvd_gemv for any number of rows, 16 at a time: the launches Ctx.gemv_rows issues in the step (same instantiation per chunk)
+static int gemv_rows(const float* W, const float* bias, const float* x, float* y, int rows, int N, int K, int ldx, int ldy, int act_in,
+                     int act_out, mvd_stream_t stream) {
+  for (int r = 0; r < rows; r += 16) {
+    const int rc = mvd_gemv(W, bias, x + (size_t)r * ldx, y + (size_t)r * ldy, rows - r < 16 ? rows - r : 16, N, K, ldx, ldy, act_in,
+                            act_out, stream);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+extern "C" int mvd_cond_vectors(const float* clip, int ld_clip, int rows, int k_in, int width, const float* w0, const float* b0,
+                                const float* w2, const float* b2, const float* w4, const float* b4, float* h1, float* h2, float* context,
+                                const float* wx, const float* bx, int nx, int ctx_rows, float* xvec, mvd_stream_t stream) {
+  MVD_CHECK_ARG(clip && w0 && w2 && w4 && h1 && h2 && context && wx && xvec, "mvd_cond_vectors: null pointer");
+  MVD_CHECK_ARG(rows > 0 && k_in > 0 && width > 0 && nx > 0 && ctx_rows >= rows && ld_clip >= k_in,
+                "mvd_cond_vectors: rows=%d k_in=%d width=%d nx=%d ctx_rows=%d (>= rows) ld_clip=%d (>= k_in)", rows, k_in, width, nx,
+                ctx_rows, ld_clip);
+  int rc = gemv_rows(w0, b0, clip, h1, rows, width, k_in, ld_clip, width, MVD_ACT_NONE, MVD_ACT_SILU, stream);
+  if (!rc) rc = gemv_rows(w2, b2, h1, h2, rows, width, width, width, width, MVD_ACT_NONE, MVD_ACT_SILU, stream);
+  if (!rc) rc = gemv_rows(w4, b4, h2, context, rows, width, width, width, width, MVD_ACT_NONE, MVD_ACT_NONE, stream);
+  if (!rc) rc = gemv_rows(wx, bx, context, xvec, ctx_rows, nx, width, width, nx, MVD_ACT_NONE, MVD_ACT_NONE, stream);
+  return rc;
 }
 
 extern "C" int mvd_unet_input_scenes(const float* x, const float* input_latents, void* out_sp, int nscene, int V, int S, int cpad, int cfg,
@@ -532,6 +578,40 @@ extern "C" int mvd_timestep_embedding_scenes(const float* steps, const int* iter
   hipLaunchKernelGGL(timestep_embedding_kernel, dim3(nscene), dim3(256), 0, (hipStream_t)stream, steps, iter, freqs, out, dim,
                      steps_scene_stride);
   MVD_CHECK_LAUNCH("mvd_timestep_embedding_scenes");
+  return 0;
+}
+
+extern "C" int mvd_step_table(const float* steps, const int* row0, int n_rows, const float* freqs, int dim, int hidden, const float* w0,
+                              const float* b0, const float* w2, const float* b2, const float* w3, const float* b3, int n3, float* tsin,
+                              float* h, float* emb, float* out3, mvd_stream_t stream) {
+  MVD_CHECK_ARG(steps && row0 && freqs && w0 && w2 && tsin && h && emb, "mvd_step_table: null pointer");
+  MVD_CHECK_ARG(n_rows >= 1 && n_rows <= 65535 && dim > 0 && dim % 2 == 0 && hidden > 0, "mvd_step_table: n_rows=%d (1 ... 65535) dim=%d hidden=%d",
+                n_rows, dim, hidden);
+  MVD_CHECK_ARG((w3 == nullptr) == (out3 == nullptr) && (w3 == nullptr || n3 > 0), "mvd_step_table: w3 / out3 / n3 go together");
+  // a row of the table per step row: the sinusoid kernel with one workgroup per row, then the step's own GEMV launches over the rows.  The
+  // step computes its row with gemv_kernel<1>, the table with <16> / <4>: a row's sum is private to its accumulator, and the library is built
+  // with -ffp-contract=off (csrc/build.py), so every instantiation adds the same products in the same order.  That is a property of the
+  // build, not of the language: tests/test_gpu_step_tables.py (rows at both ends of a <16> and a <4> launch against the step's <1>) holds
+  // it bit for bit, and a compiler or flag change that breaks it shows there -- then loop over the rows with M = 1 here.
+  int rc = mvd_timestep_embedding_scenes(steps, row0, freqs, tsin, dim, n_rows, n_rows > 1 ? 1 : 0, stream);
+  if (!rc) rc = gemv_rows(w0, b0, tsin, h, n_rows, hidden, dim, dim, hidden, MVD_ACT_NONE, MVD_ACT_SILU, stream);
+  if (!rc) rc = gemv_rows(w2, b2, h, emb, n_rows, hidden, hidden, hidden, hidden, MVD_ACT_NONE, MVD_ACT_NONE, stream);
+  if (!rc && w3) rc = gemv_rows(w3, b3, emb, out3, n_rows, n3, hidden, hidden, n3, MVD_ACT_SILU, MVD_ACT_NONE, stream);
+  return rc;
+}
+
+extern "C" int mvd_select_step_rows(const int* iter, int n_rows, const float* t0, float* d0, int w0, const float* t1, float* d1, int w1,
+                                    const float* t2, float* d2, int w2, mvd_stream_t stream) {
+  MVD_CHECK_ARG(iter && n_rows >= 1 && t0 && d0 && w0 > 0 && w1 >= 0 && w2 >= 0, "mvd_select_step_rows: bad arguments");
+  MVD_CHECK_ARG((w1 == 0 || (t1 && d1)) && (w2 == 0 || (t2 && d2)), "mvd_select_step_rows: a table with a width needs both pointers");
+  MVD_CHECK_ARG((w0 & 3) == 0 && (w1 & 3) == 0 && (w2 & 3) == 0 && (long long)w0 + w1 + w2 <= 0x3fffffff,
+                "mvd_select_step_rows: widths %d %d %d must be multiples of 4", w0, w1, w2);
+  MVD_CHECK_ARG((((uintptr_t)t0 | (uintptr_t)d0 | (uintptr_t)t1 | (uintptr_t)d1 | (uintptr_t)t2 | (uintptr_t)d2) & 15) == 0,
+                "mvd_select_step_rows: 16-byte alignment");
+  const int total = (w0 + w1 + w2) / 4;
+  hipLaunchKernelGGL(select_step_rows_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, iter, n_rows, (const float4*)t0,
+                     (float4*)d0, w0 / 4, (const float4*)t1, (float4*)d1, w1 / 4, (const float4*)t2, (float4*)d2, w2 / 4);
+  MVD_CHECK_LAUNCH("mvd_select_step_rows");
   return 0;
 }
 

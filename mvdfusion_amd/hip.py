@@ -177,6 +177,9 @@ SIGNATURES = {
     "mvd_timestep_embedding": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "mvd_timestep_embedding_scenes": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvd_advance_iter": (_i, [_vp, _vp]),
+    "mvd_cond_vectors": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "mvd_step_table": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "mvd_select_step_rows": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "mvd_zembed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mvd_gridattn_tokens": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _f, _f, _vp]),
     "mvd_gridattn_tokens_scenes": (_i, [_vp] * 10 + [_i, _i, _i, _i, _i, _i, _f, _f, _vp]),

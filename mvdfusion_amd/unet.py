@@ -273,9 +273,8 @@ class UNetModel(nn.Module):
     def _resblocks(self):
         return [m for m in self.modules() if isinstance(m, ResBlock)]
 
-    def time_biases(self, ctx, t_sin):
-        """emb = time_embed(t_sin); per ResBlock bias = in_layers.2.bias + emb_layers.1(SiLU(emb))  -- one GEMV
-        over the row-concatenated emb_layers weights (unet.py:537-538; openaimodel.py:264-273)."""
+    def temb_weights(self):
+        """(row-concatenated emb_layers weight, bias + in_layers.2.bias, {ResBlock: (lo, hi)}) of all ResBlocks, built once."""
         if self._temb is None:
             blocks = self._resblocks()
             w = torch.cat([b.emb_layers[1].weight.detach() for b in blocks], 0).contiguous()
@@ -285,21 +284,33 @@ class UNetModel(nn.Module):
                 offs[b] = (o, o + b.out_channels)
                 o += b.out_channels
             self._temb = (w, bias, offs)
-        w, bias, offs = self._temb
-        ted = self.model_channels * 4
-        R = t_sin.shape[0]        # one row per scene with per-scene timesteps (training): row n biases the rows of scene n
-        e1, emb = ctx.ws.get("temb.e1", (R, ted)), ctx.ws.get("temb.emb", (R, ted))
+        return self._temb
+
+    def time_bias_buffers(self, ctx, R):
+        """(temb.emb (R, 4 mc), temb.bias (R, sum of the ResBlock widths)): what the ResBlocks (and the training backward) read; binds
+        ctx.emb_bias to the column slices.  R: one row per scene with per-scene timesteps (training), else 1."""
+        w, _, offs = self.temb_weights()
+        emb = ctx.ws.get("temb.emb", (R, self.model_channels * 4))
         out = ctx.ws.get("temb.bias", (R, w.shape[0]))
+        ctx.emb_bias = {b: out[:, lo:hi] for b, (lo, hi) in offs.items()}
+        return emb, out
+
+    def time_biases(self, ctx, t_sin):
+        """emb = time_embed(t_sin); per ResBlock bias = in_layers.2.bias + emb_layers.1(SiLU(emb))  -- one GEMV
+        over the row-concatenated emb_layers weights (unet.py:537-538; openaimodel.py:264-273)."""
+        w, bias, _ = self.temb_weights()
+        R = t_sin.shape[0]        # one row per scene with per-scene timesteps (training): row n biases the rows of scene n
+        e1 = ctx.ws.get("temb.e1", (R, self.model_channels * 4))
+        emb, out = self.time_bias_buffers(ctx, R)
         ctx.gemv_rows(self.time_embed[0].weight, self.time_embed[0].bias, t_sin, e1, act_out=hip.ACT_SILU)
         ctx.gemv_rows(self.time_embed[2].weight, self.time_embed[2].bias, e1, emb)
         ctx.gemv_rows(w, bias, emb, out, act_in=hip.ACT_SILU)
-        ctx.emb_bias = {b: out[:, lo:hi] for b, (lo, hi) in offs.items()}
 
-    def cross_attn_vectors(self, ctx):
+    def xattn_weights(self):
         """attn2 of every SpatialTransformer sees the length-1 CLIP context: softmax over one key is 1, so its output is
         the per-view vector to_out(to_v(context)) (attention.py:170-193 with kv_len 1).  The two linear maps are composed
-        once (W = Wo Wv in fp64, rounded to fp32 -- weight preprocessing like packing) and all 16 layers are evaluated
-        by ONE GEMV per step over the row-concatenated W; each layer takes its column slice as the GEMM bias_b."""
+        once (W = Wo Wv in fp64, rounded to fp32 -- weight preprocessing like packing) and row-concatenated over all 16 layers:
+        (W, bias, {SpatialTransformer: (lo, hi)}, rows of W)."""
         if self._xattn is None:
             sts = [m for m in self.modules() if isinstance(m, SpatialTransformer)]
             ws, bs, offs, o = [], [], {}, 0
@@ -311,18 +322,31 @@ class UNetModel(nn.Module):
                 offs[st] = (o, o + st.in_channels)
                 o += st.in_channels
             self._xattn = (torch.cat(ws, 0).contiguous(), torch.cat(bs, 0).contiguous(), offs, o)
-        w, bias, offs, total = self._xattn
+        return self._xattn
+
+    def xattn_buffer(self, ctx):
+        """xattn.vec (rows of ctx.context, rows of W): each layer takes its column slice as the GEMM bias_b (binds ctx.xattn_vec)."""
+        _, _, offs, total = self.xattn_weights()
         out = ctx.ws.get("xattn.vec", (ctx.context.shape[0], total))
-        ctx.gemv_rows(w, bias, ctx.context, out)
         ctx.xattn_vec = {st: out[:, lo:hi] for st, (lo, hi) in offs.items()}
+        return out
+
+    def cross_attn_vectors(self, ctx):
+        """All 16 layers' vectors by ONE GEMV per step over the row-concatenated W (xattn_weights)."""
+        w, bias, _, _ = self.xattn_weights()
+        ctx.gemv_rows(w, bias, ctx.context, self.xattn_buffer(ctx))
 
     def run(self, ctx, x_in, t_sin, S):
         """x_in: split planes (B*S*S, 2*32) of the channels-last zero-padded input; t_sin: (1, model_channels) sinusoid (or (N, mc): one
-        timestep per scene of a scene-major batch); returns the
-        (B*S*S, 8) head output (first out_channels columns valid)."""
+        timestep per scene of a scene-major batch), None when the caller has filled temb.bias (one row) and xattn.vec itself (StepEngine's
+        per-sample vectors); returns the (B*S*S, 8) head output (first out_channels columns valid)."""
         B = ctx.B
-        self.time_biases(ctx, t_sin)
-        self.cross_attn_vectors(ctx)
+        if t_sin is None:
+            self.time_bias_buffers(ctx, 1)
+            self.xattn_buffer(ctx)
+        else:
+            self.time_biases(ctx, t_sin)
+            self.cross_attn_vectors(ctx)
         hs = []
         H = W = S
         h = x_in

@@ -92,7 +92,15 @@ class StepEngine:
         self.funet = _sinusoid_freqs(model.unet_model.unet_model.model_channels).to(dev)
         self.graphs = {}
         self.prefetchers = {}      # per captured graph: its hip.WeightPrefetcher (None when PREFETCH_WEIGHTS is off)
-        self.drop_masks = None     # training forward: (clip_mask, volume_mask, concat_mask), each (Vq,) in {0, 1} (unet.py:140-151)
+        # per-sample vectors ("Per-sample vectors"): what a step derives from the conditioning or the schedule alone is computed
+        # once per set_conditioning* / set_schedule by the step's own launches (refresh_vectors); the step then copies row `iter` of the
+        # tables (mvd_select_step_rows).  MVD_STEP_TABLES=0: every step computes them in place, as before (A/B runs).
+        self.step_tables = os.environ.get("MVD_STEP_TABLES", "1") != "0"
+        self.iter0 = torch.zeros(1, dtype=torch.int32, device=dev)        # row 0: the tables are built from the top of the step table
+        self._tables = None        # {"c", "emb", "bias" (+ scratch)}: one row per row of self.steps
+        self._cond_sig = None      # (model signature,) the conditioning vectors / the schedule tables were computed under; None: stale
+        self._tab_sig = None
+        self._drop_masks = None    # training forward: (clip_mask, volume_mask, concat_mask), each (Vq,) in {0, 1} (unet.py:140-151)
         self.n_rows = 1            # rows of the device step table; the kernels index steps[iter], noise[iter] unchecked
         self.steps_scene_stride = 0      # 0: one timestep for every scene; 1 (set_schedule_scenes, cfg=False): scene n reads step row iter + n
         self.done = 0              # host mirror of the device iteration counter
@@ -111,6 +119,83 @@ class StepEngine:
             self.in_cam[n:n + 1].copy_(pack_cameras(ic).to(self.cams.device))
             self.input_latents[n:n + 1].copy_(il.reshape(1, 5, S, S))
             self.clip_v_embed[n * V:(n + 1) * V].copy_(ce.reshape(V, 796))
+        self._cond_sig = None
+
+    @property
+    def drop_masks(self):
+        return self._drop_masks
+
+    @drop_masks.setter
+    def drop_masks(self, masks):
+        self._drop_masks = masks
+        if masks is not None:      # the masked step scales self.context in place: whatever refresh_vectors left there is gone
+            self._cond_sig = None
+
+    def invalidate(self):
+        """The weights changed: captured graphs (packed images by address) and the per-sample vectors computed from them are stale."""
+        self.graphs.clear()
+        self.prefetchers.clear()
+        self._cond_sig = self._tab_sig = None
+
+    # -- per-sample vectors ---------------------------------------------------------------------------
+    def tables_apply(self):
+        """The step may read the per-sample vectors: one shared timestep, no condition dropout, no backward behind it, and a schedule of
+        more than one row (a one-row schedule is set anew for every step -- apply_model -- so building its table would cost the step's own
+        launches plus the selection: it stays on the in-place path)."""
+        return self.step_tables and self.steps_scene_stride == 0 and self._drop_masks is None and not self.ctx.keep_fp32 and \
+            int(self.steps.shape[0]) > 1
+
+    def _model_sig(self):
+        # hip.params_signature of the whole model as ViewFusion.engine() last saw it: the check that guards the packed weight images
+        return (getattr(self.m, "_packed_sig", None),)
+
+    def vector_plan(self):
+        """Host mirror of what a graph-replayed step spends on the conditioning / time vectors: (launches in the step, rows of the
+        schedule tables or None where none is built).  In place: 2 sinusoids + 5 GEMVs over the time rows, 3 GEMVs over the conditional
+        rows, 1 over the CFG batch (16 rows per launch); with the per-sample vectors: the one row selection."""
+        if self.tables_apply():
+            return 1, int(self.steps.shape[0])
+        chunks = lambda rows: -(-rows // 16)
+        return 2 + 5 * chunks(self.t_rows) + 3 * chunks(self.N * self.Vq) + chunks(self.B), None
+
+    def vectors_valid(self):
+        sig = self._model_sig()
+        return self.tables_apply() and self._cond_sig == sig and self._tab_sig == sig
+
+    def refresh_vectors(self):
+        """Recompute what is stale: the conditioning vectors (context rows of the conditional branch, xattn.vec) after set_conditioning* /
+        a masked step, the schedule tables (ViewFusion time vector c, UNet emb and per-ResBlock bias row per step row) after
+        set_schedule, both after a weight change.  Called by step() in front of a graph capture or replay, never inside a capture."""
+        m, ctx, L, st = self.m, self.ctx, hip.lib(), hip.stream
+        unet = m.unet_model.unet_model
+        sig = self._model_sig()
+        if self._cond_sig != sig:
+            NVq, p = self.N * self.Vq, m.cc_projection
+            ctx.context = self.context
+            wx, bx, _, nx = unet.xattn_weights()
+            c1, c2 = ctx.ws.get("vf.cc1", (NVq, 768)), ctx.ws.get("vf.cc2", (NVq, 768))
+            clip = self.clip_v_embed[self.q0:self.q0 + NVq]
+            hip.check(L.mvd_cond_vectors(hip.ptr(clip), clip.stride(0), NVq, 796, 768, hip.ptr(p[0].weight), hip.ptr(p[0].bias),
+                                         hip.ptr(p[2].weight), hip.ptr(p[2].bias), hip.ptr(p[4].weight), hip.ptr(p[4].bias), hip.ptr(c1),
+                                         hip.ptr(c2), hip.ptr(self.context), hip.ptr(wx), hip.ptr(bx), nx, self.B,
+                                         hip.ptr(unet.xattn_buffer(ctx)), st()))
+            self._cond_sig = sig
+        if self._tab_sig != sig:
+            n, mc = int(self.steps.shape[0]), unet.model_channels
+            we, be, _ = unet.temb_weights()
+            ted, nb = 4 * mc, int(we.shape[0])
+            T = self._tables
+            if T is None:
+                e = lambda w: torch.empty(n, w, dtype=torch.float32, device=ctx.device)
+                T = self._tables = dict(c=e(256), emb=e(ted), bias=e(nb), tsin=e(256), h=e(256), tsu=e(mc), e1=e(ted))
+            t, u = m.time_embed, unet.time_embed
+            hip.check(L.mvd_step_table(hip.ptr(self.steps), hip.ptr(self.iter0), n, hip.ptr(self.f256), 256, 256, hip.ptr(t[0].weight),
+                                       hip.ptr(t[0].bias), hip.ptr(t[2].weight), hip.ptr(t[2].bias), None, None, 0, hip.ptr(T["tsin"]),
+                                       hip.ptr(T["h"]), hip.ptr(T["c"]), None, st()))
+            hip.check(L.mvd_step_table(hip.ptr(self.steps), hip.ptr(self.iter0), n, hip.ptr(self.funet), mc, ted, hip.ptr(u[0].weight),
+                                       hip.ptr(u[0].bias), hip.ptr(u[2].weight), hip.ptr(u[2].bias), hip.ptr(we), hip.ptr(be), nb,
+                                       hip.ptr(T["tsu"]), hip.ptr(T["e1"]), hip.ptr(T["emb"]), hip.ptr(T["bias"]), st()))
+            self._tab_sig = sig
 
     def set_schedule(self, steps_table, depth_noise, ddim_noise):
         self._set_tables(steps_table, depth_noise, ddim_noise, scene_stride=0)
@@ -138,6 +223,7 @@ class StepEngine:
             self.steps_nodiv = self.steps.clone()
             self.depth_noise = depth_noise.to(dev).contiguous()
             self.ddim_noise = ddim_noise.to(dev).contiguous()
+            self._tables = None                # (one row per step row: re-allocated with them)
         else:
             self.steps.copy_(steps_table)
             self.depth_noise.copy_(depth_noise)
@@ -145,6 +231,7 @@ class StepEngine:
         self.steps_nodiv.copy_(self.steps)
         self.steps_nodiv[:, 1] = 1.0
         self.steps_scene_stride = scene_stride
+        self._tab_sig = None
         self.n_rows = int(steps_table.shape[0]) - (self.N - 1) * scene_stride      # the kernels index steps[iter + n * stride] unchecked
         self.rewind()
 
@@ -209,13 +296,21 @@ class StepEngine:
                                       hip.ptr(self.steps), hip.ptr(self.iter), N, V, K, S, mode, st()))
         # embed_time (:276-279): sinusoid(256) -> Linear -> SiLU -> Linear; only row 0 is used downstream (t[:1]) -- one row per scene
         # when every scene has its own timestep
-        ts = ctx.ws.get("vf.tsin", (R, 256))
-        te1 = ctx.ws.get("vf.te1", (R, 256))
+        unet = m.unet_model.unet_model
+        tabs = self.vectors_valid()    # per-sample vectors: this step only picks its row (refresh_vectors computed them)
         c = ctx.ws.get("vf.c", (R, 256))
-        hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, R, sst,
-                                                  st()))
-        ctx.gemv_rows(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
-        ctx.gemv_rows(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
+        if tabs:
+            T = self._tables
+            emb, bias = unet.time_bias_buffers(ctx, 1)
+            hip.check(L.mvd_select_step_rows(hip.ptr(self.iter), int(T["c"].shape[0]), hip.ptr(T["c"]), hip.ptr(c), 256, hip.ptr(T["emb"]),
+                                             hip.ptr(emb), emb.shape[1], hip.ptr(T["bias"]), hip.ptr(bias), bias.shape[1], st()))
+        else:
+            ts = ctx.ws.get("vf.tsin", (R, 256))
+            te1 = ctx.ws.get("vf.te1", (R, 256))
+            hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.f256), hip.ptr(ts), 256, R, sst,
+                                                      st()))
+            ctx.gemv_rows(m.time_embed[0].weight, m.time_embed[0].bias, ts, te1, act_out=hip.ACT_SILU)
+            ctx.gemv_rows(m.time_embed[2].weight, m.time_embed[2].bias, te1, c)
         # view-aligned features (:303-313)
         dsrc, dsteps = self.depth_geo()
         m.view_attn.run(ctx, self.x, self.depth_noise, self.steps, self.iter, self.cams, self.in_cam,
@@ -223,12 +318,13 @@ class StepEngine:
                         vol_planes_col=self.vol_col, depth_src=None if self.depth_mode == 0 else dsrc,
                         depth_steps=None if self.depth_mode == 0 else dsteps, scenes=N, steps_scene_stride=sst)
         # cc_projection (:322)
-        p = m.cc_projection
-        c1 = ctx.ws.get("vf.cc1", (NVq, 768))
-        c2 = ctx.ws.get("vf.cc2", (NVq, 768))
-        ctx.gemv_rows(p[0].weight, p[0].bias, self.clip_v_embed[q0:q0 + NVq], c1, act_out=hip.ACT_SILU)
-        ctx.gemv_rows(p[2].weight, p[2].bias, c1, c2, act_out=hip.ACT_SILU)
-        ctx.gemv_rows(p[4].weight, p[4].bias, c2, self.context[:NVq])
+        if not tabs:
+            p = m.cc_projection
+            c1 = ctx.ws.get("vf.cc1", (NVq, 768))
+            c2 = ctx.ws.get("vf.cc2", (NVq, 768))
+            ctx.gemv_rows(p[0].weight, p[0].bias, self.clip_v_embed[q0:q0 + NVq], c1, act_out=hip.ACT_SILU)
+            ctx.gemv_rows(p[2].weight, p[2].bias, c1, c2, act_out=hip.ACT_SILU)
+            ctx.gemv_rows(p[4].weight, p[4].bias, c2, self.context[:NVq])
         if self.drop_masks is not None:        # UNetWrapper.forward(is_train=True) condition dropout (eager only, never captured)
             clip_m, vol_m, cat_m = self.drop_masks          # (N*Vq,) each, scene-major
             self.context[:NVq] *= clip_m[:, None]
@@ -245,11 +341,12 @@ class StepEngine:
             cm = self.drop_masks[2].to(torch.int16)[:, None, None]
             xin[:NVq, :, 5:10] *= cm
             xin[:NVq, :, 37:42] *= cm
-        unet = m.unet_model.unet_model
         ctx.vol_levels = m.unet_model.volume_pyramid(ctx, self.vol.view(B, S, S, D, 768), B, S, D)
-        tsu = ctx.ws.get("vf.tsin_unet", (R, unet.model_channels))
-        hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
-                                                  unet.model_channels, R, sst, st()))
+        tsu = None                     # (with the per-sample vectors temb.bias and xattn.vec are filled already)
+        if not tabs:
+            tsu = ctx.ws.get("vf.tsin_unet", (R, unet.model_channels))
+            hip.check(L.mvd_timestep_embedding_scenes(hip.ptr(self.steps), hip.ptr(self.iter), hip.ptr(self.funet), hip.ptr(tsu),
+                                                      unet.model_channels, R, sst, st()))
         y = unet.run(ctx, self.x_in, tsu, S)
         hip.check(L.mvd_cfg_ddim_update(hip.ptr(y), 8, hip.ptr(xq), hip.ptr(x0q), hip.ptr(epsq),
                                         hip.ptr(self.ddim_noise[:, q0:q0 + NVq]), N * V * 5 * S * S, hip.ptr(self.steps),
@@ -263,14 +360,17 @@ class StepEngine:
         return self.N if self.steps_scene_stride else 1
 
     def step(self, cfg_scale, do_update, use_graph=True):
-        key = (float(cfg_scale), bool(do_update), int(self.depth_mode), self.steps_scene_stride, self.pin)
+        tabs = self.tables_apply()
+        key = (float(cfg_scale), bool(do_update), int(self.depth_mode), self.steps_scene_stride, self.pin, tabs)
         if self.done >= self.n_rows:
             raise IndexError(f"StepEngine.step: iteration {self.done} is past the {self.n_rows}-row step table "
                              "(set_schedule() / rewind() before stepping again)")
         if do_update:
             self.done += 1
-        if not use_graph:
+        if not use_graph:              # (an eager step reads the per-sample vectors while they are valid, else computes them in place)
             return self.enqueue(cfg_scale, do_update)
+        if tabs:                       # a graph is captured and replayed with valid vectors only: it holds no launch that computes them
+            self.refresh_vectors()
         g = self.graphs.get(key)
         if g is None:
             # first call runs eagerly (allocates every workspace buffer, packs weights), then capture
@@ -444,8 +544,7 @@ class ViewFusion(nn.Module):
         hip.forget_param_maxima()          # (engine() measures them again before anything is packed for a step)
         if keep_engines:
             for e in self._engines.values():
-                e.graphs.clear()
-                e.prefetchers.clear()
+                e.invalidate()
         else:
             self._engines.clear()
 
